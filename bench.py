@@ -22,7 +22,8 @@ resident in HBM (what `value` was in rounds 1-2), with the `roofline` objects at
 The N = 1 line's legs: the hot path + its verification, the e2e leg (`value`), `cpu_baseline` (the reference's own
 alignToDatabase compiled in place, timed on the host cores; oracle/ is used by this leg only) and `strong_n1` (the N > 1
 lines' workload on this one GPU).  More evidence on request: --legs abi_path,other_sink,null_sink,pseudo | all.
-The legs themselves: bench_legs.py.
+The legs themselves: bench_legs.py.  --dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy, so that two
+builds can be compared output for output (the inputs are seeded: the same arguments give the same inputs).
 
 Prints ONE JSON line on rank 0 (the driver contract of the task statement).
 """
@@ -240,6 +241,79 @@ def cpu_baseline(K, db, offs, seed, n_genomes, n_pairs, read_len=READ_LEN, devic
     return out
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+# What is kept is chosen by the batch's read and pair indices, which the arguments alone set, so that the files of two builds
+# line up row for row where the builds agree.  Largest case: 8 x (11 x DUMP_ROWS + DUMP_OPS + DUMP_READS + 2 x DUMP_PAIRS)
+# + 4 x 1.5 x DUMP_TAIL_BYTES = 31 MB, under the 64 MB the files may take.
+DUMP_READS = 1 << 15             # reads whose overlap records are kept (a fixed, seeded sample of the batch's reads)
+DUMP_ROWS = 1 << 17              # at most this many of their records (whole reads: the first sampled reads that fit)
+DUMP_OPS = 1 << 19               # at most this many of their CIGAR ops (the first)
+DUMP_PAIRS = 1 << 17             # read pairs whose taxa are kept
+DUMP_TAIL_BYTES = 1 << 21        # the end of the SAM text (and half as much of the _PerRead text)
+DUMP_SEED = 20240611
+OVERLAP_DT = entry.load_package().OVERLAP_DT
+OVERLAP_COLUMNS = ("read", "entry", "rel", "revcomp", "score", "ref_begin", "ref_end", "query_begin", "query_end",
+                   "cigar_len", "cigar_off")
+
+
+def seeded_sample(n, k):
+    """a fixed, seeded, sorted sample of k of range(n) (all of it when n <= k)"""
+    return np.arange(n) if n <= k else np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+
+
+def clear_dump(d):
+    """d exists and holds none of the files of an earlier run (another run's e2e_* beside this run's hot_path_*)"""
+    os.makedirs(d, exist_ok=True)
+    for f in os.listdir(d):
+        if f.endswith(".npy") and f.startswith(("hot_path_", "e2e_")):
+            os.unlink(os.path.join(d, f))
+
+
+def write_dump(d, arrays):
+    """arrays {name: float32 / float64 ndarray} -> d/<name>.npy"""
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def dump_hot_path(d, ov, cg, n_reads):
+    """One step's alignToDatabase result on the device (ov: the overlap records, 48 bytes each in (read, entry, rel) order;
+    cg: the CIGAR ops, 4 bytes each; both uint8 tensors) of a batch of n_reads reads -> hot_path_*.npy, float64 (exact for
+    these integers): the counts, the sampled reads whose records are kept, every column of those records and their CIGAR
+    ops.  The records are picked on the device; only they and their ops come to the host."""
+    n = ov.numel() // 48
+    reads = seeded_sample(n_reads, DUMP_READS)
+    read_col = ov[:n * 48].view(torch.int32).view(n, 12)[:, 0]
+    keep = torch.isin(read_col, torch.from_numpy(reads.astype(np.int32)).to(ov.device)).nonzero().flatten()[:DUMP_ROWS + 1]
+    rows = np.frombuffer(ov[:n * 48].view(n, 48)[keep].cpu().numpy(), dtype=OVERLAP_DT)
+    if len(rows) > DUMP_ROWS:        # the read the cut falls in goes, and every sampled read after it
+        cut = rows["read"][DUMP_ROWS]
+        rows, reads = rows[rows["read"] < cut], reads[reads < cut]
+    lens = rows["cigar_len"].astype(np.int64)
+    first = np.cumsum(lens) - lens
+    at = (np.repeat(rows["cigar_off"].astype(np.int64) - first, lens) + np.arange(int(lens.sum()), dtype=np.int64))[:DUMP_OPS]
+    ops = cg.view(torch.int32)[torch.from_numpy(at).to(cg.device)].cpu().numpy().view(np.uint32)
+    out = {"hot_path_counts": np.array([n, cg.numel() // 4], dtype=np.float64), "hot_path_sampled_reads": reads.astype(np.float64),
+           "hot_path_cigar_of_sampled_rows": ops.astype(np.float64)}
+    for f in OVERLAP_COLUMNS:
+        out["hot_path_" + f] = rows[f].astype(np.float64)
+    write_dump(d, out)
+
+
+def dump_e2e(d, pairs, res, sam_path, pr_path):
+    """The e2e leg's last batch of `pairs` read pairs (res: the last repetition's result, its files still in place) ->
+    e2e_*.npy: the taxa of a seeded sample of the batch's read pairs (float64), the sizes of the two files (float64) and the
+    last bytes of each (float32)."""
+    pick = seeded_sample(pairs, DUMP_PAIRS)
+    out = {"e2e_sampled_pairs": pick.astype(np.float64), "e2e_tax_ids": res["tax_ids"][-pairs:][pick].astype(np.float64),
+           "e2e_file_bytes": np.array([os.path.getsize(sam_path), os.path.getsize(pr_path)], dtype=np.float64)}
+    for name, path, n in (("e2e_sam_text_end", sam_path, DUMP_TAIL_BYTES), ("e2e_per_read_text_end", pr_path, DUMP_TAIL_BYTES // 2)):
+        with open(path, "rb") as f:
+            f.seek(max(0, os.path.getsize(path) - n))
+            out[name] = np.frombuffer(f.read(), dtype=np.uint8).astype(np.float32)
+    write_dump(d, out)
+
+
 # ------------------------------------------------------------------------------------------------ the legs (bench_legs.py)
 from bench_legs import (FastqFiles, abi_path, cgroup_throttled_ms, choose_sink, e2e_leg, fresh_file, ids_view, solo_strong,  # noqa: E402
                         usable_cpus)
@@ -294,6 +368,11 @@ def main():
     ap.add_argument("--strong-reference", choices=["auto", "on", "off"], default=None, help=argparse.SUPPRESS)   # round 5 spelling of --strong-n1
     ap.add_argument("--total-pairs", type=int, default=10_000_000,
                     help="pairs per batch in --strong mode (the reference's --num-reads-at-once default, src/main.cpp:56)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (rank 0; float32 / float64, at "
+                         "most 64 MB, seeded samples of larger results): hot_path_* = the hot path's overlap records and CIGAR ops "
+                         "(the merged batch with --strong), e2e_* = the e2e leg's last batch (per-read-pair taxa, the end of the SAM "
+                         "and _PerRead texts)")
     args = ap.parse_args()
     if args.strong_reference == "off":
         args.strong_n1 = "off"
@@ -574,6 +653,16 @@ def main():
         elapsed = max(float(a[0]) for a in allr)
         split_max = {k: max(float(a[1 + i]) for a in allr) for i, k in enumerate(sorted(split))}
         per_rank_align = [round(float(a[1 + sorted(split).index("align")]) / args.steps * 1e3, 3) for a in allr]
+    if args.dump_outputs and rank == 0:
+        clear_dump(args.dump_outputs)
+        if strong and "ov" in merged:          # the batch-global result rank 0 holds
+            dump_hot_path(args.dump_outputs, merged["ov"], merged["cg"], 2 * args.total_pairs)
+        else:
+            ov = torch.empty(n_out * 48, dtype=torch.uint8, device=dev)
+            cg = torch.empty(max(n_cig, 1) * 4, dtype=torch.uint8, device=dev)
+            ctx.copy_results_device(ov.data_ptr(), cg.data_ptr())
+            dump_hot_path(args.dump_outputs, ov, cg[:n_cig * 4], n_reads)
+            del ov, cg
 
     # ---- outside the timed region: is what was just timed RIGHT?  (no oracle here: the generator's
     # own ground truth, the reference's structural expectations of src/Tests.h:161-264, :321-330) ----
@@ -1196,7 +1285,8 @@ def main():
             del batches
             torch.cuda.empty_cache()
             taxdb = X.TaxDB(tax_text)
-            e2e = e2e_leg(K, ctx, files, pairs, index_view, taxdb, Ksteps, args.warmup, pseudo, out_dir=args.out_dir)
+            e2e = e2e_leg(K, ctx, files, pairs, index_view, taxdb, Ksteps, args.warmup, pseudo, out_dir=args.out_dir,
+                          dump=(lambda res, sam, pr: dump_e2e(args.dump_outputs, pairs, res, sam, pr)) if args.dump_outputs else None)
             out["e2e"] = e2e
             if sink_probe:
                 out["sink_probe"] = {"GB_per_s_of_a_new_256MB_file": sink_probe, "chosen": args.out_dir}

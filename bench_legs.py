@@ -130,8 +130,10 @@ def choose_sink(out_dir, need_bytes):
     return max(probes, key=probes.get), probes
 
 
-def e2e_leg(K, ctx, files, pairs_per_batch, index_view, taxdb, steps, warmup, pseudo, reps=3, tag="e2e", out_dir="/dev/shm", native=True):
-    """K steps of the reference's batch loop, FASTQ text in host memory to SAM + _PerRead files in out_dir."""
+def e2e_leg(K, ctx, files, pairs_per_batch, index_view, taxdb, steps, warmup, pseudo, reps=3, tag="e2e", out_dir="/dev/shm", native=True,
+            dump=None):
+    """K steps of the reference's batch loop, FASTQ text in host memory to SAM + _PerRead files in out_dir.
+    dump(result, sam_path, per_read_path) is called on the last repetition before its files are removed."""
     S = importlib.import_module("kslam_amd.stream")
     T = importlib.import_module("kslam_amd.tail")
     X = importlib.import_module("kslam_amd.taxonomy")
@@ -194,6 +196,8 @@ def e2e_leg(K, ctx, files, pairs_per_batch, index_view, taxdb, steps, warmup, ps
         walls = sorted(r["wall"] for r in runs)
         med = runs[[r["wall"] for r in runs].index(walls[len(walls) // 2])]
         last = runs[-1]
+        if dump is not None:
+            dump(last, sam_path, pr_path)
         # end of run (src/SLAM.h:255-265): the abbreviated table and the XML report over all batches
         t0 = time.perf_counter()
         summary = taxdb.summary(last["tax_ids"], last["pairs"])

@@ -5,6 +5,7 @@ import os
 import re
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -241,14 +242,30 @@ def test_routed_pseudo_assembly_protocol_gloo(tmp_path, world, decline):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, OMP_NUM_THREADS="1")
     if decline is not None:
         env["DECLINE_ON"] = str(decline)
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=%d" % world,
-                        "--master-addr", "127.0.0.1", "--master-port", port, str(script)],
-                       env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    # the ranks are started here rather than by torch.distributed.run: without the launcher's process, 5 ranks and this
+    # process stay within the 6 processes that may have a GPU box's device open at once
+    # each rank writes to files of its own: no rank can block on a full pipe while another waits for it in a collective
+    logs = [(tmp_path / ("rank%d.out" % r), tmp_path / ("rank%d.err" % r)) for r in range(world)]
+    procs = []
+    for r, (out, err) in enumerate(logs):
+        with open(out, "w") as fo, open(err, "w") as fe:
+            procs.append(subprocess.Popen([sys.executable, str(script)], env=dict(env, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world)),
+                                          stdout=fo, stderr=fe))
+    deadline = time.time() + 300
+    try:
+        for p in procs:
+            p.wait(timeout=max(1.0, deadline - time.time()))
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+                p.wait()
+    stdout, stderr = "".join(o.read_text() for o, _ in logs), "".join(e.read_text() for _, e in logs)
+    assert all(p.returncode == 0 for p in procs), stdout[-2000:] + stderr[-2000:]
     if decline is None:
-        assert r.stdout.count("ROUTED_OK") == world
+        assert stdout.count("ROUTED_OK") == world
     else:
-        assert r.stdout.count("ROUTED_DECLINED") == world and "ROUTED_OK" not in r.stdout
+        assert stdout.count("ROUTED_DECLINED") == world and "ROUTED_OK" not in stdout
 
 
 @pytest.mark.parametrize("header", ["kslam.h", "kslam_tail.h", "kslam_fastq.h", "kslam_taxonomy.h", "kslam_db.h", "kslam_stream.h", "kslam_comm.h", "kslam_samtext.h"])
