@@ -157,6 +157,10 @@ void build_index(kslam_ctx *c) {
   uint32_t fb = 20;
   while (fb < 35 && ((uint64_t)1 << fb) < m * 12) fb++;
   if (c->tune.filter_bits >= 0) fb = (uint32_t)c->tune.filter_bits;
+  // filter.hip takes line_bits = fb - 10 unsigned and blocks of 2^11 pieces: below 2^20 bits that would wrap
+  // (read_tuning clamps KSLAM_FILTER_BITS to [20, 36], the automatic size starts at 20)
+  if (fb != 0 && fb < 20)
+    throw StatusError{KSLAM_ERR_INTERNAL, "membership filter of 2^" + std::to_string(fb) + " bits: the smallest is 2^20"};
   c->filter_bits = fb;
   if (fb) c->g_filter.ensure(filter_bytes(fb));
   // the probe words of the filter's build go through the record buffers of the sort that has just finished: the one that does not

@@ -868,6 +868,7 @@ def test_filter_built_block_by_block_equals_the_atomic_build(kslam, oracle, synt
     ordered by block, instead of four scattered atomics per key.  Same bits: the same read k-mers survive (count) and the
     same alignments come out, for a filter of several blocks, for KSLAM_FILTER_BITS at its smallest, for an index with
     repeated keys and k-mer 0 (poly-A), and for an index without a single k-mer."""
+    from filter_ref import expected_survivors
     rng = np.random.default_rng(99)
     genomes = [synth.random_bases(rng, 300000) for _ in range(3)] + [np.frombuffer(b"A" * 500, dtype=np.uint8).copy()]
     genomes.append(np.concatenate([genomes[0][1000:3000], genomes[1][500:900]]))             # repeated keys
@@ -895,6 +896,8 @@ def test_filter_built_block_by_block_equals_the_atomic_build(kslam, oracle, synt
             monkeypatch.delenv("KSLAM_FILTER_BUILD", raising=False)
             monkeypatch.delenv("KSLAM_FILTER_BITS", raising=False)
         assert kept["blocks"] == kept["atomics"] and 0 < kept["blocks"] < 0.5 * len(rb) * 119, (bits, kept)
+        # both builds share probe_of: hold them to the CPU restatement of the filter, survivor for survivor
+        assert kept["blocks"] == expected_survivors(rb, gb, bits, 511)[1], (bits, kept)
     c = kslam.Context()
     c.set_index([b"ACGT" * 5, b""])                   # no entry reaches 32 bases: no k-mer, an empty filter
     got, gcig = c.align_batch(rb[:50])
