@@ -5,6 +5,8 @@ Bit-exact bar: every integer field and every CIGAR op must be identical.
 import numpy as np
 import pytest
 
+from align_compare import compare_alignments as _compare_alignments
+
 pytestmark = pytest.mark.gpu
 
 
@@ -85,18 +87,6 @@ def test_find_overlaps_parity(kslam, oracle, synth):
     assert len(got) == len(exp)
     for f in ("read", "entry", "rel", "revcomp"):
         assert (got[f] == exp[f]).all(), f
-
-
-def _compare_alignments(got, gcig, exp, ecig):
-    assert len(got) == len(exp)
-    for f in ("read", "entry", "rel", "revcomp", "score", "ref_begin", "ref_end", "query_begin",
-              "query_end", "cigar_len"):
-        bad = np.nonzero(got[f] != exp[f])[0]
-        assert len(bad) == 0, "%s differs at %s: got %s exp %s" % (f, bad[:5], got[bad[:5]], exp[bad[:5]])
-    for i in range(len(got)):
-        a = gcig[int(got["cigar_off"][i]):int(got["cigar_off"][i]) + int(got["cigar_len"][i])]
-        b = ecig[int(exp["cigar_off"][i]):int(exp["cigar_off"][i]) + int(exp["cigar_len"][i])]
-        assert (a == b).all(), "cigar %d" % i
 
 
 @pytest.mark.parametrize("case", ["default", "nocigar", "threshold", "edges", "indels", "len250", "len100"])
