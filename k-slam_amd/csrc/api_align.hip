@@ -11,6 +11,17 @@ __global__ void k_lens(const uint64_t *off, uint64_t n, uint32_t *len) {
   if (i < n) len[i] = (uint32_t)(off[i + 1] - off[i]);
 }
 
+// the tuning of a chunk's CIGAR stage: a chunk of long reads puts every CIGAR on the literal one-lane kernel (the others
+// are sized by template)
+static Tuning cigar_tuning(const Tuning &t, bool long_chunk) {
+  Tuning r = t;
+  if (long_chunk) {
+    r.cigar_sys_mask = 0;
+    r.cigar_reg = false;
+  }
+  return r;
+}
+
 void finish_load_reads(kslam_ctx *c) {
   hipStream_t s = c->stream;
   const uint64_t n = c->n_reads;
@@ -158,12 +169,7 @@ void align_resident(kslam_ctx *c, bool stop_after_join, uint64_t *n_raw_out, Pai
       lmax_chunk = 0;
       for (uint64_t i = r0; i < r1; i++) lmax_chunk = std::max<uint32_t>(lmax_chunk, (uint32_t)(c->h_roff[i + 1] - c->h_roff[i]));
     }
-    Tuning tune_chunk = c->tune;
-    if (long_chunk) {   // every CIGAR of such a chunk on the literal one-lane kernel (the others are sized by template)
-      tune_chunk.cigar_sys_mask = 0;
-      tune_chunk.cigar_reg = false;
-      tune_chunk.cigar_dirs_lds = false;
-    }
+    const Tuning tune_chunk = cigar_tuning(c->tune, long_chunk);
     const uint64_t nk_all = kp[r1] - kp[r0], nsegs = c->h_spre[r1] - c->h_spre[r0];
     if (nk_all >= (1ull << 32)) throw StatusError{KSLAM_ERR_UNSUPPORTED, "a single read chunk exceeds 2^32 k-mers"};
     const uint64_t nr = r1 - r0;
@@ -356,9 +362,7 @@ void align_resident(kslam_ctx *c, bool stop_after_join, uint64_t *n_raw_out, Pai
       uint64_t ncig = 0;
       uint32_t tb_err = 0;
       cigar_prepare(c->cig, d.m, s);
-      Tuning tune_d = c->tune;
-      if (d.long_chunk) { tune_d.cigar_sys_mask = 0; tune_d.cigar_reg = false; tune_d.cigar_dirs_lds = false; }
-      cigar_traceback(cand, d.m, in, sp, d.lmax, band0, c->cig, &ncig, &tb_err, tune_d, s);
+      cigar_traceback(cand, d.m, in, sp, d.lmax, band0, c->cig, &ncig, &tb_err, cigar_tuning(c->tune, d.long_chunk), s);
       tb_err_total += tb_err;
       ensure_keep(c->res_cig, (c->n_cig + ncig + 1) * sizeof(uint32_t), c->n_cig * sizeof(uint32_t), s);
       cigar_finalize(cand, d.m, in, d.lmax, c->cig, band0, c->res_cig.as<uint32_t>(), c->n_cig, c->cells.as<uint64_t>(), s);

@@ -48,8 +48,7 @@ __global__ void k_class_flags(const uint32_t *__restrict__ bw, const uint8_t *__
   const uint32_t b = bw[i];
   uint32_t f = 0;
   if (b != 0 && !(b >> 31)) {   // bit 31: inline <n>M set by the SW kernel
-    if (big == 1) f = needbig[i] ? 1u : 0u;
-    else if (big == 2) f = (needbig[i] == 3 && band_class(b) == cls) ? 1u : 0u;   // sent back by the systolic kernel
+    if (big) f = needbig[i] ? 1u : 0u;
     else f = (!needbig[i] && band_class(b) == cls) ? 1u : 0u;
   }
   flags[i] = f;
@@ -88,14 +87,7 @@ struct CigJob {
   uint32_t *bw;
   int32_t *bmax;
   uint8_t *needbig;
-  const uint32_t *list;
-  uint32_t m;           // list entries in this launch (with m_dev: the launch's CAPACITY)
-  const uint32_t *m_dev = nullptr;   // the list's length on the device, read when the kernel runs: this launch covers entries
-                                     // [list_base, min(list_base + m, *m_dev)) -- a bin's list is still growing when the host sizes its launch
-  uint32_t m_sure = 0;               // entries of this launch the host KNEW to exist: a workgroup inside them does not wait for *m_dev
-  uint32_t list_base;   // first list entry of this launch
-  uint32_t slot_bw;     // band width the scratch slab is sized for
-  uint32_t lmax;        // max read length (row count bound)
+  ListSlice items;      // the candidates of this launch; list position li is entry items.first + li
   uint32_t cap;         // cigar ops per temp slot
   uint32_t *tmp;        // temp cigar slots: normal: [candidate][cap]; big: [list pos][cap]
   uint32_t big;
@@ -107,48 +99,12 @@ struct CigJob {
 #else
   static constexpr uint32_t variant = 0;   // compiled out of the product build
 #endif
-  // where candidates go that are not finished by this launch (nullptr: the host re-lists by flags)
-  uint32_t *bin_list[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // band doubled: the list of its new bin
-  uint32_t *bin_count = nullptr;                                // [8] (nullptr: the host re-lists by flags)
-  uint32_t *special_list = nullptr, *special_count = nullptr;   // handed back by the systolic kernel
+  // where candidates go that are not finished by this launch
+  BinLists bins = {};           // band doubled: the list of its new bin (bins.count nullptr: the host re-lists by flags)
+  uint32_t *special_list = nullptr, *special_count = nullptr;   // handed over to the one-lane kernel
   uint32_t *big_count = nullptr;                                // cigar longer than the small temp slot
-  // systolic kernels: which list positions' attempts reached the score, for k_systolic_traceback (nullptr: the
-  // group's lane 0 walks the traceback itself, at the end of the DP kernel)
-  uint8_t *tb_flag = nullptr;   // [m], zeroed: 1 = this list position's attempt reached the score
+  uint8_t *tb_flag = nullptr;   // systolic kernels: [items.cap], zeroed: 1 = this list position's attempt reached the score
 };
-
-// list entries this launch really has (CigJob::m_dev)
-// (hi: one past the last entry the calling workgroup looks at)
-__device__ inline uint32_t live_entries(const CigJob &J, uint32_t hi) {
-  if (!J.m_dev || hi <= J.m_sure) return J.m;
-  const uint32_t tot = *J.m_dev;
-  return min(J.m, tot > J.list_base ? tot - J.list_base : 0u);
-}
-
-// wave-aggregated append of candidate ci to a list (one atomic per wave)
-__device__ inline void append_candidate(bool want, uint32_t ci, uint32_t *list, uint32_t *count) {
-  const uint64_t m = __ballot(want);
-  if (!m) return;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t leader = (uint32_t)__builtin_ctzll(m);
-  uint32_t base = 0;
-  if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(m));
-  base = __shfl((int)base, (int)leader, 64);
-  if (want) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = ci;
-}
-
-// the same for a candidate whose band doubled: into the list of its new bin (lanes of a wave may differ in that)
-__device__ inline void append_doubled(const CigJob &J, bool want, uint32_t ci, uint32_t new_bw) {
-  if (!J.bin_count) return;
-  const uint32_t b = cig_bin(new_bw);
-  for (;;) {
-    const uint64_t m = __ballot(want);
-    if (!m) break;
-    const uint32_t b0 = (uint32_t)__shfl((int)b, (int)__builtin_ctzll(m), 64);
-    append_candidate(want && b == b0, ci, J.bin_list[b0], J.bin_count + b0);
-    want = want && b != b0;
-  }
-}
 
 __global__ void k_cig_class(const uint32_t *__restrict__ bw, uint64_t n, uint8_t *__restrict__ cls) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -169,7 +125,6 @@ struct LdsLayout {
   uint32_t nch;      // 16-base chunks a sequence buffer holds per lane (stage_codes_wave)
   uint32_t W1;       // row array length (2 * slot_bw + 4)
   uint32_t wd;       // direction cells per row the global slab is sized for (2 * slot_bw + 1)
-  uint32_t wpr;      // direction words per row kept in LDS (six 5-bit cells per word); 0: global slab
 };
 
 // Staging for the one-candidate-per-lane kernels, by the whole wave.  (It used to be lane-private: every lane walked
@@ -319,11 +274,9 @@ __device__ inline int32_t banded_attempt_reg(Seq &m, uint32_t *DW, uint32_t NL, 
   return mx;
 }
 
-// One candidate per lane.  LDS ([element][lane]): translated spans + the three row arrays, and,
-// for the narrow bands nearly every candidate needs, the direction matrix itself: 5 bits per band
-// cell, six cells per word, so the traceback -- a chain of dependent loads, one per step -- runs
-// at LDS latency.  Wider bands keep the directions in a global slab per block ([cell][lane],
-// coalesced, L2 resident), written fire-and-forget during the DP.
+// One candidate per lane.  LDS ([element][lane]): translated spans + the three row arrays.  The
+// directions go to a global slab per block ([cell][lane], coalesced, L2 resident), written
+// fire-and-forget during the DP.
 template <int REG_BW>   // 0: rows in LDS, any band; 1 / 2 / 4: bands up to that width in registers
 __global__ __launch_bounds__(64) void k_banded_lds(CigJob J, SwInputs in, SwParams p, LdsLayout Y) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
@@ -331,13 +284,11 @@ __global__ __launch_bounds__(64) void k_banded_lds(CigJob J, SwInputs in, SwPara
   const uint32_t lane = threadIdx.x;
   const uint32_t NL = Y.nl;
   const uint32_t li = blockIdx.x * NL + lane;
-  const bool have = lane < NL && li < live_entries(J, (blockIdx.x + 1) * NL);
+  const bool have = lane < NL && li < live_len(J.items, (blockIdx.x + 1) * NL);
   const uint32_t half = Y.nch * NL * 8u;   // bytes per packed sequence buffer
   uint8_t *SQ = lds_raw;
   uint8_t *SR = SQ + half;
   int16_t *S = reinterpret_cast<int16_t *>(lds_raw + (size_t)2 * half);
-  uint32_t *DW = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(S) +
-                                              (((size_t)3 * Y.W1 * NL * sizeof(int16_t) + 15) & ~(size_t)15));
   uint8_t *D = J.scratch + (uint64_t)blockIdx.x * J.wave_slab;
 
   uint32_t ci = 0;
@@ -347,7 +298,7 @@ __global__ __launch_bounds__(64) void k_banded_lds(CigJob J, SwInputs in, SwPara
   bool skip = !have;
   const uint8_t *qsrc = in.read_codes, *rsrc = in.genome_codes;
   if (have) {
-    ci = J.list[J.list_base + li];
+    ci = J.items.list[J.items.first + li];
     o = J.ov[ci];
     if (J.needbig[ci] == 3) J.needbig[ci] = 0;   // handed over by the systolic kernel
     band_width = (int32_t)J.bw[ci];
@@ -377,7 +328,7 @@ __global__ __launch_bounds__(64) void k_banded_lds(CigJob J, SwInputs in, SwPara
     // instantiation keeps no row arrays: to the one-lane kernel (the whole wave takes part in the append)
     const bool hand = !skip && !(band_width <= REG_BW && refLen > 2 * band_width + 1);
     if (hand) J.needbig[ci] = 3;
-    append_candidate(hand, ci, J.special_list, J.special_count);
+    wave_append(hand, ci, J.special_list, J.special_count);
     skip = skip || hand;
   }
   if (J.variant == 4) return;   // ablation: candidate header loads only
@@ -401,16 +352,9 @@ __global__ __launch_bounds__(64) void k_banded_lds(CigJob J, SwInputs in, SwPara
     }
     __device__ uint32_t q(int32_t i) { return code(SQ, (uint32_t)(i + oq), NL, lane); }
     __device__ uint32_t r(int32_t j) { return code(SR, (uint32_t)(j + orf), NL, lane); }
-    uint32_t *DW, wpr, acc;             // LDS direction words: [row * wpr + word][lane]
-    __device__ void set_dir(int32_t i, int32_t col, uint32_t v) {
-      if (wpr) {
-        const uint32_t w = (uint32_t)col / 6u, sh = 5u * ((uint32_t)col - 6u * w);
-        acc = sh ? (acc | (v << sh)) : v;   // cells of a row arrive in column order: the word is complete
-        DW[((uint32_t)i * wpr + w) * NL + lane] = acc;   // after its last cell, no read-modify-write needed
-      } else
-        D[((size_t)i * width_d + (uint32_t)col) * NL + lane] = (uint8_t)v;
-    }
-    int32_t reg_bw = 0;                 // > 0: the words hold band slots (banded_attempt_reg), not columns
+    __device__ void set_dir(int32_t i, int32_t col, uint32_t v) { D[((size_t)i * width_d + (uint32_t)col) * NL + lane] = (uint8_t)v; }
+    uint32_t *DW = nullptr;             // register variant: direction words (i / 6, band slot) in the slab (banded_attempt_reg)
+    int32_t reg_bw = 0;                 // > 0: the words hold band slots, not columns
     uint32_t nx = 0, have_idx = 0xFFFFFFFFu, have_word = 0;   // register variant: slots per row; the word fetched last
     __device__ int32_t diag_run(int32_t i, int32_t j) {   // (banded_core.h) only the register variant packs along diagonals
       if (reg_bw <= 0) return 0;
@@ -433,23 +377,15 @@ __global__ __launch_bounds__(64) void k_banded_lds(CigJob J, SwInputs in, SwPara
         }
         return (have_word >> (5u * r)) & 31u;
       }
-      if (wpr) {
-        if (reg_bw > 0 && i < reg_bw) col += reg_bw - i;   // slot = j - i + bw, col = j - max(0, i - bw)
-        const uint32_t w = (uint32_t)col / 6u, sh = 5u * ((uint32_t)col - 6u * w);
-        return (DW[((uint32_t)i * wpr + w) * NL + lane] >> sh) & 31u;
-      }
       return D[((size_t)i * width_d + (uint32_t)col) * NL + lane];
     }
-  } A{S, SQ, SR, D, NL, lane, Y.W1, (uint32_t)(band_width * 2 + 1), oq, orf, DW, Y.wpr, 0u};
+  } A{S, SQ, SR, D, NL, lane, Y.W1, (uint32_t)(band_width * 2 + 1), oq, orf};
   (void)score;
   int32_t mx;
   if constexpr (REG_BW > 0) {
-    // direction words in the global slab, [row * WPR + word][lane]; slot x of row i
-    constexpr uint32_t WPR = (2 * (REG_BW > 0 ? REG_BW : 1) + 1 + 5) / 6;
     mx = banded_attempt_reg<(REG_BW > 0 ? REG_BW : 1)>(A, reinterpret_cast<uint32_t *>(D), NL, lane, refLen,
                                                         readLen, band_width, p, J.bmax[ci]);
     A.DW = reinterpret_cast<uint32_t *>(D);
-    A.wpr = WPR;
     A.reg_bw = band_width;
     A.nx = 2 * (REG_BW > 0 ? REG_BW : 1) + 1;
   } else {
@@ -459,68 +395,12 @@ __global__ __launch_bounds__(64) void k_banded_lds(CigJob J, SwInputs in, SwPara
   J.bmax[ci] = mx;
   if (mx < score) {               // ssw.c:693-694: retry with twice the band
     J.bw[ci] = (uint32_t)band_width * 2u;
-    append_doubled(J, true, ci, (uint32_t)band_width * 2u);
+    wave_append_to_bin(J.bins, (int)cig_bin((uint32_t)band_width * 2u), ci);
     return;
   }
-  uint32_t *tmp = J.tmp + (uint64_t)(J.big ? (J.list_base + li) : ci) * J.cap;
+  uint32_t *tmp = J.tmp + (uint64_t)(J.big ? (J.items.first + li) : ci) * J.cap;
   bool ovf = false;
   const int32_t l = banded_traceback(A, refLen, readLen, band_width, tmp, J.cap, &ovf);
-  if (l < 0) {
-    atomicAdd(&J.err[0], 1u);
-    o.cigar_len = 0;
-    J.ov[ci] = o;
-    J.bw[ci] = 0;
-    return;
-  }
-  if (ovf) {
-    J.needbig[ci] = 1;  // rerun with a full-size temp slot
-    if (J.big_count) atomicAdd(J.big_count, 1u);
-    return;
-  }
-  o.cigar_len = (uint32_t)l;
-  J.ov[ci] = o;
-  J.bw[ci] = 0;
-  J.needbig[ci] = J.big ? 2 : 0;  // 2: ops live in the big temp area
-}
-
-// traceback of one candidate from the direction words a systolic attempt left in its slab
-template <int GL, int DPL>
-__device__ inline void systolic_traceback(const CigJob &J, uint32_t li, uint32_t ci, kslam_overlap o, int32_t bw,
-                                          int32_t refLen, int32_t readLen, const uint32_t *D) {
-  const int32_t k0 = (bw & 1) ? -1 : 0;
-  struct Acc {
-    const uint32_t *D;
-    int32_t bw, k0;
-    uint32_t have_idx, have_word;   // the word fetched last: a diagonal run reuses it
-    __device__ int32_t diag_run(int32_t i, int32_t j) {   // (banded_core.h)
-      const int32_t x = j - i + bw;
-      const int32_t tt = x / DPL, q = x - tt * DPL;
-      const uint32_t n = (uint32_t)((i + j - k0 - (q & 1)) >> 1);
-      const uint32_t m = n / 6u, r = n - 6u * m;
-      const uint32_t idx = (m * GL + (uint32_t)tt) * DPL + (uint32_t)q;
-      if (idx != have_idx) {
-        have_idx = idx;
-        have_word = D[idx];
-      }
-      return diag_cells_down_from(have_word, r);
-    }
-    __device__ uint32_t get_dir(int32_t i, int32_t col) {
-      const int32_t j = col + (i - bw > 0 ? i - bw : 0);
-      const int32_t x = j - i + bw;
-      const int32_t tt = x / DPL, q = x - tt * DPL;
-      const uint32_t n = (uint32_t)((i + j - k0 - (q & 1)) >> 1);
-      const uint32_t m = n / 6u, r = n - 6u * m;
-      const uint32_t idx = (m * GL + (uint32_t)tt) * DPL + (uint32_t)q;
-      if (idx != have_idx) {
-        have_idx = idx;
-        have_word = D[idx];
-      }
-      return (have_word >> (5u * r)) & 31u;
-    }
-  } A{D, bw, k0, 0xFFFFFFFFu, 0u};
-  uint32_t *tmp = J.tmp + (uint64_t)(J.big ? (J.list_base + li) : ci) * J.cap;
-  bool ovf = false;
-  const int32_t l = banded_traceback(A, refLen, readLen, bw, tmp, J.cap, &ovf);
   if (l < 0) {
     atomicAdd(&J.err[0], 1u);
     o.cigar_len = 0;
@@ -562,7 +442,7 @@ __global__ __launch_bounds__(BS) void k_cigar_systolic(CigJob J, SwInputs in, Sw
   const int32_t t = lane & (GL - 1);
   const int32_t grp = threadIdx.x / GL;
   const uint32_t li = blockIdx.x * NG + grp;
-  bool have = li < live_entries(J, (blockIdx.x + 1) * NG), special = false;
+  bool have = li < live_len(J.items, (blockIdx.x + 1) * NG), special = false;
   uint32_t ci = 0;
   kslam_overlap o;
   memset(&o, 0, sizeof o);
@@ -570,7 +450,7 @@ __global__ __launch_bounds__(BS) void k_cigar_systolic(CigJob J, SwInputs in, Sw
   const uint8_t *wc = s_w[grp];
   const uint32_t *tab = s_tab[grp];
   if (have) {
-    ci = J.list[J.list_base + li];
+    ci = J.items.list[J.items.first + li];
     o = J.ov[ci];
     bw = (int32_t)J.bw[ci];
     refLen = o.ref_end - o.ref_begin + 1;    // ssw.c:930-931
@@ -581,7 +461,7 @@ __global__ __launch_bounds__(BS) void k_cigar_systolic(CigJob J, SwInputs in, Sw
       have = false;
     }
   }
-  if (J.special_list) append_candidate(special && t == 0, ci, J.special_list, J.special_count);
+  wave_append(special && t == 0, ci, J.special_list, J.special_count);
   if (have) {
     const uint64_t ro = in.read_off[o.read];
     const uint64_t L = in.read_off[o.read + 1] - ro;
@@ -712,32 +592,78 @@ __global__ __launch_bounds__(BS) void k_cigar_systolic(CigJob J, SwInputs in, Sw
   J.bmax[ci] = best;
   if (best < (int32_t)o.score) {               // ssw.c:693-694: retry with twice the band
     J.bw[ci] = (uint32_t)bw * 2u;
-    append_doubled(J, true, ci, (uint32_t)bw * 2u);
+    wave_append_to_bin(J.bins, (int)cig_bin((uint32_t)bw * 2u), ci);
     return;
   }
-  if (J.tb_flag) {   // the walk is a chain of dependent loads: it runs in its own kernel, 64 candidates to the wave
-    // (a flag per list position, not a compacted list: one returning atomic per wave on ONE counter -- 20-odd thousand a
-    // launch at ~12 ns apiece -- was two thirds of the 16-slot launch's 0.38 ms)
-    J.tb_flag[li] = 1;
-    return;
-  }
-  systolic_traceback<GL, DPL>(J, li, ci, o, bw, refLen, readLen, D);
+  // the walk is a chain of dependent loads: it runs in its own kernel, 64 candidates to the wave (a flag per list position,
+  // not a compacted list: one returning atomic per wave on ONE counter -- 20-odd thousand a launch at ~12 ns apiece -- was
+  // two thirds of the 16-slot launch's 0.38 ms)
+  J.tb_flag[li] = 1;
 }
 
-// The tracebacks of a systolic launch, one candidate per LANE.  At the end of the DP kernel only lane 0 of a
-// group of 8 or 16 walked -- a chain of ~28 dependent loads per candidate with an eighth of the wave's lanes
-// busy, which was ~40 % of those kernels' time; here a wave has 64 walks in flight.
+// The tracebacks of a systolic launch, one candidate per LANE, from the direction words the attempt left in its slab.
+// At the end of the DP kernel only lane 0 of a group of 8 or 16 walked -- a chain of ~28 dependent loads per
+// candidate with an eighth of the wave's lanes busy, which was ~40 % of those kernels' time; here a wave has 64
+// walks in flight.
 template <int GL, int DPL>
 __global__ __launch_bounds__(256) void k_systolic_traceback(CigJob J) {
-  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
-  if (x >= live_entries(J, (blockIdx.x + 1) * blockDim.x) || !J.tb_flag[x]) return;
-  const uint32_t li = x;
-  const uint32_t ci = J.list[J.list_base + li];
+  const uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
+  if (li >= live_len(J.items, (blockIdx.x + 1) * blockDim.x) || !J.tb_flag[li]) return;
+  const uint32_t ci = J.items.list[J.items.first + li];
   kslam_overlap o = J.ov[ci];
   const int32_t bw = (int32_t)J.bw[ci];
   const int32_t refLen = o.ref_end - o.ref_begin + 1, readLen = o.query_end - o.query_begin + 1;
   const uint32_t *D = reinterpret_cast<const uint32_t *>(J.scratch) + (uint64_t)li * (J.wave_slab / 4);
-  systolic_traceback<GL, DPL>(J, li, ci, o, bw, refLen, readLen, D);
+  const int32_t k0 = (bw & 1) ? -1 : 0;
+  struct Acc {
+    const uint32_t *D;
+    int32_t bw, k0;
+    uint32_t have_idx, have_word;   // the word fetched last: a diagonal run reuses it
+    __device__ int32_t diag_run(int32_t i, int32_t j) {   // (banded_core.h)
+      const int32_t x = j - i + bw;
+      const int32_t tt = x / DPL, q = x - tt * DPL;
+      const uint32_t n = (uint32_t)((i + j - k0 - (q & 1)) >> 1);
+      const uint32_t m = n / 6u, r = n - 6u * m;
+      const uint32_t idx = (m * GL + (uint32_t)tt) * DPL + (uint32_t)q;
+      if (idx != have_idx) {
+        have_idx = idx;
+        have_word = D[idx];
+      }
+      return diag_cells_down_from(have_word, r);
+    }
+    __device__ uint32_t get_dir(int32_t i, int32_t col) {
+      const int32_t j = col + (i - bw > 0 ? i - bw : 0);
+      const int32_t x = j - i + bw;
+      const int32_t tt = x / DPL, q = x - tt * DPL;
+      const uint32_t n = (uint32_t)((i + j - k0 - (q & 1)) >> 1);
+      const uint32_t m = n / 6u, r = n - 6u * m;
+      const uint32_t idx = (m * GL + (uint32_t)tt) * DPL + (uint32_t)q;
+      if (idx != have_idx) {
+        have_idx = idx;
+        have_word = D[idx];
+      }
+      return (have_word >> (5u * r)) & 31u;
+    }
+  } A{D, bw, k0, 0xFFFFFFFFu, 0u};
+  uint32_t *tmp = J.tmp + (uint64_t)(J.big ? (J.items.first + li) : ci) * J.cap;
+  bool ovf = false;
+  const int32_t l = banded_traceback(A, refLen, readLen, bw, tmp, J.cap, &ovf);
+  if (l < 0) {
+    atomicAdd(&J.err[0], 1u);
+    o.cigar_len = 0;
+    J.ov[ci] = o;
+    J.bw[ci] = 0;
+    return;
+  }
+  if (ovf) {
+    J.needbig[ci] = 1;  // rerun with a full-size temp slot
+    if (J.big_count) atomicAdd(J.big_count, 1u);
+    return;
+  }
+  o.cigar_len = (uint32_t)l;
+  J.ov[ci] = o;
+  J.bw[ci] = 0;
+  J.needbig[ci] = J.big ? 2 : 0;  // 2: ops live in the big temp area
 }
 
 __global__ void k_cigar_lens(const kslam_overlap *__restrict__ ov, uint64_t n, uint32_t *__restrict__ lens) {
@@ -885,9 +811,13 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
   if (p.report_cigar) {
     W.counters.ensure(16 * sizeof(uint32_t));
     uint32_t *cnt = W.counters.as<uint32_t>();   // [0..7] bin list sizes, [8] handed back, [9] long cigars, [10] tracebacks of a systolic launch, [11] classes present (generic loop)
-    auto run_lists = [&](uint32_t cls, uint32_t mode) -> uint64_t {   // mode: 0 class, 1 big rerun, 2 handed back
+    W.cls.ensure(n);
+    for (int k = 0; k < 8; k++) W.cls_list[k].ensure((n + 1) * sizeof(uint32_t));
+    W.special.ensure((n + 1) * sizeof(uint32_t));
+    HIPCHK(hipMemsetAsync(cnt, 0, 16 * sizeof(uint32_t), s));
+    auto run_lists = [&](uint32_t cls, uint32_t big) -> uint64_t {   // W.list: class cls, or (big) the big rerun
       hipLaunchKernelGGL(k_class_flags, dim3(nb), dim3(256), 0, s, d_bw, W.needbig.as<uint8_t>(), n, cls,
-                         mode, W.flags.as<uint32_t>());
+                         big, W.flags.as<uint32_t>());
       exclusive_scan_u32(W.flags.as<uint32_t>(), W.pos.as<uint32_t>(), n, d_tot, W.scan_tmp.p, s);
       uint64_t m = 0;
       read_back(&m, d_tot, sizeof m, s);
@@ -895,25 +825,38 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
                                 W.pos.as<uint32_t>(), n, W.list.as<uint32_t>());
       return m;
     };
-    // one attempt for the m candidates of W.list with the systolic kernel; false when the band is
-    // too wide for it
+    // what every launch of this call shares; a launch sets its slice of a list and what differs from these
+    CigJob J0;
+    J0.ov = d_ov; J0.bw = d_bw; J0.bmax = W.bmax.as<int32_t>(); J0.needbig = W.needbig.as<uint8_t>();
+    J0.cap = CIG_CAP;
+    J0.tmp = W.tmp.as<uint32_t>();
+    J0.big = 0;
+    J0.err = d_err;
+#ifdef KSLAM_ABLATE
+    J0.variant = tune.cigar_variant;
+#endif
+    for (int k = 0; k < 8; k++) J0.bins.list[k] = W.cls_list[k].as<uint32_t>();
+    J0.bins.count = cnt;
+    J0.special_list = W.special.as<uint32_t>();
+    J0.special_count = cnt + 8;
+    J0.big_count = cnt + 9;
+    // entries [off, off + m) of a launch's slice
+    auto part = [](ListSlice L, uint64_t off, uint64_t m) {
+      L.first += (uint32_t)off;
+      L.cap = (uint32_t)m;
+      L.sure = L.sure > off ? L.sure - (uint32_t)off : 0;
+      return L;
+    };
     // bit b: bin b (cig_bin) runs on the systolic kernel.  Measured on the bench workload: bins 0-2 (bands up to 4) are
     // cheaper on the register kernel (5 of 16 diagonal slots live on the systolic one, 3.9 against 5.4 ms in round 2);
     // bin 3 (bands 5..7) costs the same on both (register kernel <8> with mixed widths in a wave: 4.43 against 4.36 ms
     // for the stage); a band of 16 in registers needs 256 VGPRs + AGPR spills and loses (5.3 ms).
     const int sys_mask = tune.cigar_sys_mask;
-    struct Route {
-      const uint32_t *list = nullptr;
-      uint32_t *const *bin_list = nullptr;   // [8]: where a candidate goes whose band doubled (nullptr: the host re-lists by flags)
-      uint32_t *bin_count = nullptr, *special_list = nullptr, *special_count = nullptr, *big_count = nullptr;
-      const uint32_t *count_dev = nullptr;   // the list's length where the kernels read it (CigJob::m_dev); then `m` is a capacity
-      uint32_t sure = 0;                     // ... and this many entries of the list are known to exist
-      bool no_reg = false;                   // the one-lane kernel whatever the band (the candidates the others handed over)
-      uint32_t first = 0;                    // the launch starts at this entry of the list
-    };
-    auto launch_systolic = [&](uint64_t m, uint32_t slot_bw, uint32_t bin, const Route &R) -> bool {
+    // one attempt for the candidates of J.items with the systolic kernel; false when the band is too wide for it
+    auto launch_systolic = [&](const CigJob &J, uint32_t slot_bw, uint32_t bin) -> bool {
       const uint32_t need = 2 * slot_bw + 1;
       if (need > 256 || !((sys_mask >> std::min(bin, 7u)) & 1)) return false;
+      const uint64_t m = J.items.cap;
       const int lm = lmax <= 160 ? 0 : (lmax <= 256 ? 1 : 2);
       const uint32_t LM = lm == 0 ? 160 : (lm == 1 ? 256 : 512);
       // lanes x diagonals per lane: 8 x 2 / 4 / 8 up to 64 slots, 16 x 8 / 16 up to 256 (a handful of
@@ -928,38 +871,19 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
       const uint64_t groups_per_launch = std::max<uint64_t>(NG, (SCRATCH_BUDGET / slab) / NG * NG);
       W.scratch.ensure(std::min<uint64_t>((m + NG - 1) / NG * NG, groups_per_launch) * slab);
       for (uint64_t g0 = 0; g0 < m; g0 += groups_per_launch) {
-        CigJob J;
-        J.ov = d_ov; J.bw = d_bw; J.bmax = W.bmax.as<int32_t>(); J.needbig = W.needbig.as<uint8_t>();
-        J.list = R.list ? R.list : W.list.as<uint32_t>();
-        if (R.bin_list) for (int k = 0; k < 8; k++) J.bin_list[k] = R.bin_list[k];
-        J.bin_count = R.bin_list ? R.bin_count : nullptr;
-        J.special_list = R.special_list; J.special_count = R.special_count; J.big_count = R.big_count;
-        J.list_base = R.first + (uint32_t)g0;
-        J.m_dev = R.count_dev;
-        J.m_sure = R.sure > J.list_base ? R.sure - J.list_base : 0;
-        J.m = (uint32_t)std::min<uint64_t>(groups_per_launch, m - g0);
-        J.slot_bw = slot_bw; J.lmax = lmax;
-        J.cap = CIG_CAP;
-        J.tmp = W.tmp.as<uint32_t>();
-        J.big = 0;
-        J.scratch = W.scratch.as<uint8_t>();
-        J.wave_slab = slab;
-        J.err = d_err;
-#ifdef KSLAM_ABLATE
-        J.variant = tune.cigar_variant;
-#endif
-        const unsigned nb = (unsigned)((J.m + NG - 1) / NG);
-        // the tracebacks of this launch in a kernel of their own (KSLAM_CIGAR_TB=inline: at the end of the DP kernel)
-        const bool tb_inline = tune.cigar_tb_inline;
-        if (!tb_inline) {
-          W.tb_list.ensure((uint64_t)J.m + 64);
-          J.tb_flag = W.tb_list.as<uint8_t>();
-          HIPCHK(hipMemsetAsync(J.tb_flag, 0, J.m, s));
-        }
-        const unsigned nb_tb = (unsigned)(((uint64_t)J.m + 255) / 256);
+        CigJob Jl = J;
+        Jl.items = part(J.items, g0, std::min<uint64_t>(groups_per_launch, m - g0));
+        Jl.scratch = W.scratch.as<uint8_t>();
+        Jl.wave_slab = slab;
+        const unsigned nb = (unsigned)((Jl.items.cap + NG - 1) / NG);
+        // the tracebacks of this launch in a kernel of their own
+        W.tb_list.ensure((uint64_t)Jl.items.cap + 64);
+        Jl.tb_flag = W.tb_list.as<uint8_t>();
+        HIPCHK(hipMemsetAsync(Jl.tb_flag, 0, Jl.items.cap, s));
+        const unsigned nb_tb = (unsigned)(((uint64_t)Jl.items.cap + 255) / 256);
 #define KSLAM_SYS(LMV, GLV, DPLV) \
-  do { hipLaunchKernelGGL((k_cigar_systolic<LMV, GLV, DPLV, 128>), dim3(nb), dim3(128), 0, s, J, in, p); \
-       if (J.tb_flag) hipLaunchKernelGGL((k_systolic_traceback<GLV, DPLV>), dim3(nb_tb), dim3(256), 0, s, J); } while (0)
+  do { hipLaunchKernelGGL((k_cigar_systolic<LMV, GLV, DPLV, 128>), dim3(nb), dim3(128), 0, s, Jl, in, p); \
+       hipLaunchKernelGGL((k_systolic_traceback<GLV, DPLV>), dim3(nb_tb), dim3(256), 0, s, Jl); } while (0)
 #define KSLAM_SYS_LM(GLV, DPLV) \
   do { if (lm == 0) KSLAM_SYS(160, GLV, DPLV); else if (lm == 1) KSLAM_SYS(256, GLV, DPLV); else KSLAM_SYS(512, GLV, DPLV); } while (0)
         if (GL == 16 && DPL == 16) KSLAM_SYS_LM(16, 16);
@@ -973,36 +897,31 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
       HIPCHK(hipGetLastError());
       return true;
     };
-    auto launch = [&](uint64_t m, uint32_t slot_bw, bool big, const Route &R) {
+    // one attempt for the candidates of J.items with the one-lane kernels (no_reg: the one with the rows in LDS, whatever
+    // the band -- the candidates the others handed over)
+    auto launch = [&](const CigJob &J, uint32_t slot_bw, bool no_reg) {
+      const uint64_t m = J.items.cap;
       LdsLayout Y;
       Y.lmax = lmax; Y.W1 = slot_bw * 2 + 4; Y.wd = slot_bw * 2 + 1;
-      // Directions: global slab.  Keeping them in LDS (KSLAM_CIGAR_DIRS=lds) was measured: the DP is
-      // LDS-instruction bound, not bound by the traceback's loads, and the extra 38 KB per block cost
-      // more occupancy than the traceback gained (class 1: 7.9 ms against 2.8 ms).
+      // Directions: global slab.  Keeping them in LDS was measured: the DP is LDS-instruction bound, not bound by the
+      // traceback's loads, and the extra 38 KB per block cost more occupancy than the traceback gained (class 1: 7.9 ms
+      // against 2.8 ms).
       Y.nch = ((lmax + 30) >> 4) + 1;   // 15 bytes of misalignment in front, up to 15 behind
-      const uint32_t wpr_fit = (Y.wd + 5) / 6;
-      const bool dir_in_lds = tune.cigar_dirs_lds &&
-                              ((size_t)2 * Y.nch * 8 + (size_t)3 * Y.W1 * sizeof(int16_t) + (size_t)lmax * wpr_fit * 4) * 16 + 64 <= 64 * 1024;
-      Y.wpr = dir_in_lds ? wpr_fit : 0;
       // narrow bands: the band in registers (KSLAM_CIGAR_REG=0 turns it off)
-      const bool use_reg = tune.cigar_reg && !R.no_reg;
+      const bool use_reg = tune.cigar_reg && !no_reg;
       // (a class-0 candidate has band 1: three slots, not the five of the band-2 instantiation it used to share)
-      const uint32_t reg_bw = (!use_reg || big || Y.wpr) ? 0u : (slot_bw <= 1 ? 1u : (slot_bw <= 2 ? 2u : (slot_bw <= 4 ? 4u : (slot_bw <= 8 ? 8u : (slot_bw <= 16 ? 16u : 0u)))));
+      const uint32_t reg_bw = (!use_reg || J.big) ? 0u : (slot_bw <= 1 ? 1u : (slot_bw <= 2 ? 2u : (slot_bw <= 4 ? 4u : (slot_bw <= 8 ? 8u : (slot_bw <= 16 ? 16u : 0u)))));
       // The register kernels keep no row arrays in LDS (round 6): a candidate they cannot hold -- a window no longer than its
       // band -- goes to the one-lane kernel through the same list the systolic kernels hand theirs over on.  3-5 KB less per
       // workgroup: 13 instead of 10 workgroups per CU for band 2.
-      if (reg_bw) {
-        if (!R.special_list) throw StatusError{KSLAM_ERR_STATE, "a register-band launch needs a hand-over list"};
-        Y.W1 = 0;
-      }
-      const size_t base_lane = (size_t)2 * Y.nch * 8 + (size_t)3 * Y.W1 * sizeof(int16_t);
-      const size_t per_lane = base_lane + (size_t)lmax * Y.wpr * 4;
+      if (reg_bw) Y.W1 = 0;
+      const size_t per_lane = (size_t)2 * Y.nch * 8 + (size_t)3 * Y.W1 * sizeof(int16_t);
       uint32_t nl = 64;
       while (nl > 1 && per_lane * nl + 64 > 64 * 1024) nl >>= 1;   // <= 64 KB: at least two blocks per CU
       Y.nl = nl;
       const size_t half = (size_t)Y.nch * nl * 8;
       const size_t rows_bytes = ((size_t)3 * Y.W1 * nl * sizeof(int16_t) + 15) & ~(size_t)15;
-      const size_t lds = 2 * half + rows_bytes + (size_t)lmax * Y.wpr * 4 * nl;
+      const size_t lds = 2 * half + rows_bytes;
       if (lds > 160 * 1024) throw StatusError{KSLAM_ERR_UNSUPPORTED, "banded traceback band does not fit LDS"};
       if (lds > 64 * 1024)
         for (const void *f : {reinterpret_cast<const void *>(&k_banded_lds<0>),
@@ -1012,132 +931,70 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
                               reinterpret_cast<const void *>(&k_banded_lds<8>),
                               reinterpret_cast<const void *>(&k_banded_lds<16>)})
           HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      uint64_t slab = Y.wpr ? 256 : (uint64_t)lmax * std::max<uint32_t>(Y.wd, reg_bw ? 8u : 0u) * nl;   // direction
-      slab = (slab + 255) & ~255ull;   // bytes per block; the register variant stores <= 8 bytes per row and lane
+      uint64_t slab = (uint64_t)lmax * std::max<uint32_t>(Y.wd, reg_bw ? 8u : 0u) * nl;   // direction bytes per block; the
+      slab = (slab + 255) & ~255ull;   // register variant stores <= 8 bytes per row and lane
       const uint64_t SCRATCH_BUDGET = 3ull << 30;
       const uint64_t blocks_per_launch = std::max<uint64_t>(1, SCRATCH_BUDGET / slab);
       const uint64_t n_blocks = (m + nl - 1) / nl;
       W.scratch.ensure(std::min<uint64_t>(n_blocks, blocks_per_launch) * slab);
       for (uint64_t b0 = 0; b0 < n_blocks; b0 += blocks_per_launch) {
-        CigJob J;
-        J.ov = d_ov; J.bw = d_bw; J.bmax = W.bmax.as<int32_t>(); J.needbig = W.needbig.as<uint8_t>();
-        J.list = R.list ? R.list : W.list.as<uint32_t>();
-        if (R.bin_list) for (int k = 0; k < 8; k++) J.bin_list[k] = R.bin_list[k];
-        J.bin_count = R.bin_list ? R.bin_count : nullptr;
-        J.big_count = R.big_count;
-        J.special_list = reg_bw ? R.special_list : nullptr;
-        J.special_count = reg_bw ? R.special_count : nullptr;
         const uint64_t nb_here = std::min<uint64_t>(blocks_per_launch, n_blocks - b0);
-        J.list_base = R.first + (uint32_t)(b0 * nl);
-        J.m_dev = R.count_dev;
-        J.m_sure = R.sure > J.list_base ? R.sure - J.list_base : 0;
-        J.m = (uint32_t)std::min<uint64_t>(nb_here * nl, m - b0 * nl);
-        J.slot_bw = slot_bw; J.lmax = lmax;
-        J.cap = big ? cap_big : CIG_CAP;
-        J.tmp = big ? W.tmp_big.as<uint32_t>() : W.tmp.as<uint32_t>();
-        J.big = big ? 1 : 0;
-        J.scratch = W.scratch.as<uint8_t>();
-        J.wave_slab = slab;
-        J.err = d_err;
-#ifdef KSLAM_ABLATE
-        J.variant = tune.cigar_variant;
-#endif
-        if (reg_bw == 1) hipLaunchKernelGGL(k_banded_lds<1>, dim3((unsigned)nb_here), dim3(64), lds, s, J, in, p, Y);
-        else if (reg_bw == 2) hipLaunchKernelGGL(k_banded_lds<2>, dim3((unsigned)nb_here), dim3(64), lds, s, J, in, p, Y);
-        else if (reg_bw == 4) hipLaunchKernelGGL(k_banded_lds<4>, dim3((unsigned)nb_here), dim3(64), lds, s, J, in, p, Y);
-        else if (reg_bw == 8) hipLaunchKernelGGL(k_banded_lds<8>, dim3((unsigned)nb_here), dim3(64), lds, s, J, in, p, Y);
-        else if (reg_bw == 16) hipLaunchKernelGGL(k_banded_lds<16>, dim3((unsigned)nb_here), dim3(64), lds, s, J, in, p, Y);
-        else hipLaunchKernelGGL(k_banded_lds<0>, dim3((unsigned)nb_here), dim3(64), lds, s, J, in, p, Y);
+        CigJob Jl = J;
+        Jl.items = part(J.items, b0 * nl, std::min<uint64_t>(nb_here * nl, m - b0 * nl));
+        Jl.scratch = W.scratch.as<uint8_t>();
+        Jl.wave_slab = slab;
+        if (reg_bw == 1) hipLaunchKernelGGL(k_banded_lds<1>, dim3((unsigned)nb_here), dim3(64), lds, s, Jl, in, p, Y);
+        else if (reg_bw == 2) hipLaunchKernelGGL(k_banded_lds<2>, dim3((unsigned)nb_here), dim3(64), lds, s, Jl, in, p, Y);
+        else if (reg_bw == 4) hipLaunchKernelGGL(k_banded_lds<4>, dim3((unsigned)nb_here), dim3(64), lds, s, Jl, in, p, Y);
+        else if (reg_bw == 8) hipLaunchKernelGGL(k_banded_lds<8>, dim3((unsigned)nb_here), dim3(64), lds, s, Jl, in, p, Y);
+        else if (reg_bw == 16) hipLaunchKernelGGL(k_banded_lds<16>, dim3((unsigned)nb_here), dim3(64), lds, s, Jl, in, p, Y);
+        else hipLaunchKernelGGL(k_banded_lds<0>, dim3((unsigned)nb_here), dim3(64), lds, s, Jl, in, p, Y);
       }
       HIPCHK(hipGetLastError());
     };
-    // Bins 0..6 (bw < 64, cig_bin above): one partition of the candidates by bin, then bin after bin; an attempt that falls
-    // short of the score doubles its band, which moves it to a later bin, and the kernels append such candidates to that
-    // bin's list themselves.
+    // Bins 0..6 (bw < 64, cig_bin above): one partition of the candidates by bin, then the sweep over the growing lists
+    // (sweep_lists): an attempt that falls short of the score doubles its band, which moves the candidate to a later bin.
+    // Pass one sizes a bin for what the partition put into it plus room for an eighth of everything in the bins before it
+    // (all of it while that is little; spare workgroups cost ~1 ns each).  Each round first runs what the systolic and
+    // register launches handed to the one-lane kernel (spans the band covers completely), laid out for the widest band
+    // among the bins that handed over.
     const bool debug = tune.debug;
-    W.cls.ensure(n);
-    for (int k = 0; k < 8; k++) W.cls_list[k].ensure((n + 1) * sizeof(uint32_t));
-    W.special.ensure((n + 1) * sizeof(uint32_t));
-    HIPCHK(hipMemsetAsync(cnt, 0, 16 * sizeof(uint32_t), s));
     hipLaunchKernelGGL(k_cig_class, dim3(nb), dim3(256), 0, s, d_bw, n, W.cls.as<uint8_t>());
-    uint32_t *lists[8];
-    for (int k = 0; k < 8; k++) lists[k] = W.cls_list[k].as<uint32_t>();
-    partition_bins(W.cls.as<uint8_t>(), n, lists, cnt, W.pos, s);
-    // ONE sweep over the bins without a read-back in front of each (round 6; the GPU used to idle 25-60 us at each of ~11 of
-    // them per chunk).  A bin's list grows while the earlier bins run (a failed attempt appends the candidate whose band
-    // doubled), so the host cannot know its length when it queues the bin's launch -- but the kernels can: a launch is
-    // sized for a CAPACITY, what the partition put into the bin plus room for an eighth of everything in the bins before
-    // it (all of it while that is little), and its workgroups read the list's real length when they run (CigJob::m_dev; failures are rare, the spare
-    // workgroups leave at once).  Then one read-back.  What did not fit a capacity, what the systolic launches handed to
-    // the one-lane kernel (spans the band covers completely; laid out for the widest band among the bins that handed over)
-    // and whatever THOSE append is left to rounds: each launches the part of every list nobody has run yet, then reads
-    // the counters again, until nothing is new.
+    partition_bins(W.cls.as<uint8_t>(), n, J0.bins, W.pos, s);
     uint32_t hc[10];
-    uint32_t done[7] = {0, 0, 0, 0, 0, 0, 0};
     read_back(hc, cnt, sizeof hc, s);
     if (debug) fprintf(stderr, "[kslam] cigar bins as the SW stage asked for them: %u %u %u %u %u %u %u %u\n", hc[0], hc[1], hc[2], hc[3], hc[4], hc[5], hc[6], hc[7]);
+    uint64_t cap[7];
+    uint64_t before = 0;
+    for (uint32_t bin = 0; bin < 7; bin++) {
+      const uint64_t room = !tune.sweep_room ? 0 : (before <= 65536 ? before : std::max<uint64_t>(65536, before / 8));
+      cap[bin] = hc[bin] + room;
+      before += hc[bin];
+    }
     uint32_t special_bw = 0;
-    {
-      uint64_t before = 0;
-      for (uint32_t bin = 0; bin < 7; bin++) {
-        const uint64_t room = !tune.sweep_room ? 0 : (before <= 65536 ? before : std::max<uint64_t>(65536, before / 8));   // (spare workgroups cost ~1 ns each)
-        const uint64_t cap = hc[bin] + room;
-        before += hc[bin];
-        if (cap == 0) continue;
-        const uint32_t slot_bw = CIG_BIN_MAX_BW[bin];
-        Route R;
-        R.list = lists[bin];
-        R.bin_list = lists;
-        R.bin_count = cnt;
-        R.special_list = W.special.as<uint32_t>();
-        R.special_count = cnt + 8;
-        R.big_count = cnt + 9;
-        R.count_dev = cnt + bin;
-        R.sure = hc[bin];
-        if (!launch_systolic(cap, slot_bw, bin, R)) launch(cap, slot_bw, false, R);
-        special_bw = std::max(special_bw, slot_bw);    // (register bins hand over too: windows no longer than their band)
-        done[bin] = (uint32_t)cap;       // (clamped to the list's length below)
-      }
-    }
-    for (int round = 0;; round++) {
-      read_back(hc, cnt, sizeof hc, s);
-      for (uint32_t bin = 0; bin < 7; bin++) done[bin] = std::min(done[bin], hc[bin]);
-      bool progressed = false;
-      if (hc[8]) {   // the few the systolic launches handed back
-        if (debug) fprintf(stderr, "[kslam]   handed to the one-lane kernel: %u\n", hc[8]);
-        Route R2;
-        R2.list = W.special.as<uint32_t>();
-        R2.bin_list = lists;
-        R2.bin_count = cnt;
-        R2.big_count = cnt + 9;
-        R2.no_reg = true;
-        launch(hc[8], special_bw, false, R2);
-        HIPCHK(hipMemsetAsync(cnt + 8, 0, sizeof(uint32_t), s));
-        special_bw = 0;
-        progressed = true;
-      }
-      for (uint32_t bin = 0; bin < 7; bin++) {
-        if (hc[bin] <= done[bin]) continue;
-        const uint64_t m = hc[bin] - done[bin];
-        const uint32_t slot_bw = CIG_BIN_MAX_BW[bin];
-        if (debug) fprintf(stderr, "[kslam] cigar round %d bin %u (band <= %u): %llu candidates left over\n", round, bin, slot_bw, (unsigned long long)m);
-        Route R;
-        R.list = lists[bin];
-        R.first = done[bin];
-        R.bin_list = lists;
-        R.bin_count = cnt;
-        R.special_list = W.special.as<uint32_t>();
-        R.special_count = cnt + 8;
-        R.big_count = cnt + 9;
-        if (!launch_systolic(m, slot_bw, bin, R)) launch(m, slot_bw, false, R);
-        special_bw = std::max(special_bw, slot_bw);
-        done[bin] = hc[bin];
-        progressed = true;
-      }
-      if (!progressed) break;
-    }
+    sweep_lists(7, cnt, hc, sizeof hc, cap, false,
+                [&](uint32_t bin, uint64_t m, uint32_t first, const uint32_t *count_dev, uint32_t sure, int round) {
+                  const uint32_t slot_bw = CIG_BIN_MAX_BW[bin];
+                  if (debug && round >= 0) fprintf(stderr, "[kslam] cigar round %d bin %u (band <= %u): %llu candidates left over\n", round, bin, slot_bw, (unsigned long long)m);
+                  CigJob J = J0;
+                  J.items = ListSlice{J0.bins.list[bin], first, (uint32_t)m, sure, count_dev};
+                  if (!launch_systolic(J, slot_bw, bin)) launch(J, slot_bw, false);
+                  special_bw = std::max(special_bw, slot_bw);    // (register bins hand over too: windows no longer than their band)
+                },
+                [&](int) {
+                  if (!hc[8]) return false;
+                  if (debug) fprintf(stderr, "[kslam]   handed to the one-lane kernel: %u\n", hc[8]);
+                  CigJob J = J0;
+                  J.items = ListSlice{W.special.as<uint32_t>(), 0, hc[8], 0, nullptr};
+                  launch(J, special_bw, true);
+                  HIPCHK(hipMemsetAsync(cnt + 8, 0, sizeof(uint32_t), s));
+                  special_bw = 0;
+                  return true;
+                }, s);
     // 64 and wider (never seen on real reads): the flag / scan / scatter loop, class c = floor(log2 bw) after class
-    // (hc is current: the loop above ends on a round that found nothing new after its last read-back)
+    // (hc is current: the sweep ends on a round that found nothing new after its last read-back)
+    CigJob Jc = J0;
+    Jc.bins.count = nullptr;   // what fails here is found by the flags of the next class
     if (hc[7]) {
       HIPCHK(hipMemsetAsync(cnt + 11, 0, sizeof(uint32_t), s));
       hipLaunchKernelGGL(k_class_mask, dim3(nb), dim3(256), 0, s, d_bw, W.needbig.as<uint8_t>(), n, cnt + 11);
@@ -1150,22 +1007,17 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
         present |= 2u << cls;   // what fails here doubles its band
         const uint32_t slot_bw = (2u << cls) - 1u;
         if (debug) fprintf(stderr, "[kslam] cigar class %u (band <= %u): %llu candidates\n", cls, slot_bw, (unsigned long long)m);
-        Route R;
-        R.big_count = cnt + 9;
-        R.special_list = W.special.as<uint32_t>();
-        R.special_count = cnt + 8;
-        if (launch_systolic(m, slot_bw, 7, R)) {
+        CigJob J = Jc;
+        J.items = ListSlice{W.list.as<uint32_t>(), 0, (uint32_t)m, 0, nullptr};
+        if (launch_systolic(J, slot_bw, 7)) {
           read_back(hc, cnt, sizeof hc, s);
           if (hc[8]) {
-            Route R2 = R;
-            R2.list = W.special.as<uint32_t>();
-            R2.special_list = nullptr;
-            R2.no_reg = true;
-            launch(hc[8], slot_bw, false, R2);
+            J.items = ListSlice{W.special.as<uint32_t>(), 0, hc[8], 0, nullptr};
+            launch(J, slot_bw, true);
             HIPCHK(hipMemsetAsync(cnt + 8, 0, sizeof(uint32_t), s));
           }
         } else {
-          launch(m, slot_bw, false, R);
+          launch(J, slot_bw, false);
         }
       }
       read_back(hc, cnt, sizeof hc, s);
@@ -1180,7 +1032,13 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
                          W.list.as<uint32_t>(), (uint32_t)n_big, reinterpret_cast<uint32_t *>(d_tot + 1));
       uint64_t mb = 0;
       read_back(&mb, d_tot + 1, sizeof mb, s);
-      launch(n_big, (uint32_t)mb, true, Route());
+      CigJob J = Jc;
+      J.items = ListSlice{W.list.as<uint32_t>(), 0, (uint32_t)n_big, 0, nullptr};
+      J.big = 1;
+      J.cap = cap_big;
+      J.tmp = W.tmp_big.as<uint32_t>();
+      J.big_count = nullptr;
+      launch(J, (uint32_t)mb, false);
     }
   }
   // cigar pool layout

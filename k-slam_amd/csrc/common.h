@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 #include "../../include/kslam.h"
@@ -43,8 +44,6 @@ struct Tuning {
   int sw_unknown_nd = 0;              // KSLAM_SW_UNKNOWN_ND: where gapped candidates start (0: by read length)
   int cigar_sys_mask = 0xF8;          // KSLAM_CIGAR_SYS: band-width bins (cigar.hip: cig_bin) that run on the systolic kernel, one bit each
   bool cigar_reg = true;              // KSLAM_CIGAR_REG=0: no band-in-registers kernel
-  bool cigar_dirs_lds = false;        // KSLAM_CIGAR_DIRS=lds: direction words in LDS
-  bool cigar_tb_inline = false;       // KSLAM_CIGAR_TB=inline: systolic tracebacks at the end of the DP kernel
   int bucket_bits_max = 27;           // KSLAM_BUCKET_BITS
   int bucket_bits_exact = 0;          // KSLAM_BUCKET_BITS_EXACT (0: sized from the index)
   int filter_bits = -1;               // KSLAM_FILTER_BITS (-1: sized from the index, 0: no filter)
@@ -57,7 +56,6 @@ struct Tuning {
   bool details_in_token = true;       // KSLAM_DETAILS_IN_TOKEN=0 (A/B): the per-row walk outside the lanes' compute token
   int plan_blocks_per_cu = 64;        // KSLAM_PLAN_BLOCKS: workgroups of k_sw_plan per CU (its waves walk through the candidates)
   int join_group_order = 1;           // KSLAM_JOIN_GROUP_ORDER=0: the overlap keys go through all their radix passes (join.hip: group_order)
-  bool sw_sweep = true;               // KSLAM_SW_SWEEP=0: a read-back in front of every SW tier (as until round 5)
   bool sweep_room = true;             // KSLAM_SWEEP_ROOM=0 (tests): the CIGAR bins' and SW tiers' launches get NO room for what earlier ones send
                                       // on, so that every such candidate takes the left-over rounds
   int join_merge = 0;                 // KSLAM_JOIN=merge: k_join_merge instead of the probe k_join_fill (join.hip)
@@ -141,6 +139,65 @@ void exclusive_scan_u32(const uint32_t *d_in, uint32_t *d_out, uint64_t n,
                         uint64_t *d_total, void *d_tmp, hipStream_t s);
 void exclusive_scan_u32_to_u64(const uint32_t *d_in, uint64_t *d_out, uint64_t n,
                                uint64_t *d_total, void *d_tmp, hipStream_t s);
+
+// Lists of candidate numbers by bin that grow while kernels run: the SW tiers (sw.hip) and the CIGAR band-width bins
+// (cigar.hip).  A kernel of one bin appends what it does not finish to the list of a later bin.
+struct BinLists {
+  uint32_t *list[8];   // list[b]: the numbers in bin b (nullptr: a bin that cannot occur)
+  uint32_t *count;     // [8] entries of each list (nullptr: nothing is appended)
+};
+// Stable 8-way partition of the element numbers 0..n-1 by d_bins[i] (bins >= 8 are left out):
+// B.list[k] receives bin k's numbers in order, B.count[k] its size.
+void partition_bins(const uint8_t *d_bins, uint64_t n, const BinLists &B, DevBuf &pos, hipStream_t s);
+// The entries [first, first + cap) of a list that one launch covers.  With count_dev, cap is a CAPACITY: the list was
+// still growing when the host sized the launch, and its workgroups read its real length when they run.  The first
+// `sure` entries of the slice existed when the host looked; a workgroup inside them does not wait for that load.
+struct ListSlice {
+  const uint32_t *list;
+  uint32_t first, cap, sure;
+  const uint32_t *count_dev;
+};
+#ifdef __HIPCC__
+// entries of the slice that exist, for a workgroup whose entries end before hi (counted from `first`)
+__device__ inline uint32_t live_len(const ListSlice &S, uint32_t hi) {
+  if (!S.count_dev || hi <= S.sure) return S.cap;
+  const uint32_t tot = *S.count_dev;
+  return min(S.cap, tot > S.first ? tot - S.first : 0u);
+}
+// wave-aggregated append of v to a list (one atomic per wave)
+__device__ inline void wave_append(bool want, uint32_t v, uint32_t *list, uint32_t *count) {
+  const uint64_t m = __ballot(want);
+  if (!m) return;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t leader = (uint32_t)__builtin_ctzll(m);
+  uint32_t base = 0;
+  if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(m));
+  base = __shfl((int)base, (int)leader, 64);
+  if (want) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = v;
+}
+// the same into the list of bin `dest` (< 0: nothing; lanes of a wave may differ in it): one atomic per wave and bin
+__device__ inline void wave_append_to_bin(const BinLists &B, int dest, uint32_t v) {
+  if (!B.count) return;
+  for (;;) {
+    const uint64_t m = __ballot(dest >= 0);
+    if (!m) break;
+    const int d0 = __shfl(dest, (int)__builtin_ctzll(m), 64);
+    wave_append(dest == d0, v, B.list[d0], B.count + d0);
+    if (dest == d0) dest = -1;
+  }
+}
+#endif
+// The sweep over bins 0 .. n_bins - 1 of such lists, with as few read-backs as it can.  Pass one launches every bin with
+// first_cap[b] > 0 at once, sized for that capacity, with the list's counter (count_dev) for its workgroups to read:
+// when the host queues a bin it cannot know what the bins before it will append.  Then rounds, each after one read-back
+// of the counters into h (h_bytes of them): a round first calls `round_hook` (a list of the caller's own, outside the
+// bins: true if it launched something), then launches, per bin, the entries nobody has launched yet (count_dev nullptr:
+// m is exact), until a round finds nothing new.  `step`: no pass one, and a read-back after every launch, so that each
+// bin runs once, whole (a caller that has nothing to size the capacities from).  h must hold the counters on entry
+// and holds them on return.  launch(bin, m, first, count_dev, sure, round): round -1 is pass one.
+using SweepLaunch = std::function<void(uint32_t bin, uint64_t m, uint32_t first, const uint32_t *count_dev, uint32_t sure, int round)>;
+void sweep_lists(uint32_t n_bins, const uint32_t *d_counts, uint32_t *h, size_t h_bytes, const uint64_t *first_cap, bool step,
+                 const SweepLaunch &launch, const std::function<bool(int round)> &round_hook, hipStream_t s);
 
 // ------------------------------------------------------------- extract.hip
 struct SegEntry {   // one wave-sized unit of extraction work
@@ -442,7 +499,7 @@ void encode_bases(const uint8_t *d_src, uint8_t *d_dst, uint64_t n, hipStream_t 
 // unflipped coordinates); d_band0[i] = initial band width for banded_sw
 // (0 = no cigar wanted, ssw.c:924-927)
 struct SwWork {
-  DevBuf flags, pos, list, list2, scan_tmp, totals, tier_list[6];
+  DevBuf flags, pos, list, totals, tier_list[6];
   // what the last chunk's tiers received from the tiers before them (sw.hip: the one sweep over the tiers is sized from it)
   uint64_t last_n = 0;
   uint32_t last_inflow[6] = {0, 0, 0, 0, 0, 0};
@@ -452,11 +509,6 @@ struct SwWork {
 void sw_scores(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, uint32_t max_read_len,
                uint32_t *d_band0, SwWork &W, uint64_t *n_full_out, const Tuning &tune, hipStream_t s,
                bool long_reads = false);   // long_reads: the chunk's reads exceed the packed kernels (sw.hip: k_sw_long)
-
-// Stable 8-way partition of the element numbers 0..n-1 by d_bins[i] (bins >= 8 are left out):
-// d_lists[k] receives bin k's numbers in order, d_counts[k] its size (sw.hip).
-void partition_bins(const uint8_t *d_bins, uint64_t n, uint32_t *const d_lists[8], uint32_t *d_counts, DevBuf &pos,
-                    hipStream_t s);
 
 // --------------------------------------------------------------- cigar.hip
 struct CigarWork {

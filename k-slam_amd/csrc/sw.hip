@@ -364,17 +364,14 @@ __device__ inline bool band_certifies(int32_t score, int32_t L, int32_t W, int32
   return amin - L >= dlo && W - amin <= dlo + ND - 1;
 }
 
-// The banded tiers of one launch configuration: diagonals swept per tier, the list each tier works
-// through and the counters behind the lists (counts[k]: entries of list k; counts[NT_FULL]: entries of
-// the full-matrix list).
+// The banded tiers of one launch configuration: diagonals swept per tier and the lists they work through
+// (bins.list[k]: tier k, bins.list[NT_FULL]: the full-matrix kernel).
 constexpr int NT_MAX = 6, NT_FULL = 7;
 struct Tiers {
   int n;                  // tiers in use
   int unknown;            // tier a candidate starts in when its seed diagonals certify nothing
   int nd[NT_MAX];         // diagonals of tier k, ascending
-  uint32_t *list[NT_MAX];
-  uint32_t *full_list;
-  uint32_t *counts;
+  BinLists bins;
 };
 
 // ---- tier planning ------------------------------------------------------------------------------
@@ -662,98 +659,6 @@ __global__ __launch_bounds__(256) void k_sw_plan(kslam_overlap *__restrict__ ov,
   }
 }
 
-// NT-way stable partition of the candidate numbers by tier: per-block counts, one small scan,
-// then a scatter that ranks within the block by ballots.
-constexpr int TIER_ITEMS = 4096;   // candidates per block
-constexpr int NT = 8;              // tier bins (up to 6 used)
-__global__ __launch_bounds__(256) void k_tier_hist(const uint8_t *__restrict__ tier, uint64_t n,
-                                                   uint32_t *__restrict__ block_hist, uint32_t n_blocks) {
-  __shared__ uint32_t h[NT];
-  if (threadIdx.x < NT) h[threadIdx.x] = 0;
-  __syncthreads();
-  uint32_t c[NT] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const uint64_t base = (uint64_t)blockIdx.x * TIER_ITEMS;
-  for (uint32_t k = threadIdx.x; k < TIER_ITEMS; k += 256) {
-    const uint64_t i = base + k;
-    if (i < n && tier[i] < NT) c[tier[i]]++;
-  }
-#pragma unroll
-  for (int k = 0; k < NT; k++) {
-    uint32_t v = c[k];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&h[k], v);
-  }
-  __syncthreads();
-  if (threadIdx.x < NT) block_hist[threadIdx.x * n_blocks + blockIdx.x] = h[threadIdx.x];
-}
-
-// exclusive scan of block_hist per tier (each tier's list starts at 0); totals[k] = tier size
-__global__ __launch_bounds__(1024) void k_tier_scan(uint32_t *__restrict__ block_hist, uint32_t n_blocks,
-                                                    uint32_t *__restrict__ totals) {
-  __shared__ uint32_t part[1024];
-  const uint32_t k = blockIdx.x;   // tier
-  uint32_t *a = block_hist + (size_t)k * n_blocks;
-  const uint32_t per = (n_blocks + 1023) / 1024;
-  const uint32_t lo = min(n_blocks, threadIdx.x * per), hi = min(n_blocks, lo + per);
-  uint32_t sum = 0;
-  for (uint32_t i = lo; i < hi; i++) sum += a[i];
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t run = 0;
-    for (uint32_t i = 0; i < 1024; i++) {
-      const uint32_t v = part[i];
-      part[i] = run;
-      run += v;
-    }
-    totals[k] = run;
-  }
-  __syncthreads();
-  uint32_t run = part[threadIdx.x];
-  for (uint32_t i = lo; i < hi; i++) {
-    const uint32_t v = a[i];
-    a[i] = run;
-    run += v;
-  }
-}
-
-struct TierLists {
-  uint32_t *list[NT];
-};
-__global__ __launch_bounds__(256) void k_tier_scatter(const uint8_t *__restrict__ tier, uint64_t n,
-                                                      const uint32_t *__restrict__ block_hist, uint32_t n_blocks,
-                                                      TierLists out) {
-  __shared__ uint32_t base[NT];      // running position of each tier inside this block
-  __shared__ uint32_t wave_cnt[NT][4];
-  if (threadIdx.x < NT) base[threadIdx.x] = block_hist[threadIdx.x * n_blocks + blockIdx.x];
-  __syncthreads();
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint64_t b0 = (uint64_t)blockIdx.x * TIER_ITEMS;
-  for (uint32_t r = 0; r < TIER_ITEMS / 256; r++) {
-    const uint64_t i = b0 + (uint64_t)r * 256 + threadIdx.x;
-    const int tk = (i < n && tier[i] < NT) ? (int)tier[i] : -1;   // bins >= NT: not listed
-    uint32_t rank = 0;
-#pragma unroll
-    for (int k = 0; k < NT; k++) {
-      const uint64_t m = __ballot(tk == k);
-      if (tk == k) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      if (lane == 0) wave_cnt[k][wv] = (uint32_t)__popcll(m);
-    }
-    __syncthreads();
-    if (tk >= 0) {
-      uint32_t off = base[tk] + rank;
-      for (uint32_t w = 0; w < wv; w++) off += wave_cnt[tk][w];
-      out.list[tk][off] = (uint32_t)i;
-    }
-    __syncthreads();
-    if (threadIdx.x < NT)
-      base[threadIdx.x] += wave_cnt[threadIdx.x][0] + wave_cnt[threadIdx.x][1] + wave_cnt[threadIdx.x][2] +
-                           wave_cnt[threadIdx.x][3];
-    __syncthreads();
-  }
-}
-
 // ---- banded anti-diagonal kernel ---------------------------------------------------------------
 // Exact pruning with an a-posteriori certificate.  The group sweeps the 64 diagonals around the
 // seed diagonal; the best score S1 found there is the score of a real alignment, hence a lower
@@ -770,22 +675,13 @@ __global__ __launch_bounds__(256) void k_tier_scatter(const uint8_t *__restrict_
 // from diagonal d+1 (both from step k-1: own registers, or one DPP row shift at the lane
 // boundary) and its own diagonal's H from step k-2.
 // GL = lanes per candidate: 8 (32 diagonals, 8 candidates per wave) or 16 (64 diagonals, 4 per wave).
-// `list` (optional) maps work items to candidates; todo[] is indexed by work item.
+// Work item i is candidate items.list[items.first + i]; a workgroup beyond the list's live length leaves at once.
 template <int LMAX, int GL, int DPL, int BS = 256>
-__global__ __launch_bounds__(BS) void k_sw_band(kslam_overlap *__restrict__ ov, uint64_t n_cap, SwInputs in, SwParams p,
-                                                 uint32_t *__restrict__ band0, const uint32_t *__restrict__ list,
-                                                 Tiers T, int self, const uint32_t *__restrict__ n_dev, uint32_t first,
-                                                 uint32_t n_sure) {
-  // n_dev: the list's length on the device, read now (the list was still growing when the host sized this launch for n_cap
-  // entries from `first` on); a workgroup beyond it leaves at once.  n_sure entries were there when the host looked: a
-  // workgroup inside them does not wait for the load
-  uint64_t n = n_cap;
-  if (n_dev && (uint64_t)(blockIdx.x + 1) * (BS / GL) > n_sure) {
-    const uint32_t tot = *n_dev;
-    n = min(n_cap, (uint64_t)(tot > first ? tot - first : 0u));
-  }
-  if ((uint64_t)blockIdx.x * (BS / GL) >= n) return;   // (block-uniform)
-  list += first;
+__global__ __launch_bounds__(BS) void k_sw_band(kslam_overlap *__restrict__ ov, SwInputs in, SwParams p,
+                                                 uint32_t *__restrict__ band0, ListSlice items, Tiers T, int self) {
+  const uint32_t n = live_len(items, (blockIdx.x + 1) * (BS / GL));
+  if (blockIdx.x * (BS / GL) >= n) return;   // (block-uniform)
+  const uint32_t *__restrict__ list = items.list + items.first;
   constexpr int NG = BS / GL;           // candidates per block
   constexpr int ND = DPL * GL;          // diagonals swept (DPL adjacent diagonals per lane)
   // The sweep also computes cells that lie outside the matrix near its corners (no per-cell range
@@ -804,7 +700,7 @@ __global__ __launch_bounds__(BS) void k_sw_band(kslam_overlap *__restrict__ ov, 
   const int32_t grp = threadIdx.x / GL;
   const uint64_t gi = (uint64_t)blockIdx.x * NG + grp;
   const bool have = gi < n;
-  const uint64_t ci = have ? (list ? list[gi] : gi) : 0;
+  const uint64_t ci = have ? list[gi] : 0;
   int32_t L = 0, W = 0, rel = 0;
   const uint8_t *qc = s_q[grp];
   uint8_t *wc = s_w[grp] + PADM;         // window codes x 6 (the bfe offset)
@@ -990,10 +886,8 @@ __global__ __launch_bounds__(BS) void k_sw_band(kslam_overlap *__restrict__ ov, 
   const bool exact = have && (p.ablate == 3 || band_certifies(f.score, L, W, dlo, ND, p));
   {  // The others move on.  What this band found is a real alignment's score, i.e. a lower bound:
      // it picks the narrowest later tier that is certain to certify (or the full matrix) directly.
-     // One atomic per wave and destination reserves the list slots.
-    const bool fail = have && t == 0 && !exact;
     int dest = -1;
-    if (fail) {
+    if (have && t == 0 && !exact) {
       dest = NT_FULL;
       const int32_t amin = certificate_amin(f.score, L, W, p);
       for (int k = self + 1; k < T.n; k++)
@@ -1002,36 +896,12 @@ __global__ __launch_bounds__(BS) void k_sw_band(kslam_overlap *__restrict__ ov, 
           break;
         }
     }
-    for (int k = self + 1; k <= NT_FULL; k++) {
-      if (k >= T.n && k != NT_FULL) continue;
-      const uint64_t m = __ballot(dest == k);
-      if (!m) continue;
-      uint32_t base = 0;
-      if (lane == (int32_t)__builtin_ctzll(m)) base = atomicAdd(T.counts + k, (uint32_t)__popcll(m));
-      base = __shfl(base, __builtin_ctzll(m), 64);
-      uint32_t *dl = k == NT_FULL ? T.full_list : T.list[k];
-      if (dest == k) dl[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)ci;
-    }
+    wave_append_to_bin(T.bins, dest, (uint32_t)ci);
   }
   sw_epilogue<GL, 6>(ov, ci, exact, t, L, f, qc, wc, p, band0);
 }
 
-}  // namespace
 
-void partition_bins(const uint8_t *d_bins, uint64_t n, uint32_t *const d_lists[8], uint32_t *d_counts, DevBuf &pos,
-                    hipStream_t s) {
-  if (n == 0) return;
-  const uint32_t n_blocks = (uint32_t)((n + TIER_ITEMS - 1) / TIER_ITEMS);
-  pos.ensure((size_t)NT * n_blocks * sizeof(uint32_t));
-  TierLists TL;
-  for (int k = 0; k < NT; k++) TL.list[k] = d_lists[k];
-  hipLaunchKernelGGL(k_tier_hist, dim3(n_blocks), dim3(256), 0, s, d_bins, n, pos.as<uint32_t>(), n_blocks);
-  hipLaunchKernelGGL(k_tier_scan, dim3(NT), dim3(1024), 0, s, pos.as<uint32_t>(), n_blocks, d_counts);
-  hipLaunchKernelGGL(k_tier_scatter, dim3(n_blocks), dim3(256), 0, s, d_bins, n, pos.as<uint32_t>(), n_blocks, TL);
-  HIPCHK(hipGetLastError());
-}
-
-namespace {
 __global__ __launch_bounds__(256) void k_encode(const uint4 *__restrict__ src, uint4 *__restrict__ dst, uint64_t n16) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n16) return;
@@ -1419,41 +1289,28 @@ void sw_scores(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, uint32_
     W.flags.ensure(n);                                   // tier per candidate (u8)
     for (int k = 0; k < T.n; k++) W.tier_list[k].ensure((n + 1) * sizeof(uint32_t));
     W.list.ensure((n + 1) * sizeof(uint32_t));           // list for the full-matrix kernel
-    const uint32_t n_blocks = (uint32_t)((n + TIER_ITEMS - 1) / TIER_ITEMS);
-    W.pos.ensure((size_t)NT * n_blocks * sizeof(uint32_t));
     W.totals.ensure(16 * sizeof(uint32_t));
     uint8_t *tier = W.flags.as<uint8_t>();
     uint32_t *counts = W.totals.as<uint32_t>();          // [k] tier sizes, [NT_FULL] full-matrix list size
     HIPCHK(hipMemsetAsync(counts, 0, 16 * sizeof(uint32_t), s));
-    TierLists TL;
-    for (int k = 0; k < NT; k++) TL.list[k] = W.tier_list[std::min(k, NT_MAX - 1)].as<uint32_t>();
-    for (int k = 0; k < T.n; k++) T.list[k] = W.tier_list[k].as<uint32_t>();
-    T.full_list = W.list.as<uint32_t>();
-    T.counts = counts;
+    for (int k = 0; k < T.n; k++) T.bins.list[k] = W.tier_list[k].as<uint32_t>();
+    T.bins.list[NT_FULL] = W.list.as<uint32_t>();
+    T.bins.count = counts;
     const unsigned pb = (unsigned)std::min<uint64_t>((n + 31) / 32, 256 * (uint64_t)tune.plan_blocks_per_cu);   // its waves walk through the candidates
     if (lm == 0) hipLaunchKernelGGL(k_sw_plan<160>, dim3(pb), dim3(256), 0, s, d_ov, n, in, p, T, tier, d_band0);
     else if (lm == 1) hipLaunchKernelGGL(k_sw_plan<256>, dim3(pb), dim3(256), 0, s, d_ov, n, in, p, T, tier, d_band0);
     else hipLaunchKernelGGL(k_sw_plan<512>, dim3(pb), dim3(256), 0, s, d_ov, n, in, p, T, tier, d_band0);
-    hipLaunchKernelGGL(k_tier_hist, dim3(n_blocks), dim3(256), 0, s, tier, n, W.pos.as<uint32_t>(), n_blocks);
-    hipLaunchKernelGGL(k_tier_scan, dim3(NT), dim3(1024), 0, s, W.pos.as<uint32_t>(), n_blocks, counts);
-    hipLaunchKernelGGL(k_tier_scatter, dim3(n_blocks), dim3(256), 0, s, tier, n, W.pos.as<uint32_t>(), n_blocks, TL);
+    partition_bins(tier, n, T.bins, W.pos, s);
     uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (debug) {
       read_back(h, counts, sizeof h, s);
       fprintf(stderr, "[kslam] SW planned: %u / %u / %u / %u / %u / %u\n", h[0], h[1], h[2], h[3], h[4], h[5]);
     }
-    // One sweep over the tiers without a read-back in front of each (round 6; ~25 us of idle GPU at each of them).  Tier k's
-    // list = what k_sw_plan put there + what the tiers before it send on -- unknown to the host when it queues tier k, known
-    // to the kernel when it runs (n_dev).  The launch is sized for planned + 1.2 x the inflow the LAST chunk of this context
-    // saw at that tier (scaled by the chunks' sizes) + 4096: chunks of one run are statistically alike.  What did not fit,
-    // and what that sends on, is left to rounds after the one read-back: each launches the part of every list nobody has
-    // run yet.  A context's first chunk (no history) and a changed tier set go tier by tier as before.
-    auto launch_tier = [&](int k, uint64_t m, const uint32_t *n_dev, uint32_t first, uint32_t n_sure = 0) {
+    auto launch_tier = [&](int k, const ListSlice &items) {
       const int nd = T.nd[k];
-      const uint32_t *list = T.list[k];
 #define KSLAM_BAND(LM, GLV, DPLV, BSV) \
-  hipLaunchKernelGGL((k_sw_band<LM, GLV, DPLV, BSV>), dim3((unsigned)((m + (BSV / GLV) - 1) / (BSV / GLV))), dim3(BSV), 0, s, \
-                     d_ov, m, in, p, d_band0, list, T, k, n_dev, first, n_sure)
+  hipLaunchKernelGGL((k_sw_band<LM, GLV, DPLV, BSV>), dim3((items.cap + (BSV / GLV) - 1) / (BSV / GLV)), dim3(BSV), 0, s, \
+                     d_ov, in, p, d_band0, items, T, k)
 #define KSLAM_BAND_LM(GLV, DPLV, BSV) \
   do { if (lm == 0) KSLAM_BAND(160, GLV, DPLV, BSV); else if (lm == 1) KSLAM_BAND(256, GLV, DPLV, BSV); \
        else KSLAM_BAND(512, GLV, DPLV, BSV); } while (0)
@@ -1468,44 +1325,36 @@ void sw_scores(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, uint32_
 #undef KSLAM_BAND_LM
 #undef KSLAM_BAND
     };
-    uint32_t planned[NT_MAX] = {0, 0, 0, 0, 0, 0}, done[NT_MAX] = {0, 0, 0, 0, 0, 0};
+    // The tiers go through the one sweep over growing lists (sweep_lists): tier k's list is what k_sw_plan put there plus
+    // what the tiers before it send on.  Pass one sizes tier k for planned + 1.2 x the inflow the LAST chunk of this
+    // context saw at that tier (scaled by the chunks' sizes) + 4096: chunks of one run are statistically alike.  A
+    // context's first chunk (no history) and a changed tier set go tier by tier.
     read_back(h, counts, sizeof h, s);
+    uint32_t planned[NT_MAX] = {0, 0, 0, 0, 0, 0};
     for (int k = 0; k < T.n; k++) planned[k] = h[k];
-    const bool history = W.last_n && W.last_tiers == T.n && W.last_lm == lm && tune.sw_sweep;
+    const bool history = W.last_n && W.last_tiers == T.n && W.last_lm == lm;
+    uint64_t cap[NT_MAX] = {0, 0, 0, 0, 0, 0};
     if (history) {
       const double scale = (double)n / (double)W.last_n;
       for (int k = 0; k < T.n; k++) {
         const uint64_t room = k && tune.sweep_room ? (uint64_t)(1.2 * scale * W.last_inflow[k]) + 4096 : 0;
-        const uint64_t cap = std::min<uint64_t>(n, planned[k] + room);
-        if (debug) fprintf(stderr, "[kslam] SW tier %d (%d diagonals): %u planned, sized for %llu\n", k, T.nd[k], planned[k], (unsigned long long)cap);
-        if (cap) launch_tier(k, cap, counts + k, 0, planned[k]);
-        done[k] = (uint32_t)cap;
+        cap[k] = std::min<uint64_t>(n, planned[k] + room);
+        if (debug) fprintf(stderr, "[kslam] SW tier %d (%d diagonals): %u planned, sized for %llu\n", k, T.nd[k], planned[k], (unsigned long long)cap[k]);
       }
     }
-    for (int round = 0;; round++) {
-      if (round || history) read_back(h, counts, sizeof h, s);
-      bool progressed = false;
-      for (int k = 0; k < T.n; k++) {
-        done[k] = std::min(done[k], h[k]);
-        if (h[k] <= done[k]) continue;
-        const uint64_t m = h[k] - done[k];
-        if (debug) fprintf(stderr, "[kslam] SW round %d tier %d (%d diagonals): %llu candidates%s\n", round, k, T.nd[k], (unsigned long long)m, history ? " left over" : "");
-        launch_tier(k, m, nullptr, done[k]);
-        done[k] = h[k];
-        progressed = true;
-        if (!history) {    // tier by tier: the next tier's size is known once this one has run
-          read_back(h, counts, sizeof h, s);
-        }
-      }
-      if (!progressed) break;
-    }
+    sweep_lists(T.n, counts, h, sizeof h, cap, !history,
+                [&](uint32_t k, uint64_t m, uint32_t first, const uint32_t *count_dev, uint32_t sure, int round) {
+                  if (debug && round >= 0)
+                    fprintf(stderr, "[kslam] SW round %d tier %d (%d diagonals): %llu candidates%s\n", round, (int)k, T.nd[k], (unsigned long long)m, history ? " left over" : "");
+                  launch_tier((int)k, ListSlice{T.bins.list[k], first, (uint32_t)m, sure, count_dev});
+                }, nullptr, s);
     W.last_n = n;
     W.last_tiers = T.n;
     W.last_lm = lm;
     for (int k = 0; k < T.n; k++) W.last_inflow[k] = h[k] - planned[k];
     read_back(h, counts, sizeof h, s);      // (the full-matrix list's length: the last round's launches may have added to it)
     n_full = h[NT_FULL];
-    full_list = W.list.as<uint32_t>();
+    full_list = T.bins.list[NT_FULL];
     if (debug) fprintf(stderr, "[kslam] SW full matrix: %llu candidates\n", (unsigned long long)n_full);
   }
   if (n_full_out) *n_full_out = n_full;

@@ -639,9 +639,6 @@ def test_every_kernel_variant_gives_the_same_alignments(kslam, synth, monkeypatc
     variants = [{"KSLAM_CIGAR_SYS": "0", "KSLAM_CIGAR_REG": "0"},   # every CIGAR on the literal one-lane kernel
                 {"KSLAM_CIGAR_SYS": "255"},                          # systolic for every band class
                 {"KSLAM_CIGAR_SYS": "0"},                            # registers for narrow, one-lane for wide
-                {"KSLAM_CIGAR_DIRS": "lds", "KSLAM_CIGAR_SYS": "0", "KSLAM_CIGAR_REG": "0"},
-                {"KSLAM_CIGAR_TB": "inline"},                        # systolic tracebacks at the end of the DP kernel
-                {"KSLAM_CIGAR_TB": "inline", "KSLAM_CIGAR_SYS": "255"},
                 {"KSLAM_SW_FULL": "1"},                              # full-matrix scores only
                 {"KSLAM_SW_NO48": "1"},                              # tiers 16 / 32 / 64 / 96
                 {"KSLAM_SW_NO96": "1"},                              # no 96-diagonal tier
@@ -650,7 +647,6 @@ def test_every_kernel_variant_gives_the_same_alignments(kslam, synth, monkeypatc
                 {"KSLAM_SORT_DIGIT_BYTES": "0"},                     # radix histograms re-read the records
                 {"KSLAM_JOIN_GROUP_ORDER": "0"},                     # overlap keys through all their radix passes (no group ranking)
                 {"KSLAM_SWEEP_ROOM": "0"},                           # CIGAR bins / SW tiers sized without room: every candidate sent on takes the left-over rounds
-                {"KSLAM_SW_SWEEP": "0"},                             # a read-back in front of every SW tier
                 {"KSLAM_JOIN": "merge"},                             # the merge join instead of the probe (join.hip: k_join_merge)
                 {"KSLAM_JOIN": "merge", "KSLAM_SORT_BYTES": "1"},    # ... with read records ordered by their top byte only
                 {"KSLAM_JOIN": "merge", "KSLAM_SORT_BYTES": "8"}]    # ... and by the whole key
