@@ -402,6 +402,7 @@ typedef struct {
 #define KSLAM_TEXT_PAIRS_SORTED 1u
 #define KSLAM_TEXT_SAM 2u
 #define KSLAM_TEXT_PER_READ 4u
+#define KSLAM_TEXT_SAM_BGZF 8u   /* sam_text holds BGZF members (include/kslam_bgzf.h) */
 kslam_status kslam_submit_batch(kslam_ctx *ctx, uint64_t n_reads, const char *const *bases,
                                 const char *const *quality, const uint32_t *lens,
                                 uint64_t *ticket);

@@ -178,7 +178,14 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
     }
     if (sam_planned) {
       sam_stage_mapq(sam);   // pow / log10 / ceil with the host's libm
-      st = guarded(c, [&] { sam_stage_kernels(c, primary, sam, primary->samtext.sam, primary->samtext.per_read); });
+      const bool bgzf = primary->samtext.sam && primary->samtext.bgzf;   // (kslam_set_sam_bgzf) compressed before the copy
+      st = guarded(c, [&] {
+        sam_stage_kernels(c, primary, sam, primary->samtext.sam, primary->samtext.per_read);
+        if (bgzf) {
+          bgzf_compress_device(c->samw.text.as<char>(), sam.text_bytes, c->bgzfw, c->bgzf_out, &sam.text_bytes, c->stream);
+          sam.d_sam = c->bgzf_out.p;
+        }
+      });
       uint64_t n_tax = 0;
       if (st == KSLAM_OK)
         st = guarded(c, [&] {
@@ -186,7 +193,8 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
                           &job->tax, &n_tax);
         });
       if (st == KSLAM_OK)
-        job->text_flags = (primary->samtext.sam ? (KSLAM_TEXT_PAIRS_SORTED | KSLAM_TEXT_SAM) : 0u) | (primary->samtext.per_read ? KSLAM_TEXT_PER_READ : 0u);
+        job->text_flags = (primary->samtext.sam ? (KSLAM_TEXT_PAIRS_SORTED | KSLAM_TEXT_SAM) : 0u) | (primary->samtext.per_read ? KSLAM_TEXT_PER_READ : 0u) |
+                          (bgzf ? KSLAM_TEXT_SAM_BGZF : 0u);
     }
     sam_stage_free(c, sam);
     t3 = now();

@@ -122,6 +122,7 @@ kslam_status kslam_multi_create(const kslam_params *params, const int32_t *devic
       kslam_destroy(c);
       return st;   // the caller reads the message and destroys m
     }
+    c->in_multi = true;
     m->ctx.push_back(c);
   }
   m->send.resize(n_devices);

@@ -112,7 +112,7 @@ void sam_stage_fetch(kslam_ctx *c, SamStage &S, bool want_sam, bool want_per_rea
   try {
     if (want_sam) {
       ht = (char *)pinned_get(c, text_bytes + 64);
-      if (text_bytes) HIPCHK(hipMemcpyAsync(ht, c->samw.text.p, text_bytes, hipMemcpyDeviceToHost, s));
+      if (text_bytes) HIPCHK(hipMemcpyAsync(ht, S.d_sam ? S.d_sam : c->samw.text.p, text_bytes, hipMemcpyDeviceToHost, s));
     }
     if (want_per_read) {
       hp = (char *)pinned_get(c, pr_bytes + 64);
@@ -479,6 +479,45 @@ kslam_status kslam_sam_text(kslam_ctx *c, int paired, uint32_t num_alignments, i
   });
   if (c) sam_stage_free(c, S);
   return st;
+}
+
+// ---- BGZF (include/kslam_bgzf.h, csrc/bgzf.hip) ----
+kslam_status kslam_bgzf_compress(kslam_ctx *c, const void *data, uint64_t len, char **out, uint64_t *out_len) {
+  if (out) *out = nullptr;
+  if (out_len) *out_len = 0;
+  char *h = nullptr;
+  const kslam_status st = guarded(c, [&] {
+    if (!out || !out_len || (len && !data)) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+    uint64_t n_out = 0;
+    if (len) {
+      c->bgzf_in.ensure(len + 64);
+      HIPCHK(hipMemcpyAsync(c->bgzf_in.p, data, len, hipMemcpyHostToDevice, c->stream));
+      bgzf_compress_device(c->bgzf_in.as<char>(), len, c->bgzfw, c->bgzf_out, &n_out, c->stream);
+    }
+    h = (char *)pinned_get(c, n_out + 64);
+    if (n_out) {
+      HIPCHK(hipMemcpyAsync(h, c->bgzf_out.p, n_out, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(stream_wait(c->stream));
+    }
+    *out = h;
+    *out_len = n_out;
+  });
+  if (st != KSLAM_OK && h) pinned_put(c, h);
+  if (st != KSLAM_OK && out) *out = nullptr;
+  return st;
+}
+
+kslam_status kslam_set_sam_bgzf(kslam_ctx *c, int on) {
+  return guarded(c, [&] {
+    if (c->in_multi) throw StatusError{KSLAM_ERR_UNSUPPORTED, "BGZF output is not available on the contexts of a kslam_multi"};
+    c->samtext.bgzf = on != 0;
+  });
+}
+
+kslam_status kslam_get_sam_bgzf(kslam_ctx *c, int *on) {
+  if (!c || !on) return KSLAM_ERR_ARG;
+  *on = c->samtext.bgzf ? 1 : 0;
+  return KSLAM_OK;
 }
 
 kslam_status kslam_take_pairs(kslam_ctx *c, kslam_read_pair **read_pairs, uint64_t *n_read_pairs, kslam_paired_overlap **pairs,

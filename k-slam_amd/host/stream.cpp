@@ -20,6 +20,7 @@
 #include "../../include/kslam_fastq.h"
 #include "../../include/kslam_stream.h"
 #include "../../include/kslam_samtext.h"
+#include "../../include/kslam_bgzf.h"
 #include "workers.hpp"
 
 namespace {
@@ -106,9 +107,23 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
       text_set = true;
     }
+    // BGZF (include/kslam_bgzf.h): every SAM byte goes to the writer compressed -- the lanes compress what they format, the
+    // header and any host-formatted batch go through kslam_bgzf_compress here; the EOF marker ends the file
+    int bgzf = 0;
+    if (kslam_get_sam_bgzf(ctx, &bgzf) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    static const auto give_back = [](void *user, void *data) { kslam_free_pinned(static_cast<kslam_ctx *>(user), data); };
+    auto enqueue_compressed = [&](const char *text, uint64_t len) -> uint64_t {
+      char *z = nullptr;
+      uint64_t zlen = 0;
+      if (kslam_bgzf_compress(ctx, text, len, &z, &zlen) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      if (kslam_sam_writer_enqueue(writer, z, zlen, +give_back, ctx) != KSLAM_OK) fail(KSLAM_ERR_ARG, kslam_tail_last_error());
+      return zlen;
+    };
     if (P->sam_fd >= 0) {
       if (kslam_sam_writer_open(P->sam_fd, &writer) != KSLAM_OK) fail(KSLAM_ERR_ARG, "could not start the SAM writer");
-      if (P->sam_header && P->sam_header_len && kslam_write_queued(writer, P->sam_header, P->sam_header_len) != 0)
+      if (bgzf && P->sam_header && P->sam_header_len)
+        enqueue_compressed(P->sam_header, P->sam_header_len);
+      else if (P->sam_header && P->sam_header_len && kslam_write_queued(writer, P->sam_header, P->sam_header_len) != 0)
         fail(KSLAM_ERR_ARG, "writing the SAM header failed");
     }
     kslam_tail_params host_all = P->tail, host_write = P->tail, host_sorted = P->tail;   // what the host stage still has to run
@@ -223,13 +238,16 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         s = guarded([&] {   // written on the GPU: the page-locked block joins the writer's queue as it is and goes back to the
                             // context's pool once it is in the file
           const double t0 = now_ms();
-          char *block = res.sam_text;
-          const uint64_t len = res.sam_text_len;
-          res.sam_text = nullptr;   // the writer owns it now
-          static const auto give_back = [](void *user, void *data) { kslam_free_pinned(static_cast<kslam_ctx *>(user), data); };
-          if (kslam_sam_writer_enqueue(writer, block, len, +give_back, ctx) != KSLAM_OK) fail(KSLAM_ERR_ARG, kslam_tail_last_error());
+          if (bgzf && !(res.text_flags & KSLAM_TEXT_SAM_BGZF)) {   // (the switch went on after the batch was formatted)
+            st.sam_bytes += enqueue_compressed(res.sam_text, res.sam_text_len);
+          } else {
+            char *block = res.sam_text;
+            const uint64_t len = res.sam_text_len;
+            res.sam_text = nullptr;   // the writer owns it now
+            if (kslam_sam_writer_enqueue(writer, block, len, +give_back, ctx) != KSLAM_OK) fail(KSLAM_ERR_ARG, kslam_tail_last_error());
+            st.sam_bytes += len;
+          }
           st.seconds_sam_text += (now_ms() - t0) * 1e-3;
-          st.sam_bytes += len;
         });
         if (s != KSLAM_OK) err = g_err;
       } else if (s == KSLAM_OK && writer) {
@@ -237,13 +255,19 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
           kslam_tail_stats ts;
           memset(&ts, 0, sizeof ts);
           const double t0 = now_ms();
+          // BGZF: the batch's text is gathered whole and compressed like a device-formatted one (same members, same bytes)
+          std::string text;
+          static const kslam_write_fn append = [](void *user, const char *data, uint64_t len) -> int {
+            static_cast<std::string *>(user)->append(data, len);
+            return 0;
+          };
           const kslam_status a = kslam_tail_finish_write_rows(&host_sorted, &reads, index, res.overlaps, res.n_overlaps, res.cigar_pool,
                                                               res.n_cigar, res.details, res.md_pool, res.n_md, res.read_pairs,
-                                                              res.n_read_pairs, res.pairs, res.n_pairs, kslam_write_queued,
-                                                              (void *)writer, &ts);
+                                                              res.n_read_pairs, res.pairs, res.n_pairs, bgzf ? append : kslam_write_queued,
+                                                              bgzf ? (void *)&text : (void *)writer, &ts);
           if (a != KSLAM_OK) fail(a, kslam_tail_last_error());
+          st.sam_bytes += bgzf ? enqueue_compressed(text.data(), text.size()) : ts.sam_bytes;
           st.seconds_sam_text += (now_ms() - t0) * 1e-3;
-          st.sam_bytes += ts.sam_bytes;
         });
         if (s != KSLAM_OK) err = g_err;
       }
@@ -301,6 +325,7 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     }
     if (worker.joinable()) worker.join();
     if (worker_status != KSLAM_OK) fail(worker_status, worker_error);
+    if (writer && bgzf && kslam_write_queued(writer, KSLAM_BGZF_EOF, KSLAM_BGZF_EOF_LEN) != 0) fail(KSLAM_ERR_ARG, "writing the BGZF EOF marker failed");
   });
 
   const double t_close = now_ms();

@@ -28,6 +28,7 @@
 #include <unistd.h>
 #include <vector>
 
+#include "../include/kslam_bgzf.h"
 #include "../include/kslam_db.h"
 #include "../include/kslam_stream.h"
 
@@ -65,7 +66,7 @@ struct Options {
   uint32_t score_threshold = 0, match = 2, mismatch = 3, gap_open = 5, gap_extend = 2;
   uint32_t num_reads = UINT32_MAX, num_reads_at_once = 10000000, num_alignments = 10;
   double score_fraction = 0.95;
-  bool sam_xa = false, just_align = false, no_pseudo = false, help = false, version = false, parse_fasta = false;
+  bool sam_xa = false, just_align = false, no_pseudo = false, help = false, version = false, parse_fasta = false, sam_bgzf = false;
   int device = 0;
   std::vector<std::string> inputs;
 };
@@ -102,13 +103,14 @@ void usage(FILE *o) {
         "  --version                             print version number\n"
         "  --just-align                          only perform alignments, not metagenomics\n"
         "  --no-pseudo-assembly                  do not link alignments together\n"
+        "  --sam-bgzf                            write --sam-file as BGZF (blocked gzip, as bgzip writes it)\n"
         "\n", o);
 }
 
 Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
-         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED };
+         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -122,6 +124,7 @@ Options parse(int argc, char **argv) {
       {"parse-genbank", no_argument, nullptr, UNSUPPORTED}, {"parse-taxonomy", no_argument, nullptr, UNSUPPORTED},
       {"server", no_argument, nullptr, UNSUPPORTED}, {"alignment-only", no_argument, nullptr, IGNORED},   // declared, never read (src/main.cpp:80-82)
       {"device", required_argument, nullptr, DEVICE},   // not in the reference: the HIP device ordinal (default 0)
+      {"sam-bgzf", no_argument, nullptr, SAM_BGZF},     // not in the reference: the SAM file as BGZF (include/kslam_bgzf.h)
       {nullptr, 0, nullptr, 0}};
   opterr = 0;
   int c;
@@ -148,6 +151,7 @@ Options parse(int argc, char **argv) {
       case SAM: o.sam = optarg; break;
       case NALIGN: o.num_alignments = to_u32(optarg, "num-alignments"); break;
       case XA: o.sam_xa = true; break;
+      case SAM_BGZF: o.sam_bgzf = true; break;
       case VERSION: o.version = true; break;
       case JUST: o.just_align = true; break;
       case NOPSEUDO: o.no_pseudo = true; break;
@@ -322,6 +326,7 @@ int run(const Options &o, const std::string &command_line) {
   kp.device = o.device;
   kslam_ctx *ctx = nullptr;
   if (kslam_create(&kp, &ctx) != KSLAM_OK) die(std::string("GPU context: ") + (ctx ? kslam_last_error(ctx) : "kslam_create failed"));
+  if (o.sam_bgzf && want_sam && kslam_set_sam_bgzf(ctx, 1) != KSLAM_OK) die(std::string("BGZF: ") + kslam_last_error(ctx));
   logl("Getting k-mers from index");
   if (kslam_set_index(ctx, index->n_entries, kslam_db_entry_bases(db), kslam_db_entry_lengths(db)) != KSLAM_OK)
     die(std::string("index: ") + kslam_last_error(ctx));
@@ -383,12 +388,15 @@ int run(const Options &o, const std::string &command_line) {
     }
     n_pairs = st.n_pairs;
   }
+  uint64_t sam_file_bytes = st.sam_bytes + header_len;
+  struct stat sam_stat;
+  if (sam_fd >= 0 && o.sam_bgzf && fstat(sam_fd, &sam_stat) == 0) sam_file_bytes = (uint64_t)sam_stat.st_size;   // compressed
   if (sam_fd >= 0) close(sam_fd);
   if (per_read_fd >= 0) close(per_read_fd);
   logl(cat("Found ", st.n_overlaps, " k-mer overlaps"));
   logl(cat("", st.n_read_pairs_aligned, " entries have k-mer overlaps"));
   if (paired && st.n_batches) logl(cat("Screening all alignment pairs with insert size >= ", st.first_max_insert_size, ""));
-  if (want_sam) logl(cat("Writing SAM output (", st.sam_bytes + header_len, " bytes)"));
+  if (want_sam) logl(cat("Writing SAM output (", sam_file_bytes, " bytes)"));
   logl("Processed\t" + std::to_string(n_pairs) + "\t reads");
   if (o.just_align) {
     logl("Done");
