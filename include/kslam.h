@@ -150,11 +150,11 @@ kslam_status kslam_reload_tuning(kslam_ctx *ctx);
 /* the HIP device ordinal the context owns (-1: none) */
 int32_t kslam_ctx_device(const kslam_ctx *ctx);
 
-/* A second context on the same device that BORROWS `primary`'s index (same device pointers; nothing of the
- * index is copied or freed by the sibling) and has its own stream, read batch and work buffers -- what the
- * pipelined lanes are made of.  For a host that keeps two batches resident at once (bench.py: a rank's shard in
- * one context, the whole batch for the batch-global tail in another).  Destroy it before the primary; it sees
- * a later kslam_set_index of the primary only after being re-created. */
+/* A second context on the same device that SHARES `primary`'s index (nothing of the index is copied; it lives
+ * while a context holds it) and has its own stream, read batch and work buffers -- what the pipelined lanes are
+ * made of.  For a host that keeps two batches resident at once (bench.py: a rank's shard in one context, the
+ * whole batch for the batch-global tail in another).  Destroy it before the primary.  It keeps the index it was
+ * created with: it sees a later kslam_set_index of the primary only after being re-created. */
 kslam_status kslam_create_sibling(kslam_ctx *primary, kslam_ctx **out);
 
 /* ---- the index: const GenbankIndex& (src/GenbankTools.h:187-220) ------

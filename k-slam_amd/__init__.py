@@ -250,7 +250,8 @@ class Context:
             raise KslamError(st, self._L.kslam_last_error(self._h).decode())
 
     def sibling(self):
-        """kslam_create_sibling: a second context on this device that borrows this context's index"""
+        """kslam_create_sibling: a second context on this device that shares this context's index (until it is re-created,
+        it keeps the index this context had at the time)"""
         h = C.c_void_p()
         self._chk(self._L.kslam_create_sibling(self._h, C.byref(h)))
         c = Context.__new__(Context)

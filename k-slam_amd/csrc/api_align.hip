@@ -89,11 +89,11 @@ float ev_ms(hipEvent_t a, hipEvent_t b) {
 
 // the hot path on the resident reads; stop_after_join: only rows a-3..a-6
 void align_resident(kslam_ctx *c, bool stop_after_join, uint64_t *n_raw_out, PairingHook *hook) {
-  if (!c->have_index) throw StatusError{KSLAM_ERR_STATE, "kslam_set_index has not been called"};
+  const GenomeIndex &ix = c->need_index();
   if (!c->have_reads) throw StatusError{KSLAM_ERR_STATE, "no reads loaded"};
   hipStream_t s = c->stream;
   kslam_timings tm{};
-  tm.n_genome_kmers = c->n_gk;
+  tm.n_genome_kmers = ix.n_gk;
   c->n_res = 0;
   c->n_cig = 0;
   c->have_details = false;
@@ -106,9 +106,9 @@ void align_resident(kslam_ctx *c, bool stop_after_join, uint64_t *n_raw_out, Pai
 
   // overlap key layout: read (chunk local) | entry | rel + bias | revcomp
   OverlapKeyLayout lay;
-  lay.bits_entry = bits_for(c->n_entries ? c->n_entries - 1 : 0);
+  lay.bits_entry = bits_for(ix.n_entries ? ix.n_entries - 1 : 0);
   lay.rel_bias = c->max_read_len;
-  lay.bits_rel = bits_for(c->max_entry_len + c->max_read_len);
+  lay.bits_rel = bits_for(ix.max_entry_len + c->max_read_len);
   if (lay.bits_entry + lay.bits_rel + 1 > 56)
     throw StatusError{KSLAM_ERR_UNSUPPORTED, "entry count x entry length too large for the packed overlap key"};
   const uint32_t max_bits_read = 63 - lay.bits_entry - lay.bits_rel;
@@ -117,12 +117,12 @@ void align_resident(kslam_ctx *c, bool stop_after_join, uint64_t *n_raw_out, Pai
   const uint64_t max_chunk_kmers = c->prm.max_kmers_per_chunk ? c->prm.max_kmers_per_chunk : (1ull << 30);
 
   GenomeIndexDev g;
-  g.key = c->gk_key.as<uint64_t>(); g.mo = c->gk_meta.as<uint2>();
-  g.bucket = c->g_bucket.as<uint32_t>(); g.bucket_bits = c->bucket_bits; g.n = (uint32_t)c->n_gk;
+  g.key = ix.gk_key.as<uint64_t>(); g.mo = ix.gk_meta.as<uint2>();
+  g.bucket = ix.g_bucket.as<uint32_t>(); g.bucket_bits = ix.bucket_bits; g.n = (uint32_t)ix.n_gk;
   SwInputs in;
   in.read_bases = c->r_bases.as<uint8_t>(); in.read_off = c->r_off.as<uint64_t>();
-  in.genome_bases = c->g_bases.as<uint8_t>(); in.genome_off = c->g_off.as<uint64_t>();
-  in.read_codes = c->r_codes.as<uint8_t>(); in.genome_codes = c->g_codes.as<uint8_t>();
+  in.genome_bases = ix.g_bases.as<uint8_t>(); in.genome_off = ix.g_off.as<uint64_t>();
+  in.read_codes = c->r_codes.as<uint8_t>(); in.genome_codes = ix.g_codes.as<uint8_t>();
   SwParams sp;
   sp.match = (int32_t)c->prm.match; sp.mismatch = (int32_t)c->prm.mismatch;
   sp.gap_open = (int32_t)c->prm.gap_open; sp.gap_extend = (int32_t)c->prm.gap_extend;
@@ -136,9 +136,9 @@ void align_resident(kslam_ctx *c, bool stop_after_join, uint64_t *n_raw_out, Pai
   // is re-sorted by (read, entry, rel)).  KSLAM_SORT_BYTES overrides (8 = full 64-bit order).
   std::vector<SortPass> kpasses;
   {
-    uint32_t nbytes = (std::min(c->bucket_bits, 24u) + 7) / 8;
+    uint32_t nbytes = (std::min(ix.bucket_bits, 24u) + 7) / 8;
     if (c->tune.sort_bytes >= 0) nbytes = (uint32_t)c->tune.sort_bytes;
-    nbytes = std::min(8u, std::max(c->filter_bits ? 0u : 1u, nbytes));   // 0: look the survivors up unsorted
+    nbytes = std::min(8u, std::max(ix.filter_bits ? 0u : 1u, nbytes));   // 0: look the survivors up unsorted
     for (uint32_t b = 8 - nbytes; b < 8; b++) kpasses.push_back(SortPass{b / 4, 8 * (b % 4), 0});
   }
   tm.sort_passes = (uint32_t)kpasses.size();
@@ -182,7 +182,7 @@ void align_resident(kslam_ctx *c, bool stop_after_join, uint64_t *n_raw_out, Pai
     // ---- a-3: read k-mer extraction ----
     HIPCHK(hipEventRecord(c->ev[0], s));
     uint64_t nk = nk_all;
-    const bool use_filter = c->filter_bits && !long_chunk;   // (k_extract_filter packs a read into 36 words)
+    const bool use_filter = ix.filter_bits && !long_chunk;   // (k_extract_filter packs a read into 36 words)
     if (use_filter && nk_all) {
       // only the k-mers the genome filter lets through are written; buffer sized from the last chunk,
       // rerun once with the exact size if it was too small
@@ -195,7 +195,7 @@ void align_resident(kslam_ctx *c, bool stop_after_join, uint64_t *n_raw_out, Pai
       for (int attempt = 0; attempt < 2; attempt++) {
         c->recs_a.ensure((cap + 1) * sizeof(uint4));
         if (with_digits) c->sortws.digits.ensure(cap + 64);
-        extract_filtered(c->r_bases.as<uint8_t>(), d_off, (uint32_t)nr, c->g_filter.p, c->filter_bits,
+        extract_filtered(c->r_bases.as<uint8_t>(), d_off, (uint32_t)nr, ix.g_filter.p, ix.filter_bits,
                          c->recs_a.as<uint4>(), d_tot + 2, cap, c->tune, s, with_digits ? c->sortws.digits.as<uint8_t>() : nullptr,
                          with_digits ? kpasses[0].word : 0u, with_digits ? kpasses[0].shift : 0u);
         read_back(&nk, d_tot + 2, sizeof nk, s);

@@ -170,15 +170,7 @@ void validate_params(const kslam_params &p) {
 }
 
 void share_index(kslam_ctx *dst, const kslam_ctx *src) {
-  dst->borrowed_index = true;
-  dst->have_index = src->have_index;
-  dst->index_stats = src->index_stats;
-  dst->n_entries = src->n_entries; dst->max_entry_len = src->max_entry_len; dst->h_goff = src->h_goff;
-  // views, not owners (DevBuf::borrow frees what dst owned before: an index of its own, if it had one)
-  dst->g_bases.borrow(src->g_bases); dst->g_off.borrow(src->g_off); dst->g_codes.borrow(src->g_codes);
-  dst->n_gk = src->n_gk; dst->gk_key.borrow(src->gk_key); dst->gk_meta.borrow(src->gk_meta); dst->gk_off.borrow(src->gk_off);
-  dst->g_bucket.borrow(src->g_bucket); dst->bucket_bits = src->bucket_bits;
-  dst->g_filter.borrow(src->g_filter); dst->filter_bits = src->filter_bits;
+  dst->index = src->index;
   dst->kept_last = 0;
   dst->pairing = src->pairing;
 }
@@ -241,25 +233,6 @@ void kslam_destroy(kslam_ctx *c) {
   if (c->device >= 0) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    // (a lane's / sibling's view of its primary's index is not freed: DevBuf::borrowed)
-    DevBuf *bufs[] = {&c->g_codes, &c->r_codes, &c->g_bases, &c->g_off, &c->gk_key, &c->gk_meta, &c->gk_off, &c->g_bucket, &c->g_filter, &c->r_bases,
-                      &c->r_off, &c->r_len, &c->nk, &c->nseg, &c->rec_start, &c->seg_start, &c->segs, &c->scan_tmp,
-                      &c->totals, &c->recs_a, &c->recs_b, &c->block_tot, &c->block_base, &c->ovk_a, &c->ovk_b,
-                      &c->flags, &c->pos, &c->band0, &c->sortws.hist, &c->sortws.status, &c->sortws.tickets, &c->sortws.digits,
-                      &c->cig.flags, &c->cig.pos, &c->cig.list, &c->cig.bmax, &c->cig.needbig,
-                      &c->cig.scan_tmp, &c->cig.totals, &c->cig.cig_off, &c->cig.tmp, &c->cig.tmp_big,
-                      &c->cig.big_pos, &c->cig.scratch, &c->sww.flags, &c->sww.pos, &c->sww.list, &c->sww.totals, &c->cells, &c->res_ov, &c->res_cig, &c->res_tmp, &c->r_qual, &c->d_tables, &c->res_det, &c->fq_text, &c->fq_bases_at, &c->fq_qual_at, &c->fqw.tile_count, &c->fqw.tile_base, &c->fqw.scan_tmp,
-                      &c->fqw.totals, &c->fqw.ev[0], &c->fqw.ev[1], &c->fqw.bases_at, &c->fqw.quality_at, &c->fqw.blen, &c->fqw.id_at,
-                      &c->fqw.id_len, &c->fqw.bases_off, &c->fqw.ids_off, &c->fqw.ids, &c->detw.lens, &c->detw.off,
-                      &c->detw.slots, &c->detw.scan_tmp, &c->detw.totals, &c->detw.md_pool, &c->pw.recs, &c->pw.count, &c->pw.base,
-                      &c->pw.inserts, &c->pw.flags, &c->pw.gpos, &c->pw.rpos, &c->pw.scan_tmp, &c->pw.totals, &c->pw.groups,
-                      &c->pw.dense, &c->pw.sort_a, &c->pw.sort_b, &c->pw.idx, &c->pw.picked, &c->pw.row_list, &c->pw.row_start, &c->pw.gaps, &c->pr_ov, &c->pr_len, &c->mg_shards, &c->mg_lens, &c->mg_off, &c->mg_scan};
-    for (DevBuf *b : bufs) b->release();
-    for (auto &b : c->annot_bufs) b.release();
-    DevBuf *sam_bufs[] = {&c->samw.plan, &c->samw.cnt_vals, &c->samw.cnt_segs, &c->samw.val_off, &c->samw.seg_off, &c->samw.scan_tmp,
-                          &c->samw.totals, &c->samw.vals, &c->samw.seg_len, &c->samw.mapq, &c->samw.text_len, &c->samw.text_off,
-                          &c->samw.text, &c->samw.tax_ids, &c->samw.pr_len, &c->samw.pr_off, &c->samw.pr_text, &c->ids_buf, &c->ids_off_buf};
-    for (DevBuf *b : sam_bufs) b->release();
     {
       std::lock_guard<std::mutex> lk(c->pin_mu);
       for (auto &b : c->pinned) pinned_free(b.p, b.cap);
@@ -270,7 +243,7 @@ void kslam_destroy(kslam_ctx *c) {
     for (auto &ev : c->evs1) if (ev) (void)hipEventDestroy(ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
   }
-  delete c;
+  delete c;   // every DevBuf frees itself, the index with the last context that holds it
 }
 
 const char *kslam_last_error(const kslam_ctx *c) { return c ? c->err.c_str() : "null context"; }

@@ -85,15 +85,28 @@ void run_extract(kslam_ctx *c, const uint8_t *d_bases, const uint64_t *d_off, ui
   extract_kmers_launch(d_bases, d_off, c->segs.as<SegEntry>(), n_segs, gap, is_gb, 0, d_out, s, d_digits, first_pass);
 }
 
-void build_index(kslam_ctx *c) {
+// kslam_set_index / _device, before the upload: the context and its lanes let go of their index (freed here unless a sibling
+// still holds it, so that the old and the new one are not resident together) and the new one starts empty
+std::shared_ptr<GenomeIndex> new_index(kslam_ctx *c, uint64_t n_entries) {
+  c->index.reset();
+  for (auto *l : c->lanes) l->c->index.reset();
+  auto ix = std::make_shared<GenomeIndex>();
+  ix->n_entries = n_entries;
+  ix->h_goff.assign(n_entries + 1, 0);
+  return ix;
+}
+
+// builds the uploaded index ixp and hands it to the context and its lanes (no batch may be in flight across kslam_set_index)
+void build_index(kslam_ctx *c, std::shared_ptr<GenomeIndex> ixp) {
+  GenomeIndex &ix = *ixp;
   hipStream_t s = c->stream;
-  const uint64_t n = c->n_entries;
-  c->max_entry_len = 0;
-  for (uint64_t i = 0; i < n; i++) c->max_entry_len = std::max(c->max_entry_len, c->h_goff[i + 1] - c->h_goff[i]);
+  const uint64_t n = ix.n_entries;
+  ix.max_entry_len = 0;
+  for (uint64_t i = 0; i < n; i++) ix.max_entry_len = std::max(ix.max_entry_len, ix.h_goff[i + 1] - ix.h_goff[i]);
   if (n >= (1ull << 30)) throw StatusError{KSLAM_ERR_UNSUPPORTED, "more than 2^30 entries (KMer.h:65 id field)"};
-  if (c->max_entry_len >= (1ull << 32)) throw StatusError{KSLAM_ERR_UNSUPPORTED, "entry longer than 2^32 bases"};
-  c->g_off.ensure((n + 1) * sizeof(uint64_t));
-  HIPCHK(hipMemcpyAsync(c->g_off.p, c->h_goff.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  if (ix.max_entry_len >= (1ull << 32)) throw StatusError{KSLAM_ERR_UNSUPPORTED, "entry longer than 2^32 bases"};
+  ix.g_off.ensure((n + 1) * sizeof(uint64_t));
+  HIPCHK(hipMemcpyAsync(ix.g_off.p, ix.h_goff.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
   struct Events {       // destroyed on every way out of this function
     hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
     ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
@@ -101,11 +114,11 @@ void build_index(kslam_ctx *c) {
   for (hipEvent_t &x : evs.e) HIPCHK(hipEventCreate(&x));
   hipEvent_t ev_begin = evs.e[0], e1 = evs.e[1], e2 = evs.e[2], e3 = evs.e[3];
   HIPCHK(hipEventRecord(ev_begin, s));
-  c->g_codes.ensure(c->h_goff[n] + 64);
-  encode_bases(c->g_bases.as<uint8_t>(), c->g_codes.as<uint8_t>(), c->h_goff[n] + 48, s);
-  Planned pl = plan_host(c->h_goff.data(), n, KSLAM_K / 2);  // gap k/2, SLAM.h:64
+  ix.g_codes.ensure(ix.h_goff[n] + 64);
+  encode_bases(ix.g_bases.as<uint8_t>(), ix.g_codes.as<uint8_t>(), ix.h_goff[n] + 48, s);
+  Planned pl = plan_host(ix.h_goff.data(), n, KSLAM_K / 2);  // gap k/2, SLAM.h:64
   if (pl.n_kmers >= (1ull << 32)) throw StatusError{KSLAM_ERR_UNSUPPORTED, "more than 2^32 genome k-mers"};
-  c->n_gk = pl.n_kmers;
+  ix.n_gk = pl.n_kmers;
   const uint64_t m = pl.n_kmers;
   c->recs_a.ensure((m + 1) * sizeof(uint4));
   c->recs_b.ensure((m + 1) * sizeof(uint4));
@@ -133,7 +146,7 @@ void build_index(kslam_ctx *c) {
   // record instead of 16
   const bool first_digits = c->tune.sort_digit_bytes && passes.size() > 1;
   if (first_digits) c->sortws.digits.ensure(m + 64);
-  run_extract(c, c->g_bases.as<uint8_t>(), c->g_off.as<uint64_t>(), n, KSLAM_K / 2, 1, pl.n_segs,
+  run_extract(c, ix.g_bases.as<uint8_t>(), ix.g_off.as<uint64_t>(), n, KSLAM_K / 2, 1, pl.n_segs,
               c->recs_a.as<uint4>(), first_digits ? c->sortws.digits.as<uint8_t>() : nullptr, first_digits ? &passes[0] : nullptr);
   c->sortws.use_digit_bytes = c->tune.sort_digit_bytes;
   c->sortws.first_digits_ready = first_digits;
@@ -144,13 +157,13 @@ void build_index(kslam_ctx *c) {
   c->sortws.first_digits_ready = false;
   c->sortws.meta_digits_in_runs = false;
   HIPCHK(hipEventRecord(e2, s));
-  c->gk_key.ensure((m + 1) * sizeof(uint64_t));
-  c->gk_meta.ensure((m + 1) * sizeof(uint2));   // {meta, offset} pairs
+  ix.gk_key.ensure((m + 1) * sizeof(uint64_t));
+  ix.gk_meta.ensure((m + 1) * sizeof(uint2));   // {meta, offset} pairs
   uint32_t bits = 8, max_bits = (uint32_t)c->tune.bucket_bits_max;   // 27: ~2.3 genome k-mers per bucket for a 5 Gb database (537 MB table)
   while (bits < max_bits && (m >> (bits + 2)) != 0) bits++;   // 2 to 4 keys per bucket (measured: 3.06 ms at 27 bits, 3.24 at 26, 3.13 at 28)
   if (c->tune.bucket_bits_exact) bits = (uint32_t)c->tune.bucket_bits_exact;   // tuning
-  c->bucket_bits = bits;
-  c->g_bucket.ensure(((1ull << bits) + 2) * sizeof(uint32_t));
+  ix.bucket_bits = bits;
+  ix.g_bucket.ensure(((1ull << bits) + 2) * sizeof(uint32_t));
   // membership filter for the read extraction: ~14 bits per genome k-mer (9.3 keys per 128-bit piece),
   // 2^32 bits = 512 MiB for the 312 M k-mers of a 5 Gb database.  KSLAM_FILTER_BITS: log2 of the size
   // in bits, 0 = extract, sort and look up every read k-mer as the reference does.
@@ -161,31 +174,31 @@ void build_index(kslam_ctx *c) {
   // (read_tuning clamps KSLAM_FILTER_BITS to [20, 36], the automatic size starts at 20)
   if (fb != 0 && fb < 20)
     throw StatusError{KSLAM_ERR_INTERNAL, "membership filter of 2^" + std::to_string(fb) + " bits: the smallest is 2^20"};
-  c->filter_bits = fb;
-  if (fb) c->g_filter.ensure(filter_bytes(fb));
+  ix.filter_bits = fb;
+  if (fb) ix.g_filter.ensure(filter_bytes(fb));
   // the probe words of the filter's build go through the record buffers of the sort that has just finished: the one that does not
   // hold the sorted list takes them first
   void *other = sorted == c->recs_a.p ? c->recs_b.p : c->recs_a.p;
   bool fused = false;
   if (fb && c->tune.filter_build_sorted)
-    fused = split_columns_and_tables(sorted, (uint32_t)m, c->gk_key.as<uint64_t>(), c->gk_meta.p, bits, c->g_bucket.as<uint32_t>(), fb, other, c->sortws, s);
+    fused = split_columns_and_tables(sorted, (uint32_t)m, ix.gk_key.as<uint64_t>(), ix.gk_meta.p, bits, ix.g_bucket.as<uint32_t>(), fb, other, c->sortws, s);
   if (!fused) {
     if (m) hipLaunchKernelGGL(k_split_soa, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, (const uint4 *)sorted,
-                              (uint32_t)m, c->gk_key.as<uint64_t>(), c->gk_meta.as<uint2>());
-    build_bucket_table(c->gk_key.as<uint64_t>(), (uint32_t)m, bits, c->g_bucket.as<uint32_t>(), s);
+                              (uint32_t)m, ix.gk_key.as<uint64_t>(), ix.gk_meta.as<uint2>());
+    build_bucket_table(ix.gk_key.as<uint64_t>(), (uint32_t)m, bits, ix.g_bucket.as<uint32_t>(), s);
   }
   if (fb) {
     if (c->tune.filter_build_sorted) {
       c->pos.ensure((filter_bytes(fb) / 32768 + 2) * sizeof(uint32_t));
-      filter_build_sorted(c->gk_key.as<uint64_t>(), (uint32_t)m, fb, c->g_filter.p, other, sorted, c->pos.as<uint32_t>(), c->sortws, s, fused);
+      filter_build_sorted(ix.gk_key.as<uint64_t>(), (uint32_t)m, fb, ix.g_filter.p, other, sorted, c->pos.as<uint32_t>(), c->sortws, s, fused);
     } else {
-      filter_build(c->gk_key.as<uint64_t>(), (uint32_t)m, fb, c->g_filter.p, s);
+      filter_build(ix.gk_key.as<uint64_t>(), (uint32_t)m, fb, ix.g_filter.p, s);
     }
   }
   HIPCHK(hipEventRecord(e3, s));
   HIPCHK(stream_wait(s));
   {
-    kslam_index_stats &st = c->index_stats;
+    kslam_index_stats &st = ix.stats;
     memset(&st, 0, sizeof st);
     st.n_genome_kmers = m;
     st.sort_passes = (uint32_t)passes.size();
@@ -198,9 +211,9 @@ void build_index(kslam_ctx *c) {
     // a batch's sort allocates what its own record count needs
     c->sortws.digits.release();
   }
+  c->index = std::move(ixp);
   c->kept_last = 0;
-  c->have_index = true;
-  for (auto *l : c->lanes) share_index(l->c, c);   // (no batch may be in flight across kslam_set_index)
+  for (auto *l : c->lanes) share_index(l->c, c);
 }
 
 }  // namespace kslam_api
@@ -209,27 +222,26 @@ extern "C" {
 
 kslam_status kslam_index_build_stats(const kslam_ctx *c, kslam_index_stats *out) {
   if (!c || !out) return KSLAM_ERR_ARG;
-  if (!c->have_index) return KSLAM_ERR_STATE;
-  *out = c->index_stats;
+  if (!c->index) return KSLAM_ERR_STATE;
+  *out = c->index->stats;
   return KSLAM_OK;
 }
 
 kslam_status kslam_set_index(kslam_ctx *c, uint64_t n_entries, const char *const *bases, const uint64_t *lens) {
   return guarded(c, [&] {
     if (n_entries && (!bases || !lens)) throw StatusError{KSLAM_ERR_ARG, "null bases/lens"};
-    c->have_index = false;
-    c->n_entries = n_entries;
-    c->h_goff.assign(n_entries + 1, 0);
-    for (uint64_t i = 0; i < n_entries; i++) c->h_goff[i + 1] = c->h_goff[i] + lens[i];
-    const uint64_t total = c->h_goff[n_entries];
-    c->g_bases.ensure(total + 64);
+    auto ixp = new_index(c, n_entries);
+    GenomeIndex &ix = *ixp;
+    for (uint64_t i = 0; i < n_entries; i++) ix.h_goff[i + 1] = ix.h_goff[i] + lens[i];
+    const uint64_t total = ix.h_goff[n_entries];
+    ix.g_bases.ensure(total + 64);
     for (uint64_t i = 0; i < n_entries; i++)
       if (lens[i])
-        HIPCHK(hipMemcpyAsync(c->g_bases.as<uint8_t>() + c->h_goff[i], bases[i], lens[i], hipMemcpyHostToDevice,
+        HIPCHK(hipMemcpyAsync(ix.g_bases.as<uint8_t>() + ix.h_goff[i], bases[i], lens[i], hipMemcpyHostToDevice,
                               c->stream));
-    HIPCHK(hipMemsetAsync(c->g_bases.as<uint8_t>() + total, 0, 64, c->stream));
+    HIPCHK(hipMemsetAsync(ix.g_bases.as<uint8_t>() + total, 0, 64, c->stream));
     HIPCHK(stream_wait(c->stream));
-    build_index(c);
+    build_index(c, std::move(ixp));
   });
 }
 
@@ -237,17 +249,16 @@ kslam_status kslam_set_index_device(kslam_ctx *c, uint64_t n_entries, const void
                                     const uint64_t *h_offsets) {
   return guarded(c, [&] {
     if (n_entries && (!d_bases || !h_offsets)) throw StatusError{KSLAM_ERR_ARG, "null bases/offsets"};
-    c->have_index = false;
-    c->n_entries = n_entries;
-    c->h_goff.assign(n_entries + 1, 0);
+    auto ixp = new_index(c, n_entries);
+    GenomeIndex &ix = *ixp;
     const uint64_t o0 = n_entries ? h_offsets[0] : 0;
-    for (uint64_t i = 0; i <= n_entries && n_entries; i++) c->h_goff[i] = h_offsets[i] - o0;
-    const uint64_t total = c->h_goff[n_entries];
-    c->g_bases.ensure(total + 64);
+    for (uint64_t i = 0; i <= n_entries && n_entries; i++) ix.h_goff[i] = h_offsets[i] - o0;
+    const uint64_t total = ix.h_goff[n_entries];
+    ix.g_bases.ensure(total + 64);
     if (total)
-      HIPCHK(hipMemcpyAsync(c->g_bases.p, (const uint8_t *)d_bases + o0, total, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(c->g_bases.as<uint8_t>() + total, 0, 64, c->stream));
-    build_index(c);
+      HIPCHK(hipMemcpyAsync(ix.g_bases.p, (const uint8_t *)d_bases + o0, total, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(ix.g_bases.as<uint8_t>() + total, 0, 64, c->stream));
+    build_index(c, std::move(ixp));
   });
 }
 

@@ -1,5 +1,5 @@
 // api_lanes.hip -- the C ABI, part 5: the operator pipelined.  Batches alternate between worker lanes (a host thread + a
-// sibling context that borrows the index each); columns, FASTQ fields or whole FASTQ texts in, results (+ pairs, details, SAM text)
+// sibling context that shares the index each); columns, FASTQ fields or whole FASTQ texts in, results (+ pairs, details, SAM text)
 // out through kslam_wait_batch / kslam_collect_batch.
 #include "context.h"
 
@@ -302,7 +302,7 @@ kslam_status kslam_submit_batch(kslam_ctx *c, uint64_t n_reads, const char *cons
   kslam_ctx::AsyncJob *job = nullptr;
   kslam_status st = guarded(c, [&] {
     if (n_reads && (!bases || !lens)) throw StatusError{KSLAM_ERR_ARG, "null bases/lens"};
-    if (!c->have_index) throw StatusError{KSLAM_ERR_STATE, "kslam_set_index has not been called"};
+    c->need_index();
     ensure_lanes(c);
     job = new kslam_ctx::AsyncJob();
     job->n_reads = n_reads;
@@ -359,7 +359,7 @@ kslam_status kslam_submit_batch_columns(kslam_ctx *c, uint64_t n_reads, const ch
   kslam_ctx::AsyncJob *job = nullptr;
   kslam_status st = guarded(c, [&] {
     if (n_reads && (!bases || !offsets)) throw StatusError{KSLAM_ERR_ARG, "null bases/offsets"};
-    if (!c->have_index) throw StatusError{KSLAM_ERR_STATE, "kslam_set_index has not been called"};
+    c->need_index();
     ensure_lanes(c);
     job = new kslam_ctx::AsyncJob();
     job->n_reads = n_reads;
@@ -389,7 +389,7 @@ kslam_status kslam_submit_batch_fastq(kslam_ctx *c, const char *r1, uint64_t len
   kslam_ctx::AsyncJob *job = nullptr;
   kslam_status st = guarded(c, [&] {
     if (n_reads && (!offsets || !bases_at || !quality_at)) throw StatusError{KSLAM_ERR_ARG, "null layout"};
-    if (!c->have_index) throw StatusError{KSLAM_ERR_STATE, "kslam_set_index has not been called"};
+    c->need_index();
     ensure_lanes(c);
     job = new kslam_ctx::AsyncJob();
     job->n_reads = n_reads;
@@ -421,7 +421,7 @@ kslam_status kslam_submit_batch_fastq_text(kslam_ctx *c, const char *r1, uint64_
   kslam_ctx::AsyncJob *job = nullptr;
   kslam_status st = guarded(c, [&] {
     if ((len1 && !r1) || (len2 && !r2)) throw StatusError{KSLAM_ERR_ARG, "null text"};
-    if (!c->have_index) throw StatusError{KSLAM_ERR_STATE, "kslam_set_index has not been called"};
+    c->need_index();
     ensure_lanes(c);
     job = new kslam_ctx::AsyncJob();
     job->borrowed = true;

@@ -29,7 +29,7 @@ void sam_stage_plan(kslam_ctx *c, const kslam_ctx *owner, int paired, uint32_t n
   if (!(c->have_pairs && c->pairs_of_result))
     throw StatusError{KSLAM_ERR_STATE, "kslam_pair_screen has not been called for this result"};
   if (!owner->have_annot) throw StatusError{KSLAM_ERR_STATE, "kslam_set_sam_annotations has not been called"};
-  if (owner->annot.n_entries != c->n_entries) throw StatusError{KSLAM_ERR_STATE, "the annotations belong to another index"};
+  if (owner->annot.n_entries != c->need_index().n_entries) throw StatusError{KSLAM_ERR_STATE, "the annotations belong to another index"};
   if (!c->have_ids) throw StatusError{KSLAM_ERR_STATE, "the batch has no read identifiers on the device (kslam_load_read_ids)"};
   if (c->prm.report_cigar && c->n_cig && !c->have_details)
     throw StatusError{KSLAM_ERR_STATE, "kslam_row_details_of_pairs has not been called for this result"};
@@ -212,8 +212,10 @@ static kslam_status row_details_impl(kslam_ctx *c, uint64_t *n_md, bool of_pairs
       referenced_rows(c->pw, &c->pres, c->n_res, &d_list, &n_list, c->stream);
       if (!d_list) d_list = reinterpret_cast<const uint32_t *>(c->res_det.p);   // (no rows at all: any non-null list of length 0)
     }
+    const GenomeIndex *ix = c->index.get();   // (a context that only adopted rows may have none)
     row_details(c->res_ov.as<kslam_overlap>(), c->n_res, c->res_cig.as<uint32_t>(), c->r_bases.as<uint8_t>(),
-                c->r_qual.as<uint8_t>(), c->r_off.as<uint64_t>(), c->g_bases.as<uint8_t>(), c->g_off.as<uint64_t>(),
+                c->r_qual.as<uint8_t>(), c->r_off.as<uint64_t>(), ix ? ix->g_bases.as<uint8_t>() : nullptr,
+                ix ? ix->g_off.as<uint64_t>() : nullptr,
                 c->d_tables.as<double>(), c->res_det.as<kslam_row_detail>(), c->detw, &c->d_md_pool, &c->n_md,
                 &c->det_flags, c->stream, d_list, n_list);
     HIPCHK(stream_wait(c->stream));
@@ -385,8 +387,7 @@ kslam_status kslam_pair_screen_overlaps(kslam_ctx *c, const kslam_overlap *overl
 kslam_status kslam_set_sam_annotations(kslam_ctx *c, const kslam_index_view *iv, const kslam_taxdb *taxdb) {
   return guarded(c, [&] {
     if (!iv) throw StatusError{KSLAM_ERR_ARG, "null index view"};
-    if (!c->have_index) throw StatusError{KSLAM_ERR_STATE, "kslam_set_index has not been called"};
-    if (iv->n_entries != c->n_entries) throw StatusError{KSLAM_ERR_ARG, "the index view has another number of entries than the index"};
+    if (iv->n_entries != c->need_index().n_entries) throw StatusError{KSLAM_ERR_ARG, "the index view has another number of entries than the index"};
     if (!iv->locus_tag_off || !iv->taxonomy_id) throw StatusError{KSLAM_ERR_ARG, "index view needs locus tags and taxonomy ids"};
     if (iv->n_genes && (!iv->gene_first || !iv->gene_start || !iv->gene_stop || !iv->gene_name_off || !iv->protein_id_off || !iv->product_off))
       throw StatusError{KSLAM_ERR_ARG, "index view has n_genes > 0 but no gene columns"};

@@ -67,32 +67,26 @@ struct Tuning {
 };
 Tuning read_tuning();   // kslam_api.hip
 
-// grow-only device buffer.  Owns its block unless it was made a VIEW of another buffer with borrow() (a sibling context's
-// index, share_index): a view never frees.  No copy-assignment: `a = b` between owners would free the block twice.
+// grow-only device buffer that owns its block.  No copy-assignment: `a = b` would free the block twice.  A buffer
+// several contexts read is shared through the object holding it (GenomeIndex, context.h), never through a second DevBuf.
 struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
-  bool borrowed = false;
   DevBuf() = default;
-  ~DevBuf() { if (p && !borrowed) (void)hipFree(p); }
+  ~DevBuf() { if (p) (void)hipFree(p); }
   DevBuf(const DevBuf &) = delete;
   DevBuf &operator=(const DevBuf &) = delete;
-  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap), borrowed(o.borrowed) { o.p = nullptr; o.cap = 0; o.borrowed = false; }
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
   DevBuf &operator=(DevBuf &&o) noexcept {
     if (this != &o) {
       release();
-      p = o.p; cap = o.cap; borrowed = o.borrowed;
-      o.p = nullptr; o.cap = 0; o.borrowed = false;
+      p = o.p; cap = o.cap;
+      o.p = nullptr; o.cap = 0;
     }
     return *this;
   }
-  // a non-owning view of `o`'s block (whatever this buffer owned before is freed)
-  void borrow(const DevBuf &o) {
-    release();
-    p = o.p; cap = o.cap; borrowed = true;
-  }
   void ensure(size_t bytes) {
-    if (bytes <= cap && !borrowed) return;      // (a view is never written into as if it were ours: it becomes an owner)
+    if (bytes <= cap) return;
     release();
     size_t want = bytes + bytes / 8 + 256;
     hipError_t e = hipMalloc(&p, want);
@@ -104,10 +98,9 @@ struct DevBuf {
     cap = want;
   }
   void release() {
-    if (p && !borrowed) (void)hipFree(p);
+    if (p) (void)hipFree(p);
     p = nullptr;
     cap = 0;
-    borrowed = false;
   }
   template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };

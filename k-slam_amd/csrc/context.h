@@ -22,12 +22,28 @@
 #include <condition_variable>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <sys/prctl.h>
 #include <thread>
 
 using namespace kslam;
+
+// The resident genome index (const GenbankIndex&): what build_index makes, never changed after.  The context that built it,
+// its worker lanes and its siblings share it; kslam_set_index builds a new one and leaves the old one to whoever still holds it.
+struct GenomeIndex {
+  kslam_index_stats stats{};     // phases of the build
+  uint64_t n_entries = 0;
+  uint64_t max_entry_len = 0;
+  std::vector<uint64_t> h_goff;  // [n_entries + 1]
+  DevBuf g_bases, g_off, g_codes;   // g_codes: encode_bases(g_bases)
+  uint64_t n_gk = 0;
+  DevBuf gk_key, gk_meta, g_bucket;
+  uint32_t bucket_bits = 8;
+  DevBuf g_filter;            // membership filter over the genome k-mers (filter.hip); filter_bits = 0: off
+  uint32_t filter_bits = 0;
+};
 
 struct kslam_ctx {
   kslam_params prm{};
@@ -38,21 +54,17 @@ struct kslam_ctx {
   hipEvent_t ev[16]{};
   hipEvent_t evs0[12]{}, evs1[12]{};   // per-pass events around the k-mer scatter kernel
 
-  // ---- index (const GenbankIndex&) ----
+  // ---- index ----
+  // null: no index (kslam_set_index not called, or it failed).  Whatever drops the last reference frees device memory: it runs
+  // with this context's device current (inside guarded() or kslam_destroy).
+  std::shared_ptr<const GenomeIndex> index;
+  const GenomeIndex &need_index() const {
+    if (!index) throw StatusError{KSLAM_ERR_STATE, "kslam_set_index has not been called"};
+    return *index;
+  }
   uint32_t group_route_pause = 0;    // chunks left on the long route after a chunk's overlap keys held a (read, entry) group too
                                      // long for join.hip's group_order (a read in a tandem repeat): such data comes in stretches,
                                      // and a chunk that tries the short route in vain pays for 4 radix passes too many
-  bool have_index = false;
-  kslam_index_stats index_stats{};   // phases of the last build_index (siblings / lanes: a copy of the primary's)
-  uint64_t n_entries = 0;
-  uint64_t max_entry_len = 0;
-  std::vector<uint64_t> h_goff;  // [n_entries + 1]
-  DevBuf g_bases, g_off, g_codes;   // g_codes: encode_bases(g_bases)
-  uint64_t n_gk = 0;
-  DevBuf gk_key, gk_meta, gk_off, g_bucket;
-  uint32_t bucket_bits = 8;
-  DevBuf g_filter;            // membership filter over the genome k-mers (filter.hip); filter_bits = 0: off
-  uint32_t filter_bits = 0;
   uint64_t kept_last = 0;     // survivors of the last chunk (sizes the next chunk's record buffers)
 
   // ---- resident read batch ----
@@ -116,9 +128,7 @@ struct kslam_ctx {
   DevBuf pr_ov, pr_len;          // kslam_pair_screen_overlaps: the records and read lengths handed in
   struct { int paired = 1; uint32_t thr = 0; double fraction = 0.95; uint32_t stages = 0; } pairing;   // for the lanes
 
-  // ---- pipelined entry (kslam_align_batch_async): worker lanes, each a sibling context that BORROWS
-  // this context's index (same device pointers, never freed by the sibling) ----
-  bool borrowed_index = false;
+  // ---- pipelined entry (kslam_align_batch_async): worker lanes, each a sibling context that shares this context's index ----
   bool holds_hook = false;       // this context counts towards the page-locked column allocator being installed
   struct AsyncJob {
     uint64_t ticket = 0;
@@ -210,7 +220,7 @@ void pinned_free(void *p, size_t bytes);
 void *pinned_get(kslam_ctx *c, size_t bytes);
 bool pinned_put(kslam_ctx *c, void *p);
 bool scoring_in_envelope(const kslam_params &p);
-// a sibling context sees the primary's index through the same device pointers
+// a sibling context shares the primary's index and pairing settings
 void share_index(kslam_ctx *dst, const kslam_ctx *src);
 
 // ---- api_index.hip

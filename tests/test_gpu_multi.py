@@ -475,6 +475,41 @@ def test_rccl_behind_the_c_abi_world_1(kslam, synth, pseudo):
     c.close()
 
 
+def test_sibling_keeps_its_index_across_set_index_of_the_primary(kslam, synth):
+    """A sibling aligns against the index its primary had when it was created (include/kslam.h: kslam_create_sibling).
+    A later kslam_set_index of the primary, to a smaller database and then to a larger one, leaves the sibling's results
+    and build statistics as they were; the primary and a new sibling align against the new index."""
+    n_pairs = 1200
+    rb, gb = _data(synth, 930, n_pairs)
+    db_a, db_b = gb, gb[:-2]                         # B: a strict subset of A's entries
+    c = kslam.Context()
+    c.set_index(db_a)
+    s = c.sibling()
+    r_a = s.align_batch(rb)
+    st_a = s.index_build_stats()
+
+    def same(x, y):
+        return x[0].tobytes() == y[0].tobytes() and x[1].tobytes() == y[1].tobytes()
+
+    c.set_index(db_b)
+    assert same(s.align_batch(rb), r_a)
+    assert s.index_build_stats() == st_a
+    ref_b = kslam.Context()
+    ref_b.set_index(db_b)
+    r_b = ref_b.align_batch(rb)
+    ref_b.close()
+    assert len(r_a[0]) > n_pairs and r_b[0].tobytes() != r_a[0].tobytes()
+    s2 = c.sibling()
+    assert same(c.align_batch(rb), r_b) and same(s2.align_batch(rb), r_b)
+    s2.close()
+    rng = np.random.default_rng(931)
+    c.set_index(db_a + [bytes(synth.random_bases(rng, 40000))])     # larger than A
+    assert same(s.align_batch(rb), r_a)
+    assert s.index_build_stats() == st_a
+    s.close()
+    c.close()
+
+
 def _fake_rccl():
     """tests/fake_rccl/libfake_rccl.so (a stand-in for the RCCL entry points comm.cpp resolves: files in /dev/shm as the
     transport), built on first use"""
