@@ -19,9 +19,11 @@ resident in HBM (what `value` was in rounds 1-2), with the `roofline` objects at
                                The line carries the N = 1 point of this workload measured in the same run
                                (`n1_same_workload`).  Without a launcher (WORLD_SIZE unset) bench.py starts the ranks itself.
 
-The N = 1 line's legs: the hot path + its verification, the e2e leg (`value`), `cpu_baseline` (the reference's own
-alignToDatabase compiled in place, timed on the host cores; oracle/ is used by this leg only) and `strong_n1` (the N > 1
-lines' workload on this one GPU).  More evidence on request: --legs abi_path,other_sink,null_sink,pseudo | all.
+A plain N = 1 run does what its `value` needs and nothing else: the inputs, the timed hot path (`hot_path`, `roofline`), the
+e2e leg (`value`), --dump-outputs, the line.  --full adds the evidence beside it: the hot path's truth check
+(`hot_path.verified`), `cpu_baseline` (the reference's own alignToDatabase compiled in place, timed on the host cores;
+oracle/ is used by this leg only) and `strong_n1` (the N > 1 lines' workload on this one GPU).  The --strong and --gpus N > 1
+lines check their merged batch in every run.  More evidence on request: --legs abi_path,other_sink,null_sink,pseudo | all.
 The legs themselves: bench_legs.py.  --dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy, so that two
 builds can be compared output for output (the inputs are seeded: the same arguments give the same inputs).
 
@@ -335,16 +337,19 @@ def main():
     ap.add_argument("--viral", type=int, default=-1, help="viral genomes appended to the database (default: 10000 for config 2, else 0)")
     ap.add_argument("--repeats", action="store_true",
                     help="repeat-rich database: an rRNA-like 1.5 kb segment x5 in every genome, an insertion element in a third of them")
+    ap.add_argument("--full", action="store_true",
+                    help="also the evidence beside `value` that a plain run leaves out: the hot path's truth check "
+                         "(hot_path.verified), cpu_baseline and strong_n1 (about a minute and a half at configs[1])")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-pairs", type=int, default=300000)
     ap.add_argument("--cpu-genomes", type=int, default=25)
-    ap.add_argument("--cpu-full", action="store_true", help="cpu_baseline on the WHOLE workload of this run (minutes to hours of CPU time)")
+    ap.add_argument("--cpu-full", action="store_true", help="with --full: cpu_baseline on the WHOLE workload of this run (minutes to hours of CPU time)")
     ap.add_argument("--cpu-baseline", choices=["auto", "full", "sample"], default="auto",
-                    help="auto: the whole configs[1] workload on the hot path's own batch when the box has >= 16 usable CPUs and the "
+                    help="with --full; auto: the whole configs[1] workload on the hot path's own batch when the box has >= 16 usable CPUs and the "
                          "memory (about 30 s), else the bounded sample (--cpu-pairs / --cpu-genomes)")
     ap.add_argument("--no-cigar", action="store_true")
-    ap.add_argument("--legs", default="", help="optional evidence legs of the N = 1 line, comma-separated or `all` (none by default: the "
-                    "driver's run is the contract legs -- hot path, e2e `value`, cpu_baseline, strong_n1): abi_path (host pointers in / host "
+    ap.add_argument("--legs", default="", help="optional evidence legs of the N = 1 line, comma-separated or `all` (none by default: a "
+                    "plain run is the hot path and the e2e `value`, --full adds cpu_baseline and strong_n1): abi_path (host pointers in / host "
                     "results out), other_sink (the e2e leg on the directory --out-dir auto did not choose), null_sink (SAM text to "
                     "/dev/null), pseudo (the e2e leg with the reference's default, pseudo-assembly on)")
     ap.add_argument("--no-abi-path", action="store_true", help=argparse.SUPPRESS)     # rounds 2-5 spelling: the leg is opt-in now
@@ -362,7 +367,7 @@ def main():
                          "what a C++ host links: librccl opened by the library, no PyTorch in the transfers); torch = torch.distributed "
                          "(k-slam_amd/dist.py, the same protocol); auto = kslam when its communicator comes up on every rank, else torch")
     ap.add_argument("--strong-n1", choices=["auto", "off"], default="auto",
-                    help="N = 1, configs[1]: after the line's own legs, also time the workload of the --gpus N > 1 lines (ONE batch of "
+                    help="N = 1, configs[1], with --full: after the line's own legs, also time the workload of the --gpus N > 1 lines (ONE batch of "
                          "--total-pairs pairs per step) on this one GPU, in this process, and attach it as `strong_n1`: the origin of the "
                          "strong-scaling curve.  Every --gpus N > 1 line measures the same thing itself (`n1_same_workload`)")
     ap.add_argument("--strong-reference", choices=["auto", "on", "off"], default=None, help=argparse.SUPPRESS)   # round 5 spelling of --strong-n1
@@ -666,19 +671,22 @@ def main():
 
     # ---- outside the timed region: is what was just timed RIGHT?  (no oracle here: the generator's
     # own ground truth, the reference's structural expectations of src/Tests.h:161-264, :321-330) ----
+    # A plain N = 1 line leaves this to --full; the --strong and multi-rank lines always check.
     def device_results():
         n_out, n_cig = ctx.align_resident()
         ov = torch.empty(n_out * 48, dtype=torch.uint8, device=dev)
         cg = torch.empty(max(n_cig, 1) * 4, dtype=torch.uint8, device=dev)
         ctx.copy_results_device(ov.data_ptr(), cg.data_ptr())
         return ov, cg[:n_cig * 4].view(torch.int32)
-    ov_a, cg_a = device_results()
-    verified = W.check_against_truth(ov_a, None if args.no_cigar else cg_a, truth, read_len)
-    ov_b, cg_b = device_results()
-    verified["run_to_run_identical"] = bool(ov_a.numel() == ov_b.numel() and torch.equal(ov_a, ov_b)
-                                            and torch.equal(cg_a, cg_b))
-    verified["ok"] = bool(verified["ok"] and verified["run_to_run_identical"])
-    ranks_seen = 1
+    check = args.full or strong or use_dist
+    verified, ranks_seen = None, 1
+    if check:
+        ov_a, cg_a = device_results()
+        verified = W.check_against_truth(ov_a, None if args.no_cigar else cg_a, truth, read_len)
+        ov_b, cg_b = device_results()
+        verified["run_to_run_identical"] = bool(ov_a.numel() == ov_b.numel() and torch.equal(ov_a, ov_b)
+                                                and torch.equal(cg_a, cg_b))
+        verified["ok"] = bool(verified["ok"] and verified["run_to_run_identical"])
     if use_dist:   # every rank checked its own shard: sum the counts, AND the verdicts
         keys = [k for k, v in verified.items() if not isinstance(v, bool)]
         t = torch.tensor([verified[k] for k in keys] + [int(verified["ok"]), int(verified["run_to_run_identical"]), 1],
@@ -715,7 +723,7 @@ def main():
             torch.equal(merged["cg"].view(torch.int32), cg_a))
         verified["ok"] = bool(verified["ok"] and verified["merged_equals_single_context"])
         verified["ok"] = bool(verified["ok"] and verified["merged_unsorted_neighbours"] == 0)
-    del ov_a, cg_a, ov_b, cg_b
+    ov_a = cg_a = ov_b = cg_b = None
 
     # ================= strong mode, second clock: through the batch-global tail to SAM text + per-read taxa on rank 0 =================
     classified = None
@@ -1168,8 +1176,9 @@ def main():
                        "genome_kmers": int(tm["n_genome_kmers"]), "overlaps_raw": int(tm["n_overlaps_raw"]),
                        "candidates": int(tm["n_overlaps"]), "cigar_ops": int(n_cig), "chunks": int(tm["n_chunks"])},
             "sw_gcups": round(tm["sw_cells"] / ((tm["ms_sw"]) * 1e-3) / 1e9, 1) if tm["ms_sw"] > 0 else 0.0,
-            "verified": verified,
         }
+        if verified is not None:
+            hot["verified"] = verified
         out = {
             "metric": "paired %dbp reads/sec classified (bit-exact SAM)" % read_len,
             "value": None, "unit": "reads/s",
@@ -1238,7 +1247,7 @@ def main():
         else:
             out["value_definition"] = "see e2e" if not args.no_e2e and not strong else "hot path only (--no-e2e): resident-input alignToDatabase"
         torch.cuda.empty_cache()       # what torch's allocator cached while generating the inputs goes back to the device
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the apples-to-apples baseline is the WHOLE workload on the batch the hot path timed: ~30 s on 16 CPUs for
             # configs[1] (profiles/r03i_bench_cpu_full.json).  Taken by default when the box can afford it, else the sample.
             import oracle as O
@@ -1326,7 +1335,7 @@ def main():
         # (configs[3]); this line's `value` is configs[1] (1 M-pair batches, FASTQ text in, files out).  The same strong step runs
         # here on this one GPU, in this process (no child, nothing exec'ed), with this context's index.  Should the leg take the
         # process down, the line as it stands is written by the handlers installed in emit_on_exit().
-        if world == 1 and not strong and config == 1 and args.strong_n1 == "auto" and not args.no_e2e and not args.no_cigar:
+        if args.full and world == 1 and not strong and config == 1 and args.strong_n1 == "auto" and not args.no_e2e and not args.no_cigar:
             n1_pairs = args.total_pairs if pairs == 1_000_000 else max(PIECES, min(args.total_pairs, 8 * pairs) // PIECES * PIECES)
             out["scaling_curve_origin"] = ("strong_n1.value: the workload of the --gpus N > 1 lines (ONE batch of %d pairs per step) on this one "
                                            "GPU; `value` itself is configs[1] and is NOT the N = 1 point of their curve.  Every N > 1 line also "

@@ -376,14 +376,15 @@ def test_sharded_tail_equals_one_context(kslam, synth, bounds, pseudo):
 
 def test_default_bench_line_keeps_the_contract(tmp_path):
     """`python bench.py` (N = 1, the driver's command) at a small size: ONE JSON line on stdout and nothing else, the
-    contract's fields, `roofline` + `cpu_baseline` + `hot_path.verified`, and the end-to-end legs behind `value` (the
-    native batch loop: files written, repetitions identical, the sink probe)."""
+    contract's fields, `roofline` and the end-to-end legs behind `value` (the native batch loop: files written, repetitions
+    identical, the sink probe).  --full adds `cpu_baseline`, `hot_path.verified` and `strong_n1`; the plain run leaves them
+    out and computes the same: its --dump-outputs files are the --full run's byte for byte."""
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--pairs", "30000", "--species", "4", "--strains", "3",
             "--genome-len", "300000", "--steps", "3", "--warmup", "1", "--cpu-pairs", "3000", "--cpu-genomes", "4"]
-    r = subprocess.run(base + ["--dump-outputs", str(tmp_path / "dump")], env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run(base + ["--full", "--dump-outputs", str(tmp_path / "dump")], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     out = r.stdout.strip().splitlines()
     assert len(out) == 1 and out[0].startswith("{"), r.stdout[:500]
@@ -419,6 +420,25 @@ def test_default_bench_line_keeps_the_contract(tmp_path):
     assert "error" not in n1, n1
     assert n1["value"] > 0 and n1["hot_path_reads_per_s"] > 0 and n1["pseudo_assembly_on"] == "gpu" and n1["sam_file_bytes"] > 0
     assert line["scaling_curve_origin"].startswith("strong_n1.value")
+    # ---- the plain run: what `value` needs and nothing else, the same outputs
+    r = subprocess.run(base + ["--dump-outputs", str(tmp_path / "plain")], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    out = r.stdout.strip().splitlines()
+    assert len(out) == 1 and out[0].startswith("{"), r.stdout[:500]
+    plain = json.loads(out[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "roofline"):
+        assert k in plain, k
+    for k in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "scaling", "dtype", "data", "config"):
+        assert plain[k] == line[k], k
+    assert plain["value"] == plain["e2e"]["reads_per_s"] and plain["e2e"]["verified"] == e["verified"]
+    assert plain["hot_path"]["counts"] == hp["counts"] and plain["roofline"]["bound"] == "hbm"
+    for k in ("cpu_baseline", "strong_n1", "e2e_sam_to_dev_null", "e2e_with_pseudo_assembly", "abi_path", "e2e_other_sink"):
+        assert k not in plain, k
+    assert "verified" not in plain["hot_path"] and plain["scaling_curve_origin"] is None
+    assert sorted(os.listdir(tmp_path / "plain")) == sorted(os.listdir(tmp_path / "dump"))
+    for f in os.listdir(tmp_path / "dump"):
+        assert (tmp_path / "plain" / f).read_bytes() == (tmp_path / "dump" / f).read_bytes(), f
     # ---- the same with every optional leg switched on
     r = subprocess.run(base + ["--legs", "all", "--strong-n1", "off", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]

@@ -5,7 +5,7 @@
 #   cp /tmp/r05src/k-slam_amd/libkslam_hip.so k-slam_amd/libkslam_hip_r05.so      (git-ignored; same C ABI, loaded through KSLAM_LIB)
 REPO="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"; cd /tmp && export TMPDIR=/tmp; cd "$REPO" || exit 1
 O=gpurun_out/r06; mkdir -p $O
-BA="--steps 10 --warmup 3 --no-cpu-baseline --no-full-pipeline"
+BA="--full --steps 10 --warmup 3 --no-cpu-baseline --no-full-pipeline"
 for i in 1 2 3; do
   for lib in r05 r06; do
     if [ $lib = r05 ]; then export KSLAM_LIB=$REPO/k-slam_amd/libkslam_hip_r05.so; else unset KSLAM_LIB; fi

@@ -2,7 +2,7 @@
 # round 6: the probe (k_join_fill) against the merge (k_join_merge, KSLAM_JOIN=merge): parity, kernel times, HBM counters
 REPO="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"; cd /tmp && export TMPDIR=/tmp; cd "$REPO" || exit 1
 O=gpurun_out/r06; mkdir -p $O
-BA="--steps 3 --warmup 1 --no-cpu-baseline --no-full-pipeline"
+BA="--full --steps 3 --warmup 1 --no-cpu-baseline --no-full-pipeline"
 KSLAM_JOIN=merge timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_scale.py -x -q > $O/join_merge_parity.log 2>&1; echo "merge parity rc=$?"; tail -3 $O/join_merge_parity.log
 for mode in probe merge; do
   for wl in c1 repeats c2; do
