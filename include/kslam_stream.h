@@ -21,6 +21,7 @@
  * kslam_taxreport_xml (include/kslam_taxonomy.h) give <out>_abbreviated and <out>.
  *
  * With kslam_set_sam_bgzf (kslam_bgzf.h) on for ctx, the SAM file is written as BGZF: the header, every batch, an EOF marker.
+ * With kslam_set_sam_bam (kslam_bam.h) on, it is written as BAM: kslam_bam_header's bytes and every batch's records, as BGZF.
  * Same library as kslam.h; needs a context with an index (kslam_set_index).  Single-end data (the reference's
  * isPaired == false branch: getSequencesFromFASTQFile, getDummyAlignmentPairsFromSingleEndReads, :198-206, :228-233):
  * tail.paired = 0, r2 = NULL, len2 = 0; "pairs" in the fields below then reads "reads".  k-slam_amd/stream.py is the same loop in Python with
@@ -59,7 +60,8 @@ typedef struct {
   uint64_t n_read_pairs_aligned;  /* read pairs with at least one alignment pair left = _PerRead lines */
   uint64_t n_alignment_pairs;
   uint64_t sam_bytes, per_read_bytes; /* sam_bytes: the batches' SAM text handed to the writer, without the header; with
-                                         kslam_set_sam_bgzf on, compressed bytes (the header member and EOF marker not counted) */
+                                         kslam_set_sam_bgzf or kslam_set_sam_bam on, compressed bytes (the header members and
+                                         EOF marker not counted) */
   uint32_t first_max_insert_size; /* the first batch's insert-size limit */
   uint32_t batches_pseudo_on_host; /* batches whose pseudo-assembly the device left to the host (an entry too large) */
   double seconds;                 /* the whole call */

@@ -178,7 +178,10 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
     }
     if (sam_planned) {
       sam_stage_mapq(sam);   // pow / log10 / ceil with the host's libm
-      const bool bgzf = primary->samtext.sam && primary->samtext.bgzf;   // (kslam_set_sam_bgzf) compressed before the copy
+      // (kslam_set_sam_bgzf) compressed before the copy; (kslam_set_sam_bam) BAM records, which are always compressed
+      const bool bam = primary->samtext.sam && primary->samtext.bam;
+      const bool bgzf = primary->samtext.sam && (primary->samtext.bgzf || bam);
+      sam.bam = bam;
       st = guarded(c, [&] {
         sam_stage_kernels(c, primary, sam, primary->samtext.sam, primary->samtext.per_read);
         if (bgzf) {
@@ -194,7 +197,7 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
         });
       if (st == KSLAM_OK)
         job->text_flags = (primary->samtext.sam ? (KSLAM_TEXT_PAIRS_SORTED | KSLAM_TEXT_SAM) : 0u) | (primary->samtext.per_read ? KSLAM_TEXT_PER_READ : 0u) |
-                          (bgzf ? KSLAM_TEXT_SAM_BGZF : 0u);
+                          (bgzf ? KSLAM_TEXT_SAM_BGZF : 0u) | (bam ? KSLAM_TEXT_SAM_BAM : 0u);
     }
     sam_stage_free(c, sam);
     t3 = now();

@@ -94,7 +94,17 @@ void sam_stage_kernels(kslam_ctx *c, const kslam_ctx *owner, SamStage &S, bool w
   S.text_bytes = S.pr_bytes = 0;
   if (want_sam) {
     if (S.n_vals) HIPCHK(hipMemcpyAsync(c->samw.mapq.p, S.h_mapq, S.n_vals, hipMemcpyHostToDevice, s));
-    sam_format(S.d_recs, S.d_groups, S.n_groups, S.in, owner->annot, S.P, c->samw, &S.text_bytes, s);
+    uint32_t bad_read = 0xFFFFFFFFu;
+    sam_format(S.d_recs, S.d_groups, S.n_groups, S.in, owner->annot, S.P, c->samw, &S.text_bytes, s, S.bam, &bad_read);
+    if (bad_read != 0xFFFFFFFFu) {   // BAM: an id longer than l_read_name can say; name it
+      uint64_t off[2];
+      read_back(off, S.in.ids_off + bad_read, sizeof off, s);
+      char id[256];
+      const uint64_t k = std::min<uint64_t>(off[1] - off[0], 200);
+      read_back(id, S.in.ids + off[0], k, s);
+      throw StatusError{KSLAM_ERR_ARG, "read id \"" + std::string(id, k) + (off[1] - off[0] > k ? "..." : "") +
+                                           "\" is longer than 254 bytes: a BAM record cannot hold it"};
+    }
   }
   if (want_per_read) {
     if (!owner->annot.up) throw StatusError{KSLAM_ERR_STATE, "the annotations hold no taxonomy tree"};
@@ -519,6 +529,36 @@ kslam_status kslam_get_sam_bgzf(kslam_ctx *c, int *on) {
   if (!c || !on) return KSLAM_ERR_ARG;
   *on = c->samtext.bgzf ? 1 : 0;
   return KSLAM_OK;
+}
+
+// ---- BAM (include/kslam_bam.h; samtext.hip: put_record) ----
+kslam_status kslam_set_sam_bam(kslam_ctx *c, int on) {
+  return guarded(c, [&] {
+    if (c->in_multi) throw StatusError{KSLAM_ERR_UNSUPPORTED, "BAM output is not available on the contexts of a kslam_multi"};
+    c->samtext.bam = on != 0;
+  });
+}
+
+kslam_status kslam_get_sam_bam(kslam_ctx *c, int *on) {
+  if (!c || !on) return KSLAM_ERR_ARG;
+  *on = c->samtext.bam ? 1 : 0;
+  return KSLAM_OK;
+}
+
+kslam_status kslam_sam_bam(kslam_ctx *c, int paired, uint32_t num_alignments, int sam_xa, char **bam, uint64_t *len) {
+  if (bam) *bam = nullptr;
+  if (len) *len = 0;
+  SamStage S;
+  const kslam_status st = guarded(c, [&] {
+    if (!bam || !len) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+    S.bam = true;
+    sam_stage_plan(c, c, paired, num_alignments, sam_xa, true, S);
+    sam_stage_mapq(S);
+    sam_stage_kernels(c, c, S, true, false);
+    sam_stage_fetch(c, S, true, false, bam, len, nullptr, nullptr, nullptr, nullptr);
+  });
+  if (c) sam_stage_free(c, S);
+  return st;
 }
 
 kslam_status kslam_take_pairs(kslam_ctx *c, kslam_read_pair **read_pairs, uint64_t *n_read_pairs, kslam_paired_overlap **pairs,

@@ -15,6 +15,7 @@
 #include "bgzf.h"
 #include "../../include/kslam_samtext.h"
 #include "../../include/kslam_bgzf.h"
+#include "../../include/kslam_bam.h"
 #include "../host/workers.hpp"
 #include <algorithm>
 #include <chrono>
@@ -109,7 +110,7 @@ struct kslam_ctx {
   std::vector<DevBuf> annot_bufs;
   bool have_annot = false;
   SamWork samw;
-  struct { bool sam = false, per_read = false, bgzf = false; uint32_t num_alignments = 10; int sam_xa = 0; } samtext;   // for the lanes
+  struct { bool sam = false, per_read = false, bgzf = false, bam = false; uint32_t num_alignments = 10; int sam_xa = 0; } samtext;   // for the lanes
   const uint8_t *d_ids = nullptr;       // read identifiers of the loaded batch (fqw.ids, or ids_buf)
   const uint64_t *d_ids_off = nullptr;
   DevBuf ids_buf, ids_off_buf;
@@ -250,6 +251,7 @@ struct SamStage {   // one batch's way through the stage
   const kslam_read_pair *d_groups = nullptr;
   uint64_t n_groups = 0, n_vals = 0, n_segs = 0, text_bytes = 0, pr_bytes = 0;
   const void *d_sam = nullptr;    // where sam_stage_fetch copies the SAM bytes from (nullptr: samw.text)
+  bool bam = false;               // BAM records instead of SAM lines (include/kslam_bam.h)
   double *h_vals = nullptr;       // pinned
   uint32_t *h_seg = nullptr;      // pinned
   uint8_t *h_mapq = nullptr;      // pinned

@@ -52,9 +52,12 @@ struct SamWork {
 // err_flags: bits of kslam_row_detail.flags met on a row that is reported (2) or whose probability matters (1).
 void sam_plan(kslam_paired_overlap *d_recs, const kslam_read_pair *d_groups, uint64_t n_groups, const SamInputs &in, const SamParams &P,
               SamWork &W, uint64_t *n_vals, uint64_t *n_segs, uint32_t *err_flags, hipStream_t s);
-// Second half, after W.mapq (u8, n_vals; same layout as W.vals) has been filled: the text into W.text.
+// Second half, after W.mapq (u8, n_vals; same layout as W.vals) has been filled: the text into W.text.  bam: BAM records
+// (include/kslam_bam.h) instead of SAM lines; when a read id is too long for one, *bad_read = the lowest such read,
+// *text_bytes = 0 and nothing is written (otherwise *bad_read = 0xFFFFFFFF).
 void sam_format(const kslam_paired_overlap *d_recs, const kslam_read_pair *d_groups, uint64_t n_groups, const SamInputs &in,
-                const SamAnnot &A, const SamParams &P, SamWork &W, uint64_t *text_bytes, hipStream_t s);
+                const SamAnnot &A, const SamParams &P, SamWork &W, uint64_t *text_bytes, hipStream_t s, bool bam = false,
+                uint32_t *bad_read = nullptr);
 // per-read LCA into W.tax_ids (u32 per read pair) and the <out>_PerRead lines into W.pr_text
 void per_read_device(const kslam_paired_overlap *d_recs, const kslam_read_pair *d_groups, uint64_t n_groups, const SamInputs &in,
                      const SamAnnot &A, SamWork &W, uint64_t *text_bytes, hipStream_t s);

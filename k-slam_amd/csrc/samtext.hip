@@ -302,6 +302,120 @@ __device__ inline void put_line(Sink &o, const SamInputs &in, const SamAnnot &A,
   o.ch('\n');
 }
 
+// ---- BAM (include/kslam_bam.h): put_line's fields as a binary record (host/tail.cpp: put_record, same bytes) ----------
+template <class Sink>
+__device__ inline void put_le(Sink &o, uint32_t v, uint32_t k) {
+  for (uint32_t i = 0; i < k; i++) o.ch((uint8_t)(v >> (8 * i)));
+}
+// an integer tag at htslib's smallest width (sam_parse1: C / S / I; the values here are never negative)
+template <class Sink>
+__device__ inline void tag_int(Sink &o, char t0, char t1, uint32_t v) {
+  o.ch((uint8_t)t0);
+  o.ch((uint8_t)t1);
+  if (v <= 255) {
+    o.ch('C');
+    put_le(o, v, 1);
+  } else if (v <= 65535) {
+    o.ch('S');
+    put_le(o, v, 2);
+  } else {
+    o.ch('I');
+    put_le(o, v, 4);
+  }
+}
+// htslib's hts_reg2bin(beg, end, 14, 5)
+__device__ inline uint32_t bam_reg2bin(int64_t beg, int64_t end) {
+  --end;
+  if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
+  if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
+  if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
+  if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
+  if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
+  return 0;
+}
+// everything after block_size
+template <class Sink>
+__device__ inline void record_body(Sink &o, const SamInputs &in, const SamAnnot &A, const SamParams &P, const Row &r, uint32_t qname_read,
+                                   uint8_t mapq, uint32_t xo, int64_t gene, uint32_t xt) {
+  const kslam_overlap *ov = r.mapped ? &in.ov[r.ov] : nullptr;
+  const bool cigar = P.report_cigar && r.mapped && in.pool && ov->cigar_len;   // put_line's CIGAR text is not empty
+  int64_t clip_tail = 0;
+  uint32_t n_ops = 0, span = 0;
+  if (cigar) {
+    clip_tail = (int64_t)(in.read_off[ov->read + 1] - in.read_off[ov->read]) - ov->query_end - 1;
+    n_ops = ov->cigar_len + (ov->query_begin > 0) + (clip_tail > 0);
+    for (uint32_t k = 0; k < ov->cigar_len; k++) {
+      const uint32_t c = in.pool[ov->cigar_off + k];
+      if ((c & 15) == 0 || (c & 15) == 2) span += c >> 4;
+    }
+  }
+  const uint64_t id_len = in.ids_off[qname_read + 1] - in.ids_off[qname_read];
+  const int32_t pos = (int32_t)r.pos - 1;
+  const int64_t end = (int64_t)pos + ((r.flag & 0x4) || !n_ops ? 1 : max(1u, span));
+  put_le(o, r.rname_entry, 4);                          // refID
+  put_le(o, (uint32_t)pos, 4);
+  put_le(o, (uint32_t)id_len + 1, 1);                   // l_read_name
+  put_le(o, mapq, 1);
+  put_le(o, bam_reg2bin(pos, end), 2);
+  put_le(o, n_ops, 2);
+  put_le(o, r.flag, 2);
+  put_le(o, 0, 4);                                      // l_seq: SEQ and QUAL are "*"
+  put_le(o, P.paired ? r.rname_entry : 0xFFFFFFFFu, 4);  // next_refID: "=" / "*"
+  put_le(o, (uint32_t)((int32_t)r.pnext - 1), 4);
+  put_le(o, (uint32_t)r.tlen, 4);
+  o.bytes(in.ids + in.ids_off[qname_read], id_len);
+  o.ch(0);
+  if (cigar) {   // the ops put_line prints: the clips from query_begin / query_end, M I D from the pool
+    if (ov->query_begin > 0) put_le(o, (uint32_t)ov->query_begin << 4 | 4u, 4);
+    for (uint32_t k = 0; k < ov->cigar_len; k++) put_le(o, in.pool[ov->cigar_off + k], 4);
+    if (clip_tail > 0) put_le(o, (uint32_t)clip_tail << 4 | 4u, 4);
+  }
+  if (r.mapped) {
+    uint32_t nm = 0;
+    if (P.report_cigar) {
+      LIT(o, "MDZ");
+      if (walked(in, r.ov)) {
+        const kslam_row_detail &d = in.det[r.ov];
+        o.bytes(in.md_pool + d.md_off, d.md_len);
+        nm = d.nm;
+      }
+      o.ch(0);
+    }
+    tag_int(o, 'A', 'S', r.as);
+    tag_int(o, 'X', 'S', r.xs);
+    tag_int(o, 'N', 'M', nm);
+    tag_int(o, 'X', '0', xo);
+    if (xt != 0) tag_int(o, 'X', 'T', xt);
+    if (gene >= 0) {
+      if (A.gname_off[gene + 1] > A.gname_off[gene]) {
+        LIT(o, "XGZ");
+        o.bytes(A.gname + A.gname_off[gene], A.gname_off[gene + 1] - A.gname_off[gene]);
+        o.ch(0);
+      }
+      if (A.prot_off[gene + 1] > A.prot_off[gene]) {
+        LIT(o, "XPZ");
+        o.bytes(A.prot + A.prot_off[gene], A.prot_off[gene + 1] - A.prot_off[gene]);
+        o.ch(0);
+      }
+      if (A.prod_off[gene + 1] > A.prod_off[gene]) {
+        LIT(o, "XRZ\"");
+        o.bytes(A.prod + A.prod_off[gene], A.prod_off[gene + 1] - A.prod_off[gene]);
+        o.ch('"');
+        o.ch(0);
+      }
+    }
+  }
+}
+// block_size first: the record's own length from a count of it alone, then the record
+template <class Sink>
+__device__ inline void put_record(Sink &o, const SamInputs &in, const SamAnnot &A, const SamParams &P, const Row &r, uint32_t qname_read,
+                                  uint8_t mapq, uint32_t xo, int64_t gene, uint32_t xt) {
+  CountSink n;
+  record_body(n, in, A, P, r, qname_read, mapq, xo, gene, xt);
+  put_le(o, (uint32_t)n.n, 4);
+  record_body(o, in, A, P, r, qname_read, mapq, xo, gene, xt);
+}
+
 // ---- plan: the reference's per-pair sort, the rows to report, which mates need libm ----------------------------------
 __global__ __launch_bounds__(256) void k_sam_plan(Rec *__restrict__ recs, const kslam_read_pair *__restrict__ groups, uint64_t n_groups,
                                                   SamInputs in, SamParams P, SamPlan *__restrict__ plan, uint32_t *__restrict__ n_vals,
@@ -373,7 +487,7 @@ __global__ __launch_bounds__(256) void k_sam_collect(const Rec *__restrict__ rec
 }
 
 // the text of one read pair's lines (host/tail.cpp: write_group from the mapping qualities on)
-template <class Sink>
+template <bool BAM, class Sink>
 __device__ inline void write_group(Sink &o, const Rec *v, const kslam_read_pair &grp, const SamPlan pl, const SamInputs &in, const SamAnnot &A,
                                    const SamParams &P, const uint8_t *mapq_vals, uint64_t val_at) {
   const uint32_t n_rows = pl.n_rows, use1 = pl.use1, use2 = pl.use2;
@@ -392,16 +506,24 @@ __device__ inline void write_group(Sink &o, const Rec *v, const kslam_read_pair 
     const uint8_t q2 = b.mapped ? (need2 ? mapq_vals[at2 + k] : (uint8_t)P.mapq_unique) : 0;
     const int64_t gene = best_gene(A, p.entry, p.ref_start, p.ref_end);
     const uint32_t xt = A.tax[p.entry];
-    put_line(o, in, A, P, a, grp.r1_read, q1, use1, gene, xt);
-    if (P.paired) put_line(o, in, A, P, b, grp.r2_read, q2, use2, gene, xt);
+    if (BAM) {
+      put_record(o, in, A, P, a, grp.r1_read, q1, use1, gene, xt);
+      if (P.paired) put_record(o, in, A, P, b, grp.r2_read, q2, use2, gene, xt);
+    } else {
+      put_line(o, in, A, P, a, grp.r1_read, q1, use1, gene, xt);
+      if (P.paired) put_line(o, in, A, P, b, grp.r2_read, q2, use2, gene, xt);
+    }
     if (P.sam_xa) break;
   }
 }
 
+// BAM: bad_read (initially 0xFFFFFFFF) = the lowest read whose id a record cannot hold (> 254 bytes); nothing is written then
+template <bool BAM>
 __global__ __launch_bounds__(256) void k_sam_lengths(const Rec *__restrict__ recs, const kslam_read_pair *__restrict__ groups,
                                                      uint64_t n_groups, SamInputs in, SamAnnot A, SamParams P,
                                                      const SamPlan *__restrict__ plan, const uint64_t *__restrict__ val_off,
-                                                     const uint8_t *__restrict__ mapq_vals, uint32_t *__restrict__ text_len) {
+                                                     const uint8_t *__restrict__ mapq_vals, uint32_t *__restrict__ text_len,
+                                                     uint32_t *__restrict__ bad_read) {
   const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= n_groups) return;
   const SamPlan pl = plan[g];
@@ -409,10 +531,16 @@ __global__ __launch_bounds__(256) void k_sam_lengths(const Rec *__restrict__ rec
     text_len[g] = 0;
     return;
   }
+  if (BAM) {
+    const uint32_t r1 = groups[g].r1_read, r2 = groups[g].r2_read;
+    if (in.ids_off[r1 + 1] - in.ids_off[r1] > 254) atomicMin(bad_read, r1);
+    if (P.paired && in.ids_off[r2 + 1] - in.ids_off[r2] > 254) atomicMin(bad_read, r2);
+  }
   CountSink o;
-  write_group(o, recs + groups[g].first, groups[g], pl, in, A, P, mapq_vals, val_off[g]);
+  write_group<BAM>(o, recs + groups[g].first, groups[g], pl, in, A, P, mapq_vals, val_off[g]);
   text_len[g] = (uint32_t)o.n;
 }
+template <bool BAM>
 __global__ __launch_bounds__(256) void k_sam_write(const Rec *__restrict__ recs, const kslam_read_pair *__restrict__ groups,
                                                    uint64_t n_groups, SamInputs in, SamAnnot A, SamParams P,
                                                    const SamPlan *__restrict__ plan, const uint64_t *__restrict__ val_off,
@@ -423,7 +551,7 @@ __global__ __launch_bounds__(256) void k_sam_write(const Rec *__restrict__ recs,
   const SamPlan pl = plan[g];
   if (!pl.n_rows) return;
   ByteSink o(text + text_off[g]);
-  write_group(o, recs + groups[g].first, groups[g], pl, in, A, P, mapq_vals, val_off[g]);
+  write_group<BAM>(o, recs + groups[g].first, groups[g], pl, in, A, P, mapq_vals, val_off[g]);
   o.flush();
 }
 
@@ -529,21 +657,39 @@ void sam_plan(kslam_paired_overlap *d_recs, const kslam_read_pair *d_groups, uin
 }
 
 void sam_format(const kslam_paired_overlap *d_recs, const kslam_read_pair *d_groups, uint64_t n_groups, const SamInputs &in,
-                const SamAnnot &A, const SamParams &P, SamWork &W, uint64_t *text_bytes, hipStream_t s) {
+                const SamAnnot &A, const SamParams &P, SamWork &W, uint64_t *text_bytes, hipStream_t s, bool bam, uint32_t *bad_read) {
   *text_bytes = 0;
+  if (bad_read) *bad_read = 0xFFFFFFFFu;
   if (!n_groups) return;
   W.text_len.ensure(n_groups * 4);
   W.text_off.ensure((n_groups + 1) * 8);
-  hipLaunchKernelGGL(k_sam_lengths, dim3(blocks_for(n_groups)), dim3(256), 0, s, d_recs, d_groups, n_groups, in, A, P, W.plan.as<SamPlan>(),
-                     W.val_off.as<uint64_t>(), W.mapq.as<uint8_t>(), W.text_len.as<uint32_t>());
+  uint32_t *d_bad = W.totals.as<uint32_t>() + 10;   // (u64 slot 5)
+  if (bam) {
+    HIPCHK(hipMemsetAsync(d_bad, 0xFF, 4, s));
+    hipLaunchKernelGGL(k_sam_lengths<true>, dim3(blocks_for(n_groups)), dim3(256), 0, s, d_recs, d_groups, n_groups, in, A, P,
+                       W.plan.as<SamPlan>(), W.val_off.as<uint64_t>(), W.mapq.as<uint8_t>(), W.text_len.as<uint32_t>(), d_bad);
+  } else {
+    hipLaunchKernelGGL(k_sam_lengths<false>, dim3(blocks_for(n_groups)), dim3(256), 0, s, d_recs, d_groups, n_groups, in, A, P,
+                       W.plan.as<SamPlan>(), W.val_off.as<uint64_t>(), W.mapq.as<uint8_t>(), W.text_len.as<uint32_t>(), d_bad);
+  }
   HIPCHK(hipGetLastError());
   exclusive_scan_u32_to_u64(W.text_len.as<uint32_t>(), W.text_off.as<uint64_t>(), n_groups, W.totals.as<uint64_t>() + 2, W.scan_tmp.p, s);
-  uint64_t total = 0;
-  read_back(&total, W.totals.as<uint64_t>() + 2, sizeof total, s);
+  uint64_t t[4];   // u64 slots 2 .. 5: the total, (3, 4: other stages), the BAM refusal
+  read_back(t, W.totals.as<uint64_t>() + 2, sizeof t, s);
+  const uint64_t total = t[0];
+  if (bam && (uint32_t)t[3] != 0xFFFFFFFFu) {
+    if (bad_read) *bad_read = (uint32_t)t[3];
+    return;   // nothing written
+  }
   W.text.ensure(total + 64);
-  if (total)
-    hipLaunchKernelGGL(k_sam_write, dim3(blocks_for(n_groups)), dim3(256), 0, s, d_recs, d_groups, n_groups, in, A, P, W.plan.as<SamPlan>(),
-                       W.val_off.as<uint64_t>(), W.mapq.as<uint8_t>(), W.text_off.as<uint64_t>(), W.text.as<uint8_t>());
+  if (total) {
+    if (bam)
+      hipLaunchKernelGGL(k_sam_write<true>, dim3(blocks_for(n_groups)), dim3(256), 0, s, d_recs, d_groups, n_groups, in, A, P,
+                         W.plan.as<SamPlan>(), W.val_off.as<uint64_t>(), W.mapq.as<uint8_t>(), W.text_off.as<uint64_t>(), W.text.as<uint8_t>());
+    else
+      hipLaunchKernelGGL(k_sam_write<false>, dim3(blocks_for(n_groups)), dim3(256), 0, s, d_recs, d_groups, n_groups, in, A, P,
+                         W.plan.as<SamPlan>(), W.val_off.as<uint64_t>(), W.mapq.as<uint8_t>(), W.text_off.as<uint64_t>(), W.text.as<uint8_t>());
+  }
   HIPCHK(hipGetLastError());
   *text_bytes = total;
 }

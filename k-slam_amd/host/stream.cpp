@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <string>
 #include <thread>
 #include <unistd.h>
@@ -21,6 +22,7 @@
 #include "../../include/kslam_stream.h"
 #include "../../include/kslam_samtext.h"
 #include "../../include/kslam_bgzf.h"
+#include "../../include/kslam_bam.h"
 #include "workers.hpp"
 
 namespace {
@@ -109,8 +111,10 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     }
     // BGZF (include/kslam_bgzf.h): every SAM byte goes to the writer compressed -- the lanes compress what they format, the
     // header and any host-formatted batch go through kslam_bgzf_compress here; the EOF marker ends the file
-    int bgzf = 0;
-    if (kslam_get_sam_bgzf(ctx, &bgzf) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    int bgzf = 0, bam = 0;
+    if (kslam_get_sam_bgzf(ctx, &bgzf) != KSLAM_OK || kslam_get_sam_bam(ctx, &bam) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    // BAM (include/kslam_bam.h): the same file framing, with kslam_bam_header's bytes and BAM records inside the members
+    if (bam) bgzf = 1;
     static const auto give_back = [](void *user, void *data) { kslam_free_pinned(static_cast<kslam_ctx *>(user), data); };
     auto enqueue_compressed = [&](const char *text, uint64_t len) -> uint64_t {
       char *z = nullptr;
@@ -121,7 +125,14 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     };
     if (P->sam_fd >= 0) {
       if (kslam_sam_writer_open(P->sam_fd, &writer) != KSLAM_OK) fail(KSLAM_ERR_ARG, "could not start the SAM writer");
-      if (bgzf && P->sam_header && P->sam_header_len)
+      if (bam) {
+        char *h = nullptr;
+        uint64_t hlen = 0;
+        if (kslam_bam_header(index, P->sam_header, P->sam_header ? P->sam_header_len : 0, &h, &hlen) != KSLAM_OK)
+          fail(KSLAM_ERR_ARG, kslam_tail_last_error());
+        std::unique_ptr<char, decltype(&free)> own(h, &free);
+        enqueue_compressed(h, hlen);
+      } else if (bgzf && P->sam_header && P->sam_header_len)
         enqueue_compressed(P->sam_header, P->sam_header_len);
       else if (P->sam_header && P->sam_header_len && kslam_write_queued(writer, P->sam_header, P->sam_header_len) != 0)
         fail(KSLAM_ERR_ARG, "writing the SAM header failed");
@@ -238,6 +249,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         s = guarded([&] {   // written on the GPU: the page-locked block joins the writer's queue as it is and goes back to the
                             // context's pool once it is in the file
           const double t0 = now_ms();
+          if (bam && !(res.text_flags & KSLAM_TEXT_SAM_BAM))   // (a batch formatted before the switch went on: text, not records)
+            fail(KSLAM_ERR_STATE, "kslam_set_sam_bam was switched on while a batch was in flight");
           if (bgzf && !(res.text_flags & KSLAM_TEXT_SAM_BGZF)) {   // (the switch went on after the batch was formatted)
             st.sam_bytes += enqueue_compressed(res.sam_text, res.sam_text_len);
           } else {
@@ -261,10 +274,11 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
             static_cast<std::string *>(user)->append(data, len);
             return 0;
           };
-          const kslam_status a = kslam_tail_finish_write_rows(&host_sorted, &reads, index, res.overlaps, res.n_overlaps, res.cigar_pool,
-                                                              res.n_cigar, res.details, res.md_pool, res.n_md, res.read_pairs,
-                                                              res.n_read_pairs, res.pairs, res.n_pairs, bgzf ? append : kslam_write_queued,
-                                                              bgzf ? (void *)&text : (void *)writer, &ts);
+          // BAM: the same stage writing records (kslam_tail_finish_write_rows_bam), gathered and compressed the same way
+          const kslam_status a = (bam ? kslam_tail_finish_write_rows_bam : kslam_tail_finish_write_rows)(
+              &host_sorted, &reads, index, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, res.details, res.md_pool, res.n_md,
+              res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs, bgzf ? append : kslam_write_queued,
+              bgzf ? (void *)&text : (void *)writer, &ts);
           if (a != KSLAM_OK) fail(a, kslam_tail_last_error());
           st.sam_bytes += bgzf ? enqueue_compressed(text.data(), text.size()) : ts.sam_bytes;
           st.seconds_sam_text += (now_ms() - t0) * 1e-3;

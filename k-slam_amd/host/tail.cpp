@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../../include/kslam_tail.h"
+#include "../../include/kslam_bam.h"
 #include <cerrno>
 #include <unistd.h>
 #include <fcntl.h>
@@ -831,6 +832,7 @@ struct SamInput {
   const char *md_pool = nullptr;
   uint64_t n_md = 0;
   bool groups_sorted = false;  // KSLAM_TAIL_GROUPS_SORTED: writeSAMOutputPairs' per-pair sort already done
+  bool bam = false;            // BAM records (put_record) instead of SAM lines (include/kslam_bam.h)
 };
 
 struct Row {  // SAMEntry, src/SAM.h:238-277, text fields as slices of the task's scratch
@@ -1298,6 +1300,136 @@ void put_line(const SamInput &in, Text &out, const Text &scratch, const Row &r, 
   out.n = (size_t)(o.w - out.p);
 }
 
+// ---- BAM (include/kslam_bam.h): the line above as a binary record (SAMv1 section 4.2; csrc/samtext.hip: put_record) ----
+// htslib's hts_reg2bin(beg, end, 14, 5)
+inline uint16_t bam_reg2bin(int64_t beg, int64_t end) {
+  --end;
+  if (beg >> 14 == end >> 14) return (uint16_t)(((1 << 15) - 1) / 7 + (beg >> 14));
+  if (beg >> 17 == end >> 17) return (uint16_t)(((1 << 12) - 1) / 7 + (beg >> 17));
+  if (beg >> 20 == end >> 20) return (uint16_t)(((1 << 9) - 1) / 7 + (beg >> 20));
+  if (beg >> 23 == end >> 23) return (uint16_t)(((1 << 6) - 1) / 7 + (beg >> 23));
+  if (beg >> 26 == end >> 26) return (uint16_t)(((1 << 3) - 1) / 7 + (beg >> 26));
+  return 0;
+}
+
+struct RecordWriter {
+  char *w;
+  explicit RecordWriter(char *at) : w(at) {}
+  void bytes(const char *s, size_t k) {
+    memcpy(w, s, k);
+    w += k;
+  }
+  void u8(uint32_t v) { *w++ = (char)v; }
+  void u16(uint32_t v) {
+    const uint16_t x = (uint16_t)v;
+    memcpy(w, &x, 2);
+    w += 2;
+  }
+  void u32(uint32_t v) {
+    memcpy(w, &v, 4);
+    w += 4;
+  }
+  // an integer tag at htslib's smallest width (sam_parse1: C / S / I, c / s / i for negative values)
+  void tag_int(const char *tag, int64_t v) {
+    bytes(tag, 2);
+    if (v >= 0) {
+      if (v <= 255) { u8('C'); u8((uint32_t)v); }
+      else if (v <= 65535) { u8('S'); u16((uint32_t)v); }
+      else { u8('I'); u32((uint32_t)v); }
+    } else {
+      if (v >= -128) { u8('c'); u8((uint32_t)v); }
+      else if (v >= -32768) { u8('s'); u16((uint32_t)v); }
+      else { u8('i'); u32((uint32_t)v); }
+    }
+  }
+  void tag_z(const char *tag, const char *s, size_t k) {
+    bytes(tag, 2);
+    u8('Z');
+    bytes(s, k);
+    u8(0);
+  }
+};
+
+[[noreturn]] void long_read_id(const char *id, size_t k) {
+  fail(KSLAM_ERR_ARG, "read id \"" + std::string(id, k) + "\" is longer than 254 bytes: a BAM record cannot hold it");
+}
+
+// put_line's fields as a BAM record, from the same Row; the CIGAR ops are read back from the text put_line would print
+void put_record(const SamInput &in, Text &out, const Text &scratch, const Row &r, uint32_t qname_read,
+                int64_t gene, uint32_t xt, bool paired) {
+  const kslam_index_view *ix = in.index;
+  const kslam_reads_view *rd = in.reads;
+  const char *id = rd->ids + rd->ids_off[qname_read];
+  const size_t id_len = rd->ids_off[qname_read + 1] - rd->ids_off[qname_read];
+  if (id_len > 254) long_read_id(id, id_len);
+  const bool cigar = in.p->report_cigar && !r.cigar_star;
+  size_t bound = id_len + 4 * r.cigar_len + r.md_len + 256;
+  if (gene >= 0)
+    bound += (ix->gene_name_off[gene + 1] - ix->gene_name_off[gene]) + (ix->protein_id_off[gene + 1] - ix->protein_id_off[gene]) +
+             (ix->product_off[gene + 1] - ix->product_off[gene]);
+  char *const start = out.need(bound);
+  RecordWriter o(start + 4);   // block_size goes in last
+  // the CIGAR text -> ops (digits, then M I D S), with the reference span (M and D)
+  const char *ct = scratch.p + r.cigar_at;
+  uint32_t n_ops = 0, span = 0;
+  char *const ops_at = start + 36 + id_len + 1;
+  if (cigar) {
+    uint32_t len = 0;
+    for (size_t i = 0; i < r.cigar_len; i++) {
+      const char c = ct[i];
+      if (c >= '0' && c <= '9') {
+        len = len * 10 + (uint32_t)(c - '0');
+        continue;
+      }
+      const uint32_t op = c == 'M' ? 0 : c == 'I' ? 1 : c == 'D' ? 2 : 4;
+      if (op == 0 || op == 2) span += len;
+      const uint32_t word = len << 4 | op;
+      memcpy(ops_at + 4 * n_ops, &word, 4);
+      n_ops++;
+      len = 0;
+    }
+  }
+  if (n_ops > 65535) fail(KSLAM_ERR_ARG, "more than 65535 CIGAR operations: a BAM record cannot hold them");
+  const int32_t pos = (int32_t)r.pos - 1;
+  const int64_t end = (int64_t)pos + ((r.flag & 0x4) || !n_ops ? 1 : std::max<uint32_t>(1, span));
+  o.u32(r.rname_entry);                                 // refID
+  o.u32((uint32_t)pos);                                 // pos
+  o.u8((uint32_t)id_len + 1);                           // l_read_name
+  o.u8(r.mapq);
+  o.u16(bam_reg2bin(pos, end));
+  o.u16(n_ops);
+  o.u16(r.flag);
+  o.u32(0);                                             // l_seq: SEQ and QUAL are "*"
+  o.u32(paired ? r.rname_entry : 0xFFFFFFFFu);          // next_refID: "=" / "*"
+  o.u32((uint32_t)((int32_t)r.pnext - 1));              // next_pos
+  o.u32((uint32_t)r.tlen);
+  o.bytes(id, id_len);
+  o.u8(0);
+  o.w += 4 * (size_t)n_ops;                             // (written above)
+  if (r.mapped) {
+    if (in.p->report_cigar) o.tag_z("MD", scratch.p + r.md_at, r.md_len);
+    o.tag_int("AS", r.as);
+    o.tag_int("XS", r.xs);
+    o.tag_int("NM", r.nm);
+    o.tag_int("X0", r.xo);
+    if (xt != 0) o.tag_int("XT", xt);
+    if (gene >= 0) {
+      if (ix->gene_name_off[gene + 1] > ix->gene_name_off[gene])
+        o.tag_z("XG", ix->gene_name + ix->gene_name_off[gene], ix->gene_name_off[gene + 1] - ix->gene_name_off[gene]);
+      if (ix->protein_id_off[gene + 1] > ix->protein_id_off[gene])
+        o.tag_z("XP", ix->protein_id + ix->protein_id_off[gene], ix->protein_id_off[gene + 1] - ix->protein_id_off[gene]);
+      if (ix->product_off[gene + 1] > ix->product_off[gene]) {
+        o.bytes("XRZ\"", 4);
+        o.bytes(ix->product + ix->product_off[gene], ix->product_off[gene + 1] - ix->product_off[gene]);
+        o.bytes("\"", 2);   // the closing quote and the NUL
+      }
+    }
+  }
+  const uint32_t block_size = (uint32_t)(o.w - start - 4);
+  memcpy(start, &block_size, 4);
+  out.n = (size_t)(o.w - out.p);
+}
+
 // writeSAMOutputPairs (src/SAM.h:443-512) with getSAMFromPair (src/SAM.h:352-433)
 void write_group(const SamInput &in, const Group &g, Rec *recs, Text &out, Text &scratch,
                  std::vector<Row> &rows, std::vector<int64_t> &genes) {
@@ -1421,8 +1553,13 @@ void write_group(const SamInput &in, const Group &g, Rec *recs, Text &out, Text 
     a.mapq = mapq_of(a.prob, sum1);
     b.mapq = mapq_of(b.prob, sum2);
     const uint32_t xt = in.index->taxonomy_id[recs[k].entry];
-    put_line(in, out, scratch, a, g.r1_read, genes[k], xt, paired);
-    if (paired) put_line(in, out, scratch, b, g.r2_read, genes[k], xt, paired);
+    if (in.bam) {
+      put_record(in, out, scratch, a, g.r1_read, genes[k], xt, paired);
+      if (paired) put_record(in, out, scratch, b, g.r2_read, genes[k], xt, paired);
+    } else {
+      put_line(in, out, scratch, a, g.r1_read, genes[k], xt, paired);
+      if (paired) put_line(in, out, scratch, b, g.r2_read, genes[k], xt, paired);
+    }
     if (in.p->sam_xa) break;
   }
 }
@@ -1642,7 +1779,7 @@ void tail_to_sam(const kslam_tail_params *params, const kslam_reads_view *reads,
                  const kslam_index_view *index, const kslam_overlap *overlaps, uint64_t n_overlaps,
                  const uint32_t *cigar_pool, uint64_t n_cigar, const SamSink &sink,
                  kslam_tail_stats *stats, const kslam_row_detail *det = nullptr, const char *md_pool = nullptr,
-                 uint64_t n_md = 0) {
+                 uint64_t n_md = 0, bool bam = false) {
   Input in = make_input(params, reads, overlaps, n_overlaps);
   Arena &A = arena();
   std::lock_guard<std::mutex> one(A.call);
@@ -1651,6 +1788,7 @@ void tail_to_sam(const kslam_tail_params *params, const kslam_reads_view *reads,
   memset(&st, 0, sizeof st);
   run_tail(in, A, ts, st);
   SamInput si{params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar};
+  si.bam = bam;
   if (det && cigar_pool) {
     if (!md_pool && n_md) fail(KSLAM_ERR_ARG, "null MD pool");
     si.det = det;
@@ -1841,13 +1979,13 @@ kslam_status kslam_tail_finish_prepare(const kslam_tail_params *params, const ks
   });
 }
 
-kslam_status kslam_tail_finish_write_rows(const kslam_tail_params *params, const kslam_reads_view *reads,
-                                          const kslam_index_view *index, const kslam_overlap *overlaps,
-                                          uint64_t n_overlaps, const uint32_t *cigar_pool, uint64_t n_cigar,
-                                          const kslam_row_detail *details, const char *md_pool, uint64_t n_md,
-                                          kslam_read_pair *read_pairs, uint64_t n_read_pairs,
-                                          kslam_paired_overlap *pairs, uint64_t n_pairs, kslam_write_fn write,
-                                          void *user, kslam_tail_stats *stats) {
+// kslam_tail_finish_write_rows and its BAM twin (bam: put_record instead of put_line)
+static kslam_status finish_write_rows(bool bam, const kslam_tail_params *params, const kslam_reads_view *reads,
+                                      const kslam_index_view *index, const kslam_overlap *overlaps, uint64_t n_overlaps,
+                                      const uint32_t *cigar_pool, uint64_t n_cigar, const kslam_row_detail *details,
+                                      const char *md_pool, uint64_t n_md, kslam_read_pair *read_pairs, uint64_t n_read_pairs,
+                                      kslam_paired_overlap *pairs, uint64_t n_pairs, kslam_write_fn write, void *user,
+                                      kslam_tail_stats *stats) {
   return guarded([&] {
     if (!write) fail(KSLAM_ERR_ARG, "null writer");
     if ((!read_pairs && n_read_pairs) || (!pairs && n_pairs)) fail(KSLAM_ERR_ARG, "null argument");
@@ -1881,6 +2019,7 @@ kslam_status kslam_tail_finish_write_rows(const kslam_tail_params *params, const
     st.threads = in.threads;
     SamInput si{params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar};
     si.groups_sorted = (params->stages & KSLAM_TAIL_GROUPS_SORTED) != 0;
+    si.bam = bam;
     if (details && cigar_pool) {
       if (!md_pool && n_md) fail(KSLAM_ERR_ARG, "null MD pool");
       si.det = details;
@@ -1894,6 +2033,70 @@ kslam_status kslam_tail_finish_write_rows(const kslam_tail_params *params, const
     sam_stage(si, A, in.threads, ts.groups, ts.n_groups, ts.recs, sink, &st.sam_bytes);
     st.ms_sam = now_ms() - t1;
     if (stats) *stats = st;
+  });
+}
+
+kslam_status kslam_tail_finish_write_rows(const kslam_tail_params *params, const kslam_reads_view *reads,
+                                          const kslam_index_view *index, const kslam_overlap *overlaps,
+                                          uint64_t n_overlaps, const uint32_t *cigar_pool, uint64_t n_cigar,
+                                          const kslam_row_detail *details, const char *md_pool, uint64_t n_md,
+                                          kslam_read_pair *read_pairs, uint64_t n_read_pairs,
+                                          kslam_paired_overlap *pairs, uint64_t n_pairs, kslam_write_fn write,
+                                          void *user, kslam_tail_stats *stats) {
+  return finish_write_rows(false, params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar, details, md_pool, n_md, read_pairs,
+                           n_read_pairs, pairs, n_pairs, write, user, stats);
+}
+
+// ---- BAM (include/kslam_bam.h): the same stage with put_record ----
+kslam_status kslam_tail_finish_write_rows_bam(const kslam_tail_params *params, const kslam_reads_view *reads,
+                                              const kslam_index_view *index, const kslam_overlap *overlaps, uint64_t n_overlaps,
+                                              const uint32_t *cigar_pool, uint64_t n_cigar, const kslam_row_detail *details,
+                                              const char *md_pool, uint64_t n_md, kslam_read_pair *read_pairs,
+                                              uint64_t n_read_pairs, kslam_paired_overlap *pairs, uint64_t n_pairs,
+                                              kslam_write_fn write, void *user, kslam_tail_stats *stats) {
+  return finish_write_rows(true, params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar, details, md_pool, n_md, read_pairs,
+                           n_read_pairs, pairs, n_pairs, write, user, stats);
+}
+
+kslam_status kslam_tail_sam_bam(const kslam_tail_params *params, const kslam_reads_view *reads, const kslam_index_view *index,
+                                const kslam_overlap *overlaps, uint64_t n_overlaps, const uint32_t *cigar_pool, uint64_t n_cigar,
+                                char **bam, uint64_t *len, kslam_tail_stats *stats) {
+  return guarded([&] {
+    if (!bam || !len) fail(KSLAM_ERR_ARG, "null output argument");
+    SamSink sink;
+    sink.text = bam;
+    sink.text_len = len;
+    tail_to_sam(params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar, sink, stats, nullptr, nullptr, 0, true);
+  });
+}
+
+kslam_status kslam_bam_header(const kslam_index_view *index, const char *sam_header, uint64_t len, char **out, uint64_t *out_len) {
+  return guarded([&] {
+    if (!index || !out || !out_len || !index->bases_off || !index->locus_tag_off || (len && !sam_header))
+      fail(KSLAM_ERR_ARG, "null argument");
+    if (len > INT32_MAX || index->n_entries > INT32_MAX) fail(KSLAM_ERR_ARG, "the header text or the reference list is too long for BAM");
+    Text h;
+    auto i32 = [&](uint64_t v) {
+      const uint32_t x = (uint32_t)v;
+      h.put((const char *)&x, 4);
+    };
+    h.put("BAM\1", 4);
+    i32(len);
+    if (len) h.put(sam_header, (size_t)len);
+    i32(index->n_entries);
+    for (uint64_t e = 0; e < index->n_entries; e++) {
+      const uint64_t k = index->locus_tag_off[e + 1] - index->locus_tag_off[e];
+      i32(k + 1);
+      put_col(h, index->locus_tag, index->locus_tag_off, e);
+      h.put('\0');
+      i32(index->bases_off[e + 1] - index->bases_off[e]);
+    }
+    char *buf = (char *)malloc(h.n + 1);
+    if (!buf) fail(KSLAM_ERR_OOM, "out of host memory");
+    memcpy(buf, h.p, h.n);
+    buf[h.n] = 0;
+    *out = buf;
+    *out_len = h.n;
   });
 }
 

@@ -28,6 +28,7 @@
 #include <unistd.h>
 #include <vector>
 
+#include "../include/kslam_bam.h"
 #include "../include/kslam_bgzf.h"
 #include "../include/kslam_db.h"
 #include "../include/kslam_stream.h"
@@ -66,7 +67,8 @@ struct Options {
   uint32_t score_threshold = 0, match = 2, mismatch = 3, gap_open = 5, gap_extend = 2;
   uint32_t num_reads = UINT32_MAX, num_reads_at_once = 10000000, num_alignments = 10;
   double score_fraction = 0.95;
-  bool sam_xa = false, just_align = false, no_pseudo = false, help = false, version = false, parse_fasta = false, sam_bgzf = false;
+  bool sam_xa = false, just_align = false, no_pseudo = false, help = false, version = false, parse_fasta = false, sam_bgzf = false,
+       sam_bam = false;
   int device = 0;
   std::vector<std::string> inputs;
 };
@@ -104,13 +106,14 @@ void usage(FILE *o) {
         "  --just-align                          only perform alignments, not metagenomics\n"
         "  --no-pseudo-assembly                  do not link alignments together\n"
         "  --sam-bgzf                            write --sam-file as BGZF (blocked gzip, as bgzip writes it)\n"
+        "  --sam-bam                             write --sam-file as BAM (implies --sam-bgzf)\n"
         "\n", o);
 }
 
 Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
-         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF };
+         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -125,6 +128,7 @@ Options parse(int argc, char **argv) {
       {"server", no_argument, nullptr, UNSUPPORTED}, {"alignment-only", no_argument, nullptr, IGNORED},   // declared, never read (src/main.cpp:80-82)
       {"device", required_argument, nullptr, DEVICE},   // not in the reference: the HIP device ordinal (default 0)
       {"sam-bgzf", no_argument, nullptr, SAM_BGZF},     // not in the reference: the SAM file as BGZF (include/kslam_bgzf.h)
+      {"sam-bam", no_argument, nullptr, SAM_BAM},       // not in the reference: the SAM file as BAM (include/kslam_bam.h)
       {nullptr, 0, nullptr, 0}};
   opterr = 0;
   int c;
@@ -152,6 +156,7 @@ Options parse(int argc, char **argv) {
       case NALIGN: o.num_alignments = to_u32(optarg, "num-alignments"); break;
       case XA: o.sam_xa = true; break;
       case SAM_BGZF: o.sam_bgzf = true; break;
+      case SAM_BAM: o.sam_bam = true; break;
       case VERSION: o.version = true; break;
       case JUST: o.just_align = true; break;
       case NOPSEUDO: o.no_pseudo = true; break;
@@ -327,6 +332,7 @@ int run(const Options &o, const std::string &command_line) {
   kslam_ctx *ctx = nullptr;
   if (kslam_create(&kp, &ctx) != KSLAM_OK) die(std::string("GPU context: ") + (ctx ? kslam_last_error(ctx) : "kslam_create failed"));
   if (o.sam_bgzf && want_sam && kslam_set_sam_bgzf(ctx, 1) != KSLAM_OK) die(std::string("BGZF: ") + kslam_last_error(ctx));
+  if (o.sam_bam && want_sam && kslam_set_sam_bam(ctx, 1) != KSLAM_OK) die(std::string("BAM: ") + kslam_last_error(ctx));
   logl("Getting k-mers from index");
   if (kslam_set_index(ctx, index->n_entries, kslam_db_entry_bases(db), kslam_db_entry_lengths(db)) != KSLAM_OK)
     die(std::string("index: ") + kslam_last_error(ctx));
@@ -390,7 +396,7 @@ int run(const Options &o, const std::string &command_line) {
   }
   uint64_t sam_file_bytes = st.sam_bytes + header_len;
   struct stat sam_stat;
-  if (sam_fd >= 0 && o.sam_bgzf && fstat(sam_fd, &sam_stat) == 0) sam_file_bytes = (uint64_t)sam_stat.st_size;   // compressed
+  if (sam_fd >= 0 && (o.sam_bgzf || o.sam_bam) && fstat(sam_fd, &sam_stat) == 0) sam_file_bytes = (uint64_t)sam_stat.st_size;   // compressed
   if (sam_fd >= 0) close(sam_fd);
   if (per_read_fd >= 0) close(per_read_fd);
   logl(cat("Found ", st.n_overlaps, " k-mer overlaps"));
