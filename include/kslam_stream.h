@@ -22,6 +22,7 @@
  *
  * With kslam_set_sam_bgzf (kslam_bgzf.h) on for ctx, the SAM file is written as BGZF: the header, every batch, an EOF marker.
  * With kslam_set_sam_bam (kslam_bam.h) on, it is written as BAM: kslam_bam_header's bytes and every batch's records, as BGZF.
+ * With kslam_set_sam_seq (kslam_samseq.h) on, the rows without flag 0x100 carry SEQ and QUAL, in any of the three forms.
  * Same library as kslam.h; needs a context with an index (kslam_set_index).  Single-end data (the reference's
  * isPaired == false branch: getSequencesFromFASTQFile, getDummyAlignmentPairsFromSingleEndReads, :198-206, :228-233):
  * tail.paired = 0, r2 = NULL, len2 = 0; "pairs" in the fields below then reads "reads".  k-slam_amd/stream.py is the same loop in Python with

@@ -95,7 +95,16 @@ void sam_stage_kernels(kslam_ctx *c, const kslam_ctx *owner, SamStage &S, bool w
   if (want_sam) {
     if (S.n_vals) HIPCHK(hipMemcpyAsync(c->samw.mapq.p, S.h_mapq, S.n_vals, hipMemcpyHostToDevice, s));
     uint32_t bad_read = 0xFFFFFFFFu;
-    sam_format(S.d_recs, S.d_groups, S.n_groups, S.in, owner->annot, S.P, c->samw, &S.text_bytes, s, S.bam, &bad_read);
+    // SEQ / QUAL come from the gathered columns: every way a batch is loaded leaves r_bases (and, with qualities, r_qual)
+    // resident, the FASTQ-text lanes included (details.hip: gather_fields), so both record kinds and all routes read them
+    SamSeq sq;
+    if (S.seq) {
+      if (!c->have_reads) throw StatusError{KSLAM_ERR_STATE, "no resident read batch to take SEQ and QUAL from"};
+      sq.bases = c->r_bases.as<uint8_t>();
+      sq.qual = c->have_qual ? c->r_qual.as<uint8_t>() : nullptr;
+    }
+    sam_format(S.d_recs, S.d_groups, S.n_groups, S.in, owner->annot, S.P, c->samw, &S.text_bytes, s, S.bam, &bad_read,
+               S.seq ? &sq : nullptr);
     if (bad_read != 0xFFFFFFFFu) {   // BAM: an id longer than l_read_name can say; name it
       uint64_t off[2];
       read_back(off, S.in.ids_off + bad_read, sizeof off, s);
@@ -482,6 +491,7 @@ kslam_status kslam_sam_text(kslam_ctx *c, int paired, uint32_t num_alignments, i
   const kslam_status st = guarded(c, [&] {
     if (sam_text && !sam_len) throw StatusError{KSLAM_ERR_ARG, "sam_text without sam_len"};
     if ((per_read_text && !per_read_len) || (tax_ids && !n_tax_ids)) throw StatusError{KSLAM_ERR_ARG, "an output without its length"};
+    S.seq = c->samtext.seq;
     sam_stage_plan(c, c, paired, num_alignments, sam_xa, sam_text != nullptr, S);
     sam_stage_mapq(S);
     const bool want_sam = sam_text != nullptr, want_pr = per_read_text != nullptr || tax_ids != nullptr;
@@ -545,6 +555,20 @@ kslam_status kslam_get_sam_bam(kslam_ctx *c, int *on) {
   return KSLAM_OK;
 }
 
+// ---- SEQ / QUAL (include/kslam_samseq.h; samtext.hip: put_seq_text / put_seq_bam) ----
+kslam_status kslam_set_sam_seq(kslam_ctx *c, int on) {
+  return guarded(c, [&] {
+    if (c->in_multi) throw StatusError{KSLAM_ERR_UNSUPPORTED, "SEQ and QUAL are not available on the contexts of a kslam_multi"};
+    c->samtext.seq = on != 0;
+  });
+}
+
+kslam_status kslam_get_sam_seq(kslam_ctx *c, int *on) {
+  if (!c || !on) return KSLAM_ERR_ARG;
+  *on = c->samtext.seq ? 1 : 0;
+  return KSLAM_OK;
+}
+
 kslam_status kslam_sam_bam(kslam_ctx *c, int paired, uint32_t num_alignments, int sam_xa, char **bam, uint64_t *len) {
   if (bam) *bam = nullptr;
   if (len) *len = 0;
@@ -552,6 +576,7 @@ kslam_status kslam_sam_bam(kslam_ctx *c, int paired, uint32_t num_alignments, in
   const kslam_status st = guarded(c, [&] {
     if (!bam || !len) throw StatusError{KSLAM_ERR_ARG, "null argument"};
     S.bam = true;
+    S.seq = c->samtext.seq;
     sam_stage_plan(c, c, paired, num_alignments, sam_xa, true, S);
     sam_stage_mapq(S);
     sam_stage_kernels(c, c, S, true, false);

@@ -16,6 +16,7 @@
 #include "../../include/kslam_samtext.h"
 #include "../../include/kslam_bgzf.h"
 #include "../../include/kslam_bam.h"
+#include "../../include/kslam_samseq.h"
 #include "../host/workers.hpp"
 #include <algorithm>
 #include <chrono>
@@ -110,7 +111,7 @@ struct kslam_ctx {
   std::vector<DevBuf> annot_bufs;
   bool have_annot = false;
   SamWork samw;
-  struct { bool sam = false, per_read = false, bgzf = false, bam = false; uint32_t num_alignments = 10; int sam_xa = 0; } samtext;   // for the lanes
+  struct { bool sam = false, per_read = false, bgzf = false, bam = false, seq = false; uint32_t num_alignments = 10; int sam_xa = 0; } samtext;   // for the lanes
   const uint8_t *d_ids = nullptr;       // read identifiers of the loaded batch (fqw.ids, or ids_buf)
   const uint64_t *d_ids_off = nullptr;
   DevBuf ids_buf, ids_off_buf;
@@ -252,6 +253,7 @@ struct SamStage {   // one batch's way through the stage
   uint64_t n_groups = 0, n_vals = 0, n_segs = 0, text_bytes = 0, pr_bytes = 0;
   const void *d_sam = nullptr;    // where sam_stage_fetch copies the SAM bytes from (nullptr: samw.text)
   bool bam = false;               // BAM records instead of SAM lines (include/kslam_bam.h)
+  bool seq = false;               // SEQ and QUAL on the rows without flag 0x100 (include/kslam_samseq.h)
   double *h_vals = nullptr;       // pinned
   uint32_t *h_seg = nullptr;      // pinned
   uint8_t *h_mapq = nullptr;      // pinned

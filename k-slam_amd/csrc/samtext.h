@@ -31,6 +31,11 @@ struct SamInputs {   // one batch, all device pointers
   const uint64_t *read_off = nullptr;        // base offsets = read lengths
 };
 
+struct SamSeq {   // the batch's bases and qualities for SEQ / QUAL (include/kslam_samseq.h), laid out by SamInputs.read_off
+  const uint8_t *bases = nullptr;
+  const uint8_t *qual = nullptr;             // nullptr: the batch was loaded without qualities
+};
+
 struct SamParams {
   uint32_t num_alignments = 10;   // --num-alignments
   int32_t paired = 1, sam_xa = 0, report_cigar = 1;
@@ -54,10 +59,11 @@ void sam_plan(kslam_paired_overlap *d_recs, const kslam_read_pair *d_groups, uin
               SamWork &W, uint64_t *n_vals, uint64_t *n_segs, uint32_t *err_flags, hipStream_t s);
 // Second half, after W.mapq (u8, n_vals; same layout as W.vals) has been filled: the text into W.text.  bam: BAM records
 // (include/kslam_bam.h) instead of SAM lines; when a read id is too long for one, *bad_read = the lowest such read,
-// *text_bytes = 0 and nothing is written (otherwise *bad_read = 0xFFFFFFFF).
+// *text_bytes = 0 and nothing is written (otherwise *bad_read = 0xFFFFFFFF).  seq: not nullptr = the rows without flag
+// 0x100 carry SEQ and QUAL from these columns (their own kernel instantiations; nullptr runs the ones without).
 void sam_format(const kslam_paired_overlap *d_recs, const kslam_read_pair *d_groups, uint64_t n_groups, const SamInputs &in,
                 const SamAnnot &A, const SamParams &P, SamWork &W, uint64_t *text_bytes, hipStream_t s, bool bam = false,
-                uint32_t *bad_read = nullptr);
+                uint32_t *bad_read = nullptr, const SamSeq *seq = nullptr);
 // per-read LCA into W.tax_ids (u32 per read pair) and the <out>_PerRead lines into W.pr_text
 void per_read_device(const kslam_paired_overlap *d_recs, const kslam_read_pair *d_groups, uint64_t n_groups, const SamInputs &in,
                      const SamAnnot &A, SamWork &W, uint64_t *text_bytes, hipStream_t s);

@@ -30,6 +30,7 @@
 #include "common.h"
 #include "gnu_sort.h"
 #include "samtext.h"
+#include "seqcodes.h"
 
 namespace kslam {
 
@@ -70,6 +71,13 @@ struct ByteSink {
   }
   __device__ void lit(const char *s, uint32_t n) {
     for (uint32_t i = 0; i < n; i++) ch((uint8_t)s[i]);
+  }
+  // eight bytes at once (v's low byte first): one store whatever k is; the bytes that do not fit wait in acc
+  __device__ void word(uint64_t v) {
+    const uint64_t out = acc | (v << (8 * k));
+    __builtin_memcpy(w, &out, 8);
+    w += 8;
+    acc = k ? v >> (64 - 8 * k) : 0;
   }
   __device__ void flush() {
     for (uint32_t i = 0; i < k; i++) w[i] = (uint8_t)(acc >> (8 * i));
@@ -220,10 +228,148 @@ __device__ inline bool walked(const SamInputs &in, uint32_t row) { return in.poo
 __device__ inline double row_logp(const SamInputs &in, uint32_t row) { return walked(in, row) ? in.det[row].logp : 0.0; }
 __device__ inline uint32_t row_flags(const SamInputs &in, uint32_t row) { return walked(in, row) ? in.det[row].flags : 0u; }
 
-// SAMEntry::getEntry, src/SAM.h:278-305 (host/tail.cpp: put_line)
+// ---- SEQ / QUAL (include/kslam_samseq.h; host/tail.cpp: put_seq_text / put_seq_bam, same bytes) ------------------------
+// The three byte tables of the switch-on kernels, in LDS: filled by the block's threads before anything else.
+struct SeqLut {
+  uint8_t comp[256];    // kslam_seq::complement
+  uint8_t code[256];    // kslam_seq::nibble
+  uint8_t rcode[256];   // nibble(complement(c)): a reverse row's code straight from the read's byte
+};
+__device__ inline void fill_lut(SeqLut &t) {
+  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) {   // (one trip with the 256-thread blocks of this file)
+    const uint8_t c = kslam_seq::complement((uint8_t)i);
+    t.comp[i] = c;
+    t.code[i] = kslam_seq::nibble((uint8_t)i);
+    t.rcode[i] = kslam_seq::nibble(c);
+  }
+}
+// the block's tables, filled and behind a barrier; nothing, and no LDS, for the switch-off kernels
+template <bool SEQ>
+__device__ inline const SeqLut *block_lut() {
+  if constexpr (SEQ) {
+    __shared__ SeqLut t;
+    fill_lut(t);
+    __syncthreads();
+    return &t;
+  } else {
+    return nullptr;
+  }
+}
+struct SeqCols {   // where a row's two columns come from; lut is nullptr in the count pass
+  const uint8_t *bases = nullptr, *qual = nullptr;   // the read's, qual nullptr: the batch has no qualities
+  uint32_t len = 0;
+  bool rev = false;     // FLAG 0x10
+  const SeqLut *lut = nullptr;
+};
+__device__ inline uint64_t load8(const uint8_t *p) {
+  uint64_t v;
+  __builtin_memcpy(&v, p, 8);
+  return v;
+}
+__device__ inline uint64_t map8(uint64_t v, const uint8_t *t) {
+  uint64_t r = 0;
+#pragma unroll
+  for (uint32_t b = 0; b < 8; b++) r |= (uint64_t)t[(v >> (8 * b)) & 0xFF] << (8 * b);
+  return r;
+}
+// sixteen bases (a = the first eight in output order, low byte first) -> eight bytes, high nibble first
+__device__ inline uint64_t pack16(uint64_t a, uint64_t b, const uint8_t *code) {
+  uint64_t r = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 4; j++) {
+    r |= (uint64_t)(code[(a >> (16 * j)) & 0xFF] << 4 | code[(a >> (16 * j + 8)) & 0xFF]) << (8 * j);
+    r |= (uint64_t)(code[(b >> (16 * j)) & 0xFF] << 4 | code[(b >> (16 * j + 8)) & 0xFF]) << (8 * j + 32);
+  }
+  return r;
+}
+// s[0 .. n) forward, or from the end; t: a table every byte goes through (nullptr: none)
+__device__ inline void copy_bytes(ByteSink &o, const uint8_t *s, uint32_t n, bool rev, const uint8_t *t) {
+  const uint32_t nw = n >> 3, tail = n & 7;
+  if (!rev) {
+    for (uint32_t i = 0; i < nw; i++) o.word(load8(s + 8 * i));
+    for (uint32_t j = 0; j < tail; j++) o.ch(s[8 * nw + j]);
+  } else {
+    for (uint32_t i = 0; i < nw; i++) {
+      const uint64_t v = __builtin_bswap64(load8(s + n - 8 * (i + 1)));
+      o.word(t ? map8(v, t) : v);
+    }
+    for (uint32_t j = tail; j-- > 0;) o.ch(t ? t[s[j]] : s[j]);
+  }
+}
+// columns 10 and 11 of a line, without the tab in front
 template <class Sink>
+__device__ inline void put_seq_text(Sink &o, const SeqCols &c);
+template <>
+__device__ inline void put_seq_text<CountSink>(CountSink &o, const SeqCols &c) {
+  o.n += c.len ? (c.qual ? 2ull * c.len + 1 : c.len + 2ull) : 3;
+}
+template <>
+__device__ inline void put_seq_text<ByteSink>(ByteSink &o, const SeqCols &c) {
+  if (!c.len) {   // a read without bases
+    LIT(o, "*\t*");
+    return;
+  }
+  copy_bytes(o, c.bases, c.len, c.rev, c.lut->comp);
+  o.ch('\t');
+  if (c.qual) copy_bytes(o, c.qual, c.len, c.rev, nullptr); else o.ch('*');
+}
+// seq and qual of a record
+template <class Sink>
+__device__ inline void put_seq_bam(Sink &o, const SeqCols &c);
+template <>
+__device__ inline void put_seq_bam<CountSink>(CountSink &o, const SeqCols &c) { o.n += (c.len + 1) / 2 + (uint64_t)c.len; }
+template <>
+__device__ inline void put_seq_bam<ByteSink>(ByteSink &o, const SeqCols &c) {
+  const uint32_t n = c.len, n16 = n >> 4;
+  const uint8_t *s = c.bases, *code = c.rev ? c.lut->rcode : c.lut->code;
+  for (uint32_t i = 0; i < n16; i++) {
+    uint64_t a, b;
+    if (!c.rev) {
+      a = load8(s + 16 * i);
+      b = load8(s + 16 * i + 8);
+    } else {
+      a = __builtin_bswap64(load8(s + n - 16 * i - 8));
+      b = __builtin_bswap64(load8(s + n - 16 * i - 16));
+    }
+    o.word(pack16(a, b, code));
+  }
+  for (uint32_t j = 16 * n16; j < n; j += 2) {   // the last nibble of an odd length is 0
+    const uint32_t hi = code[c.rev ? s[n - 1 - j] : s[j]];
+    const uint32_t lo = j + 1 < n ? code[c.rev ? s[n - 2 - j] : s[j + 1]] : 0u;
+    o.ch((uint8_t)(hi << 4 | lo));
+  }
+  const uint32_t nw = n >> 3;
+  if (!c.qual) {   // no qualities: 0xFF
+    for (uint32_t i = 0; i < nw; i++) o.word(~0ull);
+    for (uint32_t j = 8 * nw; j < n; j++) o.ch(0xFF);
+    return;
+  }
+  // quality - 33 on eight bytes, borrows kept inside each byte
+  const uint64_t H = 0x8080808080808080ull, Y = 0x2121212121212121ull;
+  for (uint32_t i = 0; i < nw; i++) {
+    const uint64_t x = c.rev ? __builtin_bswap64(load8(c.qual + n - 8 * (i + 1))) : load8(c.qual + 8 * i);
+    o.word(((x | H) - Y) ^ ((x ^ ~Y) & H));
+  }
+  for (uint32_t j = 8 * nw; j < n; j++) o.ch((uint8_t)((c.rev ? c.qual[n - 1 - j] : c.qual[j]) - 33));
+}
+// a row's columns: rows with 0x100 carry none (SEQ false: nobody asks)
+template <bool SEQ>
+__device__ inline SeqCols seq_cols(const SamSeq &sq, const SamInputs &in, const Row &r, uint32_t read, const SeqLut *lut) {
+  SeqCols c;
+  if (!SEQ) return c;
+  const uint64_t at = in.read_off[read];
+  c.len = (uint32_t)(in.read_off[read + 1] - at);
+  c.bases = sq.bases + at;
+  c.qual = sq.qual ? sq.qual + at : nullptr;
+  c.rev = (r.flag & 0x10) != 0;
+  c.lut = lut;
+  return c;
+}
+
+// SAMEntry::getEntry, src/SAM.h:278-305 (host/tail.cpp: put_line)
+template <bool SEQ, class Sink>
 __device__ inline void put_line(Sink &o, const SamInputs &in, const SamAnnot &A, const SamParams &P, const Row &r, uint32_t qname_read,
-                                uint8_t mapq, uint32_t xo, int64_t gene, uint32_t xt) {
+                                uint8_t mapq, uint32_t xo, int64_t gene, uint32_t xt, const SeqCols &sc) {
   o.bytes(in.ids + in.ids_off[qname_read], in.ids_off[qname_read + 1] - in.ids_off[qname_read]);
   o.ch('\t');
   put_num(o, r.flag);
@@ -260,7 +406,12 @@ __device__ inline void put_line(Sink &o, const SamInputs &in, const SamAnnot &A,
   put_num(o, r.pnext);
   o.ch('\t');
   put_snum(o, r.tlen);
-  LIT(o, "\t*\t*");
+  if (SEQ && !(r.flag & 0x100)) {
+    o.ch('\t');
+    put_seq_text(o, sc);
+  } else {
+    LIT(o, "\t*\t*");
+  }
   if (r.mapped) {
     uint32_t nm = 0;
     if (P.report_cigar) {
@@ -334,9 +485,9 @@ __device__ inline uint32_t bam_reg2bin(int64_t beg, int64_t end) {
   return 0;
 }
 // everything after block_size
-template <class Sink>
+template <bool SEQ, class Sink>
 __device__ inline void record_body(Sink &o, const SamInputs &in, const SamAnnot &A, const SamParams &P, const Row &r, uint32_t qname_read,
-                                   uint8_t mapq, uint32_t xo, int64_t gene, uint32_t xt) {
+                                   uint8_t mapq, uint32_t xo, int64_t gene, uint32_t xt, const SeqCols &sc) {
   const kslam_overlap *ov = r.mapped ? &in.ov[r.ov] : nullptr;
   const bool cigar = P.report_cigar && r.mapped && in.pool && ov->cigar_len;   // put_line's CIGAR text is not empty
   int64_t clip_tail = 0;
@@ -359,7 +510,8 @@ __device__ inline void record_body(Sink &o, const SamInputs &in, const SamAnnot 
   put_le(o, bam_reg2bin(pos, end), 2);
   put_le(o, n_ops, 2);
   put_le(o, r.flag, 2);
-  put_le(o, 0, 4);                                      // l_seq: SEQ and QUAL are "*"
+  const bool seq = SEQ && !(r.flag & 0x100);
+  put_le(o, seq ? sc.len : 0u, 4);                      // l_seq: 0 when SEQ and QUAL are "*"
   put_le(o, P.paired ? r.rname_entry : 0xFFFFFFFFu, 4);  // next_refID: "=" / "*"
   put_le(o, (uint32_t)((int32_t)r.pnext - 1), 4);
   put_le(o, (uint32_t)r.tlen, 4);
@@ -370,6 +522,7 @@ __device__ inline void record_body(Sink &o, const SamInputs &in, const SamAnnot 
     for (uint32_t k = 0; k < ov->cigar_len; k++) put_le(o, in.pool[ov->cigar_off + k], 4);
     if (clip_tail > 0) put_le(o, (uint32_t)clip_tail << 4 | 4u, 4);
   }
+  if (seq) put_seq_bam(o, sc);
   if (r.mapped) {
     uint32_t nm = 0;
     if (P.report_cigar) {
@@ -407,13 +560,13 @@ __device__ inline void record_body(Sink &o, const SamInputs &in, const SamAnnot 
   }
 }
 // block_size first: the record's own length from a count of it alone, then the record
-template <class Sink>
+template <bool SEQ, class Sink>
 __device__ inline void put_record(Sink &o, const SamInputs &in, const SamAnnot &A, const SamParams &P, const Row &r, uint32_t qname_read,
-                                  uint8_t mapq, uint32_t xo, int64_t gene, uint32_t xt) {
+                                  uint8_t mapq, uint32_t xo, int64_t gene, uint32_t xt, const SeqCols &sc) {
   CountSink n;
-  record_body(n, in, A, P, r, qname_read, mapq, xo, gene, xt);
+  record_body<SEQ>(n, in, A, P, r, qname_read, mapq, xo, gene, xt, sc);
   put_le(o, (uint32_t)n.n, 4);
-  record_body(o, in, A, P, r, qname_read, mapq, xo, gene, xt);
+  record_body<SEQ>(o, in, A, P, r, qname_read, mapq, xo, gene, xt, sc);
 }
 
 // ---- plan: the reference's per-pair sort, the rows to report, which mates need libm ----------------------------------
@@ -487,9 +640,9 @@ __global__ __launch_bounds__(256) void k_sam_collect(const Rec *__restrict__ rec
 }
 
 // the text of one read pair's lines (host/tail.cpp: write_group from the mapping qualities on)
-template <bool BAM, class Sink>
+template <bool BAM, bool SEQ, class Sink>
 __device__ inline void write_group(Sink &o, const Rec *v, const kslam_read_pair &grp, const SamPlan pl, const SamInputs &in, const SamAnnot &A,
-                                   const SamParams &P, const uint8_t *mapq_vals, uint64_t val_at) {
+                                   const SamParams &P, const uint8_t *mapq_vals, uint64_t val_at, const SamSeq &sq, const SeqLut *lut) {
   const uint32_t n_rows = pl.n_rows, use1 = pl.use1, use2 = pl.use2;
   const bool need1 = pl.need & 1u, need2 = pl.need & 2u;
   const uint64_t at1 = val_at, at2 = val_at + (need1 ? n_rows : 0);
@@ -507,23 +660,24 @@ __device__ inline void write_group(Sink &o, const Rec *v, const kslam_read_pair 
     const int64_t gene = best_gene(A, p.entry, p.ref_start, p.ref_end);
     const uint32_t xt = A.tax[p.entry];
     if (BAM) {
-      put_record(o, in, A, P, a, grp.r1_read, q1, use1, gene, xt);
-      if (P.paired) put_record(o, in, A, P, b, grp.r2_read, q2, use2, gene, xt);
+      put_record<SEQ>(o, in, A, P, a, grp.r1_read, q1, use1, gene, xt, seq_cols<SEQ>(sq, in, a, grp.r1_read, lut));
+      if (P.paired) put_record<SEQ>(o, in, A, P, b, grp.r2_read, q2, use2, gene, xt, seq_cols<SEQ>(sq, in, b, grp.r2_read, lut));
     } else {
-      put_line(o, in, A, P, a, grp.r1_read, q1, use1, gene, xt);
-      if (P.paired) put_line(o, in, A, P, b, grp.r2_read, q2, use2, gene, xt);
+      put_line<SEQ>(o, in, A, P, a, grp.r1_read, q1, use1, gene, xt, seq_cols<SEQ>(sq, in, a, grp.r1_read, lut));
+      if (P.paired) put_line<SEQ>(o, in, A, P, b, grp.r2_read, q2, use2, gene, xt, seq_cols<SEQ>(sq, in, b, grp.r2_read, lut));
     }
     if (P.sam_xa) break;
   }
 }
 
 // BAM: bad_read (initially 0xFFFFFFFF) = the lowest read whose id a record cannot hold (> 254 bytes); nothing is written then
-template <bool BAM>
+// SEQ: the rows without 0x100 carry SEQ and QUAL (include/kslam_samseq.h); sq is read by those instantiations alone
+template <bool BAM, bool SEQ>
 __global__ __launch_bounds__(256) void k_sam_lengths(const Rec *__restrict__ recs, const kslam_read_pair *__restrict__ groups,
                                                      uint64_t n_groups, SamInputs in, SamAnnot A, SamParams P,
                                                      const SamPlan *__restrict__ plan, const uint64_t *__restrict__ val_off,
                                                      const uint8_t *__restrict__ mapq_vals, uint32_t *__restrict__ text_len,
-                                                     uint32_t *__restrict__ bad_read) {
+                                                     uint32_t *__restrict__ bad_read, SamSeq sq) {
   const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= n_groups) return;
   const SamPlan pl = plan[g];
@@ -537,21 +691,22 @@ __global__ __launch_bounds__(256) void k_sam_lengths(const Rec *__restrict__ rec
     if (P.paired && in.ids_off[r2 + 1] - in.ids_off[r2] > 254) atomicMin(bad_read, r2);
   }
   CountSink o;
-  write_group<BAM>(o, recs + groups[g].first, groups[g], pl, in, A, P, mapq_vals, val_off[g]);
+  write_group<BAM, SEQ>(o, recs + groups[g].first, groups[g], pl, in, A, P, mapq_vals, val_off[g], sq, nullptr);
   text_len[g] = (uint32_t)o.n;
 }
-template <bool BAM>
+template <bool BAM, bool SEQ>
 __global__ __launch_bounds__(256) void k_sam_write(const Rec *__restrict__ recs, const kslam_read_pair *__restrict__ groups,
                                                    uint64_t n_groups, SamInputs in, SamAnnot A, SamParams P,
                                                    const SamPlan *__restrict__ plan, const uint64_t *__restrict__ val_off,
                                                    const uint8_t *__restrict__ mapq_vals, const uint64_t *__restrict__ text_off,
-                                                   uint8_t *__restrict__ text) {
+                                                   uint8_t *__restrict__ text, SamSeq sq) {
+  const SeqLut *lut = block_lut<SEQ>();   // (before any thread leaves: it holds a barrier)
   const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= n_groups) return;
   const SamPlan pl = plan[g];
   if (!pl.n_rows) return;
   ByteSink o(text + text_off[g]);
-  write_group<BAM>(o, recs + groups[g].first, groups[g], pl, in, A, P, mapq_vals, val_off[g]);
+  write_group<BAM, SEQ>(o, recs + groups[g].first, groups[g], pl, in, A, P, mapq_vals, val_off[g], sq, lut);
   o.flush();
 }
 
@@ -657,21 +812,26 @@ void sam_plan(kslam_paired_overlap *d_recs, const kslam_read_pair *d_groups, uin
 }
 
 void sam_format(const kslam_paired_overlap *d_recs, const kslam_read_pair *d_groups, uint64_t n_groups, const SamInputs &in,
-                const SamAnnot &A, const SamParams &P, SamWork &W, uint64_t *text_bytes, hipStream_t s, bool bam, uint32_t *bad_read) {
+                const SamAnnot &A, const SamParams &P, SamWork &W, uint64_t *text_bytes, hipStream_t s, bool bam, uint32_t *bad_read,
+                const SamSeq *seq) {
   *text_bytes = 0;
   if (bad_read) *bad_read = 0xFFFFFFFFu;
   if (!n_groups) return;
   W.text_len.ensure(n_groups * 4);
   W.text_off.ensure((n_groups + 1) * 8);
   uint32_t *d_bad = W.totals.as<uint32_t>() + 10;   // (u64 slot 5)
+  const SamSeq sq = seq ? *seq : SamSeq{};
+  const dim3 grid(blocks_for(n_groups)), block(256);
+  if (bam) HIPCHK(hipMemsetAsync(d_bad, 0xFF, 4, s));
+#define SAM_LENGTHS(B, Q)                                                                                                    \
+  hipLaunchKernelGGL((k_sam_lengths<B, Q>), grid, block, 0, s, d_recs, d_groups, n_groups, in, A, P, W.plan.as<SamPlan>(),   \
+                     W.val_off.as<uint64_t>(), W.mapq.as<uint8_t>(), W.text_len.as<uint32_t>(), d_bad, sq)
   if (bam) {
-    HIPCHK(hipMemsetAsync(d_bad, 0xFF, 4, s));
-    hipLaunchKernelGGL(k_sam_lengths<true>, dim3(blocks_for(n_groups)), dim3(256), 0, s, d_recs, d_groups, n_groups, in, A, P,
-                       W.plan.as<SamPlan>(), W.val_off.as<uint64_t>(), W.mapq.as<uint8_t>(), W.text_len.as<uint32_t>(), d_bad);
+    if (seq) SAM_LENGTHS(true, true); else SAM_LENGTHS(true, false);
   } else {
-    hipLaunchKernelGGL(k_sam_lengths<false>, dim3(blocks_for(n_groups)), dim3(256), 0, s, d_recs, d_groups, n_groups, in, A, P,
-                       W.plan.as<SamPlan>(), W.val_off.as<uint64_t>(), W.mapq.as<uint8_t>(), W.text_len.as<uint32_t>(), d_bad);
+    if (seq) SAM_LENGTHS(false, true); else SAM_LENGTHS(false, false);
   }
+#undef SAM_LENGTHS
   HIPCHK(hipGetLastError());
   exclusive_scan_u32_to_u64(W.text_len.as<uint32_t>(), W.text_off.as<uint64_t>(), n_groups, W.totals.as<uint64_t>() + 2, W.scan_tmp.p, s);
   uint64_t t[4];   // u64 slots 2 .. 5: the total, (3, 4: other stages), the BAM refusal
@@ -683,12 +843,15 @@ void sam_format(const kslam_paired_overlap *d_recs, const kslam_read_pair *d_gro
   }
   W.text.ensure(total + 64);
   if (total) {
-    if (bam)
-      hipLaunchKernelGGL(k_sam_write<true>, dim3(blocks_for(n_groups)), dim3(256), 0, s, d_recs, d_groups, n_groups, in, A, P,
-                         W.plan.as<SamPlan>(), W.val_off.as<uint64_t>(), W.mapq.as<uint8_t>(), W.text_off.as<uint64_t>(), W.text.as<uint8_t>());
-    else
-      hipLaunchKernelGGL(k_sam_write<false>, dim3(blocks_for(n_groups)), dim3(256), 0, s, d_recs, d_groups, n_groups, in, A, P,
-                         W.plan.as<SamPlan>(), W.val_off.as<uint64_t>(), W.mapq.as<uint8_t>(), W.text_off.as<uint64_t>(), W.text.as<uint8_t>());
+#define SAM_WRITE(B, Q)                                                                                                    \
+  hipLaunchKernelGGL((k_sam_write<B, Q>), grid, block, 0, s, d_recs, d_groups, n_groups, in, A, P, W.plan.as<SamPlan>(),   \
+                     W.val_off.as<uint64_t>(), W.mapq.as<uint8_t>(), W.text_off.as<uint64_t>(), W.text.as<uint8_t>(), sq)
+    if (bam) {
+      if (seq) SAM_WRITE(true, true); else SAM_WRITE(true, false);
+    } else {
+      if (seq) SAM_WRITE(false, true); else SAM_WRITE(false, false);
+    }
+#undef SAM_WRITE
   }
   HIPCHK(hipGetLastError());
   *text_bytes = total;

@@ -23,6 +23,7 @@
 #include "../../include/kslam_samtext.h"
 #include "../../include/kslam_bgzf.h"
 #include "../../include/kslam_bam.h"
+#include "../../include/kslam_samseq.h"
 #include "workers.hpp"
 
 namespace {
@@ -111,8 +112,9 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     }
     // BGZF (include/kslam_bgzf.h): every SAM byte goes to the writer compressed -- the lanes compress what they format, the
     // header and any host-formatted batch go through kslam_bgzf_compress here; the EOF marker ends the file
-    int bgzf = 0, bam = 0;
-    if (kslam_get_sam_bgzf(ctx, &bgzf) != KSLAM_OK || kslam_get_sam_bam(ctx, &bam) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    int bgzf = 0, bam = 0, seq = 0;
+    if (kslam_get_sam_bgzf(ctx, &bgzf) != KSLAM_OK || kslam_get_sam_bam(ctx, &bam) != KSLAM_OK || kslam_get_sam_seq(ctx, &seq) != KSLAM_OK)
+      fail(KSLAM_ERR_ARG, "null context");
     // BAM (include/kslam_bam.h): the same file framing, with kslam_bam_header's bytes and BAM records inside the members
     if (bam) bgzf = 1;
     static const auto give_back = [](void *user, void *data) { kslam_free_pinned(static_cast<kslam_ctx *>(user), data); };
@@ -181,7 +183,7 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     //       second one at the same time.  From here on both only READ `res`; the pool shares its workers between their
     //       loops, and the serial stretches of one (offsets, buffer growth, the per-read file's write) run under the
     //       other's loops instead of leaving the workers idle.
-    auto host_stage = [&](kslam_batch_result res) {
+    auto host_stage = [&](kslam_batch_result res, Window win) {
       name_thread("kslam-host");
       kslam_reads_view reads = {res.n_reads, nullptr, res.reads_bases_off, nullptr, res.reads_bases_off, res.reads_ids, res.reads_ids_off};
       kslam_status tax_status = KSLAM_OK;
@@ -251,6 +253,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
           const double t0 = now_ms();
           if (bam && !(res.text_flags & KSLAM_TEXT_SAM_BAM))   // (a batch formatted before the switch went on: text, not records)
             fail(KSLAM_ERR_STATE, "kslam_set_sam_bam was switched on while a batch was in flight");
+          if ((seq != 0) != ((res.text_flags & KSLAM_TEXT_SAM_SEQ) != 0))   // (host-formatted batches follow `seq`: one file, one form)
+            fail(KSLAM_ERR_STATE, "kslam_set_sam_seq was changed while kslam_stream_classify was running");
           if (bgzf && !(res.text_flags & KSLAM_TEXT_SAM_BGZF)) {   // (the switch went on after the batch was formatted)
             st.sam_bytes += enqueue_compressed(res.sam_text, res.sam_text_len);
           } else {
@@ -275,10 +279,34 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
             return 0;
           };
           // BAM: the same stage writing records (kslam_tail_finish_write_rows_bam), gathered and compressed the same way
-          const kslam_status a = (bam ? kslam_tail_finish_write_rows_bam : kslam_tail_finish_write_rows)(
-              &host_sorted, &reads, index, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, res.details, res.md_pool, res.n_md,
-              res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs, bgzf ? append : kslam_write_queued,
-              bgzf ? (void *)&text : (void *)writer, &ts);
+          // SEQ / QUAL (include/kslam_samseq.h): the twin with the switch on, either record kind.  The lanes keep the bases
+          // and qualities on the device, so a batch that is formatted here has its window parsed into columns first
+          // (host/fastq.cpp, the same records the device indexed); the rows then read what the device's rows read.
+          kslam_reads_columns cols;
+          memset(&cols, 0, sizeof cols);
+          struct Release { kslam_reads_columns *c; ~Release() { kslam_reads_free(c); } } release{&cols};
+          kslam_reads_view seq_reads = reads;
+          if (seq) {
+            uint64_t c1 = 0, c2 = 0;
+            const kslam_status q = paired ? kslam_fastq_parse_pair(r1 + win.p1, win.e1 - win.p1, r2 + win.p2, win.e2 - win.p2, 0, 1,
+                                                                   P->tail.threads, &cols, &c1, &c2)
+                                          : kslam_fastq_parse(r1 + win.p1, win.e1 - win.p1, 0, 1, P->tail.threads, &cols, &c1);
+            if (q != KSLAM_OK) fail(q, kslam_tail_last_error());
+            if (cols.n_reads != res.n_reads || memcmp(cols.bases_off, res.reads_bases_off, sizeof(uint64_t) * (res.n_reads + 1)) != 0)
+              fail(KSLAM_ERR_INTERNAL, "the host's parse of a batch differs from the device's index");
+            seq_reads.bases = cols.bases;
+            seq_reads.quality = cols.quality;
+            seq_reads.quality_off = cols.quality_off;
+          }
+          const kslam_write_fn wr = bgzf ? append : kslam_write_queued;
+          void *const wu = bgzf ? (void *)&text : (void *)writer;
+          const kslam_status a =
+              seq ? kslam_tail_finish_write_rows_seq(&host_sorted, &seq_reads, index, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar,
+                                                     res.details, res.md_pool, res.n_md, res.read_pairs, res.n_read_pairs, res.pairs,
+                                                     res.n_pairs, bam, wr, wu, &ts)
+                  : (bam ? kslam_tail_finish_write_rows_bam : kslam_tail_finish_write_rows)(
+                        &host_sorted, &reads, index, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, res.details, res.md_pool,
+                        res.n_md, res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs, wr, wu, &ts);
           if (a != KSLAM_OK) fail(a, kslam_tail_last_error());
           st.sam_bytes += bgzf ? enqueue_compressed(text.data(), text.size()) : ts.sam_bytes;
           st.seconds_sam_text += (now_ms() - t0) * 1e-3;
@@ -298,6 +326,7 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       }
     };
 
+    std::deque<Window> windows;   // of the tickets, in their order
     for (;;) {
       Window w;
       while (tickets.size() < depth && next_window(&w)) {
@@ -311,12 +340,15 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
           fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
         st.seconds_submitting += (now_ms() - tsub) * 1e-3;
         tickets.push_back(tk);
+        windows.push_back(w);
       }
       if (tickets.empty()) break;
       const double ta = now_ms();
       kslam_batch_result res;
       const uint64_t tk = tickets.front();
       tickets.pop_front();
+      const Window win = windows.front();
+      windows.pop_front();
       const kslam_status cs = kslam_collect_batch(ctx, tk, &res);
       const double tb = now_ms();
       st.seconds_waiting_for_gpu += (tb - ta) * 1e-3;
@@ -335,7 +367,7 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         kslam_release_batch(ctx, &res);
         fail(KSLAM_ERR_INTERNAL, "the lane returned no device pairing");
       }
-      worker = std::thread(host_stage, res);
+      worker = std::thread(host_stage, res, win);
     }
     if (worker.joinable()) worker.join();
     if (worker_status != KSLAM_OK) fail(worker_status, worker_error);

@@ -38,6 +38,8 @@
 
 #include "../../include/kslam_tail.h"
 #include "../../include/kslam_bam.h"
+#include "../../include/kslam_samseq.h"
+#include "../csrc/seqcodes.h"
 #include <cerrno>
 #include <unistd.h>
 #include <fcntl.h>
@@ -833,6 +835,7 @@ struct SamInput {
   uint64_t n_md = 0;
   bool groups_sorted = false;  // KSLAM_TAIL_GROUPS_SORTED: writeSAMOutputPairs' per-pair sort already done
   bool bam = false;            // BAM records (put_record) instead of SAM lines (include/kslam_bam.h)
+  bool seq = false;            // SEQ and QUAL on the rows without flag 0x100 (include/kslam_samseq.h)
 };
 
 struct Row {  // SAMEntry, src/SAM.h:238-277, text fields as slices of the task's scratch
@@ -1037,6 +1040,7 @@ bool cigar_and_md(const SamInput &in, const kslam_overlap &o, Text &scratch, Row
     }
     return true;
   }
+  if (!in.reads->quality) fail(KSLAM_ERR_ARG, "a CIGAR to walk on the host needs the quality strings");
   const char *bases = in.reads->bases + rb, *qual = in.reads->quality + qb;
   const char *ref = in.index->bases + in.index->bases_off[o.entry];
   const int64_t ref_len = (int64_t)(in.index->bases_off[o.entry + 1] - in.index->bases_off[o.entry]);
@@ -1230,6 +1234,62 @@ struct LineWriter {
   }
 };
 
+// ---- SEQ / QUAL (include/kslam_samseq.h; csrc/samtext.hip: put_seq_text / put_seq_bam, same bytes) ----
+struct SeqCols {   // a row's two columns: the read's bases and qualities, and whether FLAG 0x10 turns them round
+  const char *bases = nullptr, *qual = nullptr;   // qual nullptr: the batch has no qualities
+  size_t len = 0;
+  bool on = false, rev = false;
+};
+SeqCols seq_cols(const SamInput &in, uint16_t flag, uint32_t read) {
+  SeqCols c;
+  if (!in.seq || (flag & 0x100)) return c;
+  const kslam_reads_view *rd = in.reads;
+  c.on = true;
+  c.len = (size_t)(rd->bases_off[read + 1] - rd->bases_off[read]);
+  c.bases = rd->bases + rd->bases_off[read];
+  c.qual = rd->quality ? rd->quality + rd->quality_off[read] : nullptr;
+  c.rev = (flag & 0x10) != 0;
+  if (c.qual && rd->quality_off[read + 1] - rd->quality_off[read] != c.len)
+    fail(KSLAM_ERR_ARG, "quality string length differs from the read length");
+  return c;
+}
+// columns 10 and 11, without the tab in front; at most 2 * len + 3 bytes
+char *put_seq_text(char *w, const SeqCols &c) {
+  if (!c.len) {   // a read without bases
+    memcpy(w, "*\t*", 3);
+    return w + 3;
+  }
+  const size_t n = c.len;
+  if (!c.rev) {
+    memcpy(w, c.bases, n);
+  } else {
+    for (size_t i = 0; i < n; i++) w[i] = (char)kslam_seq::complement((uint8_t)c.bases[n - 1 - i]);
+  }
+  w += n;
+  *w++ = '\t';
+  if (!c.qual) {
+    *w++ = '*';
+  } else {
+    if (!c.rev) memcpy(w, c.qual, n); else for (size_t i = 0; i < n; i++) w[i] = c.qual[n - 1 - i];
+    w += n;
+  }
+  return w;
+}
+// seq and qual of a record: (len + 1) / 2 + len bytes
+char *put_seq_bam(char *w, const SeqCols &c) {
+  const size_t n = c.len;
+  auto code = [&](size_t i) -> uint32_t {
+    return c.rev ? kslam_seq::nibble(kslam_seq::complement((uint8_t)c.bases[n - 1 - i])) : kslam_seq::nibble((uint8_t)c.bases[i]);
+  };
+  for (size_t i = 0; i < n; i += 2) *w++ = (char)(code(i) << 4 | (i + 1 < n ? code(i + 1) : 0u));   // the last nibble of an odd length is 0
+  if (!c.qual) {
+    memset(w, 0xFF, n);
+  } else {
+    for (size_t i = 0; i < n; i++) w[i] = (char)((uint8_t)(c.rev ? c.qual[n - 1 - i] : c.qual[i]) - 33);
+  }
+  return w + n;
+}
+
 // SAMEntry::getEntry, src/SAM.h:278-305
 void put_line(const SamInput &in, Text &out, const Text &scratch, const Row &r, uint32_t qname_read,
               int64_t gene, uint32_t xt, bool paired) {
@@ -1238,6 +1298,8 @@ void put_line(const SamInput &in, Text &out, const Text &scratch, const Row &r, 
   // everything variable in the line + room for the fixed text and 12 numbers of <= 20 digits
   size_t bound = (rd->ids_off[qname_read + 1] - rd->ids_off[qname_read]) +
                  (ix->locus_tag_off[r.rname_entry + 1] - ix->locus_tag_off[r.rname_entry]) + r.cigar_len + r.md_len + 384;
+  const SeqCols sc = seq_cols(in, r.flag, qname_read);
+  bound += 2 * sc.len;
   if (gene >= 0)
     bound += (ix->gene_name_off[gene + 1] - ix->gene_name_off[gene]) + (ix->protein_id_off[gene + 1] - ix->protein_id_off[gene]) +
              (ix->product_off[gene + 1] - ix->product_off[gene]);
@@ -1262,7 +1324,12 @@ void put_line(const SamInput &in, Text &out, const Text &scratch, const Row &r, 
   o.num(r.pnext);
   o.ch('\t');
   o.snum(r.tlen);
-  o.lit("\t*\t*");
+  if (sc.on) {
+    o.ch('\t');
+    o.w = put_seq_text(o.w, sc);
+  } else {
+    o.lit("\t*\t*");
+  }
   if (r.mapped) {
     if (in.p->report_cigar) {
       o.lit("\tMD:Z:");
@@ -1364,6 +1431,8 @@ void put_record(const SamInput &in, Text &out, const Text &scratch, const Row &r
   if (id_len > 254) long_read_id(id, id_len);
   const bool cigar = in.p->report_cigar && !r.cigar_star;
   size_t bound = id_len + 4 * r.cigar_len + r.md_len + 256;
+  const SeqCols sc = seq_cols(in, r.flag, qname_read);
+  bound += 2 * sc.len;
   if (gene >= 0)
     bound += (ix->gene_name_off[gene + 1] - ix->gene_name_off[gene]) + (ix->protein_id_off[gene + 1] - ix->protein_id_off[gene]) +
              (ix->product_off[gene + 1] - ix->product_off[gene]);
@@ -1399,13 +1468,14 @@ void put_record(const SamInput &in, Text &out, const Text &scratch, const Row &r
   o.u16(bam_reg2bin(pos, end));
   o.u16(n_ops);
   o.u16(r.flag);
-  o.u32(0);                                             // l_seq: SEQ and QUAL are "*"
+  o.u32(sc.on ? (uint32_t)sc.len : 0u);                 // l_seq: 0 when SEQ and QUAL are "*"
   o.u32(paired ? r.rname_entry : 0xFFFFFFFFu);          // next_refID: "=" / "*"
   o.u32((uint32_t)((int32_t)r.pnext - 1));              // next_pos
   o.u32((uint32_t)r.tlen);
   o.bytes(id, id_len);
   o.u8(0);
   o.w += 4 * (size_t)n_ops;                             // (written above)
+  if (sc.on) o.w = put_seq_bam(o.w, sc);
   if (r.mapped) {
     if (in.p->report_cigar) o.tag_z("MD", scratch.p + r.md_at, r.md_len);
     o.tag_int("AS", r.as);
@@ -1779,7 +1849,7 @@ void tail_to_sam(const kslam_tail_params *params, const kslam_reads_view *reads,
                  const kslam_index_view *index, const kslam_overlap *overlaps, uint64_t n_overlaps,
                  const uint32_t *cigar_pool, uint64_t n_cigar, const SamSink &sink,
                  kslam_tail_stats *stats, const kslam_row_detail *det = nullptr, const char *md_pool = nullptr,
-                 uint64_t n_md = 0, bool bam = false) {
+                 uint64_t n_md = 0, bool bam = false, bool seq = false) {
   Input in = make_input(params, reads, overlaps, n_overlaps);
   Arena &A = arena();
   std::lock_guard<std::mutex> one(A.call);
@@ -1789,6 +1859,7 @@ void tail_to_sam(const kslam_tail_params *params, const kslam_reads_view *reads,
   run_tail(in, A, ts, st);
   SamInput si{params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar};
   si.bam = bam;
+  si.seq = seq;
   if (det && cigar_pool) {
     if (!md_pool && n_md) fail(KSLAM_ERR_ARG, "null MD pool");
     si.det = det;
@@ -1979,8 +2050,8 @@ kslam_status kslam_tail_finish_prepare(const kslam_tail_params *params, const ks
   });
 }
 
-// kslam_tail_finish_write_rows and its BAM twin (bam: put_record instead of put_line)
-static kslam_status finish_write_rows(bool bam, const kslam_tail_params *params, const kslam_reads_view *reads,
+// kslam_tail_finish_write_rows and its twins (bam: put_record instead of put_line; seq: SEQ and QUAL on the primary rows)
+static kslam_status finish_write_rows(bool bam, bool seq, const kslam_tail_params *params, const kslam_reads_view *reads,
                                       const kslam_index_view *index, const kslam_overlap *overlaps, uint64_t n_overlaps,
                                       const uint32_t *cigar_pool, uint64_t n_cigar, const kslam_row_detail *details,
                                       const char *md_pool, uint64_t n_md, kslam_read_pair *read_pairs, uint64_t n_read_pairs,
@@ -2020,6 +2091,7 @@ static kslam_status finish_write_rows(bool bam, const kslam_tail_params *params,
     SamInput si{params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar};
     si.groups_sorted = (params->stages & KSLAM_TAIL_GROUPS_SORTED) != 0;
     si.bam = bam;
+    si.seq = seq;
     if (details && cigar_pool) {
       if (!md_pool && n_md) fail(KSLAM_ERR_ARG, "null MD pool");
       si.det = details;
@@ -2043,7 +2115,7 @@ kslam_status kslam_tail_finish_write_rows(const kslam_tail_params *params, const
                                           kslam_read_pair *read_pairs, uint64_t n_read_pairs,
                                           kslam_paired_overlap *pairs, uint64_t n_pairs, kslam_write_fn write,
                                           void *user, kslam_tail_stats *stats) {
-  return finish_write_rows(false, params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar, details, md_pool, n_md, read_pairs,
+  return finish_write_rows(false, false, params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar, details, md_pool, n_md, read_pairs,
                            n_read_pairs, pairs, n_pairs, write, user, stats);
 }
 
@@ -2054,7 +2126,7 @@ kslam_status kslam_tail_finish_write_rows_bam(const kslam_tail_params *params, c
                                               const char *md_pool, uint64_t n_md, kslam_read_pair *read_pairs,
                                               uint64_t n_read_pairs, kslam_paired_overlap *pairs, uint64_t n_pairs,
                                               kslam_write_fn write, void *user, kslam_tail_stats *stats) {
-  return finish_write_rows(true, params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar, details, md_pool, n_md, read_pairs,
+  return finish_write_rows(true, false, params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar, details, md_pool, n_md, read_pairs,
                            n_read_pairs, pairs, n_pairs, write, user, stats);
 }
 
@@ -2068,6 +2140,29 @@ kslam_status kslam_tail_sam_bam(const kslam_tail_params *params, const kslam_rea
     sink.text_len = len;
     tail_to_sam(params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar, sink, stats, nullptr, nullptr, 0, true);
   });
+}
+
+// ---- SEQ / QUAL (include/kslam_samseq.h): the same stages with the switch on ----
+kslam_status kslam_tail_sam_seq(const kslam_tail_params *params, const kslam_reads_view *reads, const kslam_index_view *index,
+                                const kslam_overlap *overlaps, uint64_t n_overlaps, const uint32_t *cigar_pool, uint64_t n_cigar,
+                                int bam, char **out, uint64_t *len, kslam_tail_stats *stats) {
+  return guarded([&] {
+    if (!out || !len) fail(KSLAM_ERR_ARG, "null output argument");
+    SamSink sink;
+    sink.text = out;
+    sink.text_len = len;
+    tail_to_sam(params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar, sink, stats, nullptr, nullptr, 0, bam != 0, true);
+  });
+}
+
+kslam_status kslam_tail_finish_write_rows_seq(const kslam_tail_params *params, const kslam_reads_view *reads,
+                                              const kslam_index_view *index, const kslam_overlap *overlaps, uint64_t n_overlaps,
+                                              const uint32_t *cigar_pool, uint64_t n_cigar, const kslam_row_detail *details,
+                                              const char *md_pool, uint64_t n_md, kslam_read_pair *read_pairs,
+                                              uint64_t n_read_pairs, kslam_paired_overlap *pairs, uint64_t n_pairs, int bam,
+                                              kslam_write_fn write, void *user, kslam_tail_stats *stats) {
+  return finish_write_rows(bam != 0, true, params, reads, index, overlaps, n_overlaps, cigar_pool, n_cigar, details, md_pool, n_md,
+                           read_pairs, n_read_pairs, pairs, n_pairs, write, user, stats);
 }
 
 kslam_status kslam_bam_header(const kslam_index_view *index, const char *sam_header, uint64_t len, char **out, uint64_t *out_len) {

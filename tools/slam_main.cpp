@@ -31,6 +31,7 @@
 #include "../include/kslam_bam.h"
 #include "../include/kslam_bgzf.h"
 #include "../include/kslam_db.h"
+#include "../include/kslam_samseq.h"
 #include "../include/kslam_stream.h"
 
 namespace {
@@ -68,7 +69,7 @@ struct Options {
   uint32_t num_reads = UINT32_MAX, num_reads_at_once = 10000000, num_alignments = 10;
   double score_fraction = 0.95;
   bool sam_xa = false, just_align = false, no_pseudo = false, help = false, version = false, parse_fasta = false, sam_bgzf = false,
-       sam_bam = false;
+       sam_bam = false, sam_seq = false;
   int device = 0;
   std::vector<std::string> inputs;
 };
@@ -107,13 +108,14 @@ void usage(FILE *o) {
         "  --no-pseudo-assembly                  do not link alignments together\n"
         "  --sam-bgzf                            write --sam-file as BGZF (blocked gzip, as bgzip writes it)\n"
         "  --sam-bam                             write --sam-file as BAM (implies --sam-bgzf)\n"
+        "  --sam-seq                             write SEQ and QUAL on the primary rows of --sam-file instead of \"*\"\n"
         "\n", o);
 }
 
 Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
-         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM };
+         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -129,6 +131,7 @@ Options parse(int argc, char **argv) {
       {"device", required_argument, nullptr, DEVICE},   // not in the reference: the HIP device ordinal (default 0)
       {"sam-bgzf", no_argument, nullptr, SAM_BGZF},     // not in the reference: the SAM file as BGZF (include/kslam_bgzf.h)
       {"sam-bam", no_argument, nullptr, SAM_BAM},       // not in the reference: the SAM file as BAM (include/kslam_bam.h)
+      {"sam-seq", no_argument, nullptr, SAM_SEQ},       // not in the reference: SEQ and QUAL in the SAM file (include/kslam_samseq.h)
       {nullptr, 0, nullptr, 0}};
   opterr = 0;
   int c;
@@ -157,6 +160,7 @@ Options parse(int argc, char **argv) {
       case XA: o.sam_xa = true; break;
       case SAM_BGZF: o.sam_bgzf = true; break;
       case SAM_BAM: o.sam_bam = true; break;
+      case SAM_SEQ: o.sam_seq = true; break;
       case VERSION: o.version = true; break;
       case JUST: o.just_align = true; break;
       case NOPSEUDO: o.no_pseudo = true; break;
@@ -333,6 +337,7 @@ int run(const Options &o, const std::string &command_line) {
   if (kslam_create(&kp, &ctx) != KSLAM_OK) die(std::string("GPU context: ") + (ctx ? kslam_last_error(ctx) : "kslam_create failed"));
   if (o.sam_bgzf && want_sam && kslam_set_sam_bgzf(ctx, 1) != KSLAM_OK) die(std::string("BGZF: ") + kslam_last_error(ctx));
   if (o.sam_bam && want_sam && kslam_set_sam_bam(ctx, 1) != KSLAM_OK) die(std::string("BAM: ") + kslam_last_error(ctx));
+  if (o.sam_seq && want_sam && kslam_set_sam_seq(ctx, 1) != KSLAM_OK) die(std::string("SEQ: ") + kslam_last_error(ctx));
   logl("Getting k-mers from index");
   if (kslam_set_index(ctx, index->n_entries, kslam_db_entry_bases(db), kslam_db_entry_lengths(db)) != KSLAM_OK)
     die(std::string("index: ") + kslam_last_error(ctx));
