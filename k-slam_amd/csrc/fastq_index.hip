@@ -16,6 +16,7 @@
 // reader): a line ends at "\n", "\r\n" or a lone "\r"; records are exactly four lines whatever they
 // contain; at the true end of the stream the unterminated rest (if any) and then one more, empty, line
 // are read, which can complete a record; `consumed` is where the reference's stream would stand.
+// The kernels here are pinned at every seam of their tiling by tests/test_gpu_fastq_index.py (texts: tests/fastq_seams.py).
 #include "common.h"
 
 namespace kslam {
