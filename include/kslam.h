@@ -561,6 +561,42 @@ kslam_status kslam_selftest_sort(kslam_ctx *ctx, uint64_t n, uint32_t iters,
                                  float *ms_per_sort, float *ms_per_scatter_launch,
                                  uint64_t *n_inversions);
 
+/* ---- test hooks for the device primitives every stage stands on (tests/test_gpu_sort_scan.py) ----
+ * The LSD radix sort (csrc/radix_sort.hip) with any pass list and any of its switches.  One pass = one 8-bit digit:
+ *   word 0 / 1                         bits [shift, shift + 8) of that 32-bit word of the record, after XOR with invert;
+ *   word 2 on FOUR-word records        the same of the third word (a k-mer record's meta word);
+ *   word 2 on TWO-word records         bits [shift, shift + 8) of the record as ONE 64-bit key (word 1 << 32 | word 0),
+ *                                      whatever words they straddle; invert, hi_shift and hi_bits do not apply (hi_bits 0);
+ *   hi_bits > 0                        a digit of two fields of the word: bits [shift, shift + 8 - hi_bits) below bits
+ *                                      [hi_shift, hi_shift + hi_bits).
+ * passes[0] is the least significant digit; every pass is stable. */
+typedef struct {
+  uint32_t word, shift, invert, hi_shift, hi_bits;
+} kslam_sort_pass;
+#define KSLAM_SORT_SETUP 1u          /* the one-time sorts' kernels (*_setup) */
+#define KSLAM_SORT_DIGIT_BYTES 2u    /* each scatter writes the next pass's digit bytes, the histograms read those */
+#define KSLAM_SORT_META_IN_RUNS 4u   /* setup + digit bytes, four-word records: word-2 digits take the histogram made for few values */
+#define KSLAM_SORT_FIRST_DIGITS 8u   /* first_digits holds passes[0]'s digit of every record (else first_digits is not read);
+                                        used with KSLAM_SORT_DIGIT_BYTES and two passes or more, as the sort itself does */
+/* recs: n host records of rec_words (2 or 4) 32-bit words, sorted in place.  The context's sort switches are as before on
+ * return.  KSLAM_ERR_ARG, before anything is launched, for: rec_words not 2 or 4, n_passes > 12, n >= 2^32, a null pointer
+ * that is needed, an unknown flag, KSLAM_SORT_FIRST_DIGITS without first_digits, and a pass with word > 2, hi_bits > 7,
+ * hi_shift + hi_bits > 32, hi_bits on the 64-bit key digit, or a digit that reads past its word (shift + 8 - hi_bits > 32)
+ * or past the 64-bit key (shift + 8 > 64). */
+kslam_status kslam_debug_radix_sort(kslam_ctx *ctx, uint32_t *recs, uint64_t n, uint32_t rec_words,
+                                    const kslam_sort_pass *passes, uint32_t n_passes, uint32_t flags,
+                                    const uint8_t *first_digits);
+/* The exclusive scans (csrc/scan.hip): out[i] = in[0] + ... + in[i - 1], as uint32 (wide 0: modulo 2^32) or uint64 (wide 1);
+ * *total (may be NULL) = the exact sum.  The device input / output start in_skew / out_skew (<= 15) elements into their
+ * allocations, so that the paths for buffers not aligned to 16 bytes run.  n < 2^32. */
+kslam_status kslam_debug_scan(kslam_ctx *ctx, const uint32_t *in, uint64_t n, void *out, int wide,
+                              uint32_t in_skew, uint32_t out_skew, uint64_t *total);
+/* The stable 8-way partition the SW tiers and the CIGAR bins share (csrc/scan.hip: partition_bins) of the element numbers
+ * 0 .. n - 1 by bins[i]: counts[k] = elements of bin k (k < 8; other bins are listed nowhere), lists (room for n) = the
+ * eight lists one after the other, each ascending.  n < 2^32. */
+kslam_status kslam_debug_partition_bins(kslam_ctx *ctx, const uint8_t *bins, uint64_t n, uint32_t *lists,
+                                        uint32_t *counts);
+
 #ifdef __cplusplus
 }
 #endif

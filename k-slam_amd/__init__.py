@@ -37,6 +37,7 @@ assert ROW_DETAIL_DT.itemsize == 32
 
 STATUS = {0: "OK", 1: "ERR_ARG", 2: "ERR_NO_DEVICE", 3: "ERR_OOM", 4: "ERR_UNSUPPORTED",
           5: "ERR_STATE", 6: "ERR_INTERNAL"}
+KSLAM_ERR_ARG = 1
 
 # every symbol include/kslam.h declares
 EXPORTS = ["kslam_abi_version", "kslam_index_build_stats", "kslam_version", "kslam_check_std_sort", "kslam_create", "kslam_destroy", "kslam_last_error", "kslam_reload_tuning", "kslam_ctx_device", "kslam_create_sibling", "kslam_adopt_results_device",
@@ -48,7 +49,8 @@ EXPORTS = ["kslam_abi_version", "kslam_index_build_stats", "kslam_version", "ksl
            "kslam_load_reads", "kslam_load_reads_device", "kslam_align_resident",
            "kslam_fetch_results", "kslam_take_results", "kslam_copy_results_device", "kslam_get_timings",
            "kslam_extract_kmers", "kslam_sort_kmers", "kslam_find_overlaps", "kslam_free",
-           "kslam_selftest_sort", "kslam_merge_shards_device", "kslam_shard_counts_device",
+           "kslam_selftest_sort", "kslam_debug_radix_sort", "kslam_debug_scan", "kslam_debug_partition_bins",
+           "kslam_merge_shards_device", "kslam_shard_counts_device",
            "kslam_export_shard_device", "kslam_multi_create", "kslam_multi_destroy",
            "kslam_multi_last_error", "kslam_multi_set_index", "kslam_multi_align_batch", "kslam_multi_free_batch"]
 
@@ -100,6 +102,10 @@ class IndexStats(C.Structure):
     """kslam_index_stats (include/kslam.h)"""
     _fields_ = [("n_genome_kmers", C.c_uint64), ("sort_passes", C.c_uint32), ("n_entries", C.c_uint32),
                 ("ms_encode_extract", C.c_float), ("ms_sort", C.c_float), ("ms_tables", C.c_float), ("ms_total", C.c_float)]
+
+
+# kslam_debug_radix_sort flags
+SORT_SETUP, SORT_DIGIT_BYTES, SORT_META_IN_RUNS, SORT_FIRST_DIGITS = 1, 2, 4, 8
 
 
 class KslamError(RuntimeError):
@@ -186,6 +192,9 @@ def lib():
         L.kslam_free.argtypes = [vp]
         L.kslam_selftest_sort.argtypes = [vp, u64, u32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                           C.POINTER(u64)]
+        L.kslam_debug_radix_sort.argtypes = [vp, vp, u64, u32, vp, u32, u32, vp]
+        L.kslam_debug_scan.argtypes = [vp, vp, u64, vp, C.c_int, u32, u32, vp]
+        L.kslam_debug_partition_bins.argtypes = [vp, vp, u64, vp, vp]
         L.kslam_merge_shards_device.argtypes = [vp, u32, vp, u64, vp, vp, vp, vp]
         L.kslam_shard_counts_device.argtypes = [vp, u64, vp]
         L.kslam_export_shard_device.argtypes = [vp, u64, u64, u64, u64, u64, vp, vp, vp, vp]
@@ -627,6 +636,38 @@ class Context:
         a, b, inv = C.c_float(), C.c_float(), C.c_uint64()
         self._chk(self._L.kslam_selftest_sort(self._h, n, iters, C.byref(a), C.byref(b), C.byref(inv)))
         return float(a.value), float(b.value), int(inv.value)
+
+    def debug_radix_sort(self, recs, passes, flags=0, first_digits=None):
+        """kslam_debug_radix_sort: recs uint32 [n, 2 or 4]; passes rows of (word, shift, invert, hi_shift, hi_bits);
+        flags of SORT_*; first_digits uint8 [n] or None -> the sorted records"""
+        out = np.array(recs, dtype=np.uint32, order="C")
+        assert out.ndim == 2
+        pl = np.ascontiguousarray(passes, dtype=np.uint32).reshape(-1, 5)
+        fd = None if first_digits is None else np.ascontiguousarray(first_digits, dtype=np.uint8)
+        assert fd is None or len(fd) == len(out)
+        if fd is not None and len(fd) == 0:
+            fd = np.zeros(1, dtype=np.uint8)       # (a pointer the library can tell from NULL)
+        self._chk(self._L.kslam_debug_radix_sort(self._h, out.ctypes.data, out.shape[0], out.shape[1], pl.ctypes.data, len(pl),
+                                                 flags, None if fd is None else fd.ctypes.data))
+        return out
+
+    def debug_scan(self, values, wide, in_skew=0, out_skew=0, want_total=True):
+        """kslam_debug_scan -> (exclusive sums as uint32 / uint64, total or None)"""
+        v = np.ascontiguousarray(values, dtype=np.uint32)
+        out = np.zeros(len(v), dtype=np.uint64 if wide else np.uint32)
+        tot = C.c_uint64(0)
+        self._chk(self._L.kslam_debug_scan(self._h, v.ctypes.data, len(v), out.ctypes.data, int(wide), in_skew, out_skew,
+                                           C.addressof(tot) if want_total else None))
+        return out, (int(tot.value) if want_total else None)
+
+    def debug_partition_bins(self, bins):
+        """kslam_debug_partition_bins -> (the 8 lists, the 8 counts)"""
+        b = np.ascontiguousarray(bins, dtype=np.uint8)
+        lists = np.zeros(max(len(b), 1), dtype=np.uint32)
+        counts = np.zeros(8, dtype=np.uint32)
+        self._chk(self._L.kslam_debug_partition_bins(self._h, b.ctypes.data, len(b), lists.ctypes.data, counts.ctypes.data))
+        edges = np.concatenate([[0], np.cumsum(counts.astype(np.int64))])
+        return [lists[edges[k]:edges[k + 1]] for k in range(8)], counts
 
     def find_overlaps(self):
         out = C.c_void_p()

@@ -367,4 +367,114 @@ kslam_status kslam_find_overlaps(kslam_ctx *c, kslam_overlap_temp **out, uint64_
   });
 }
 
+// ---- test hooks for the shared device primitives (tests/test_gpu_sort_scan.py): radix_sort.hip with any pass list and any
+// of its switches, scan.hip's two scans at any alignment, partition_bins.  Buffers of their own: nothing of the context's
+// but sortws is touched, and its switches are put back.
+kslam_status kslam_debug_radix_sort(kslam_ctx *c, uint32_t *recs, uint64_t n, uint32_t rec_words, const kslam_sort_pass *passes,
+                                    uint32_t n_passes, uint32_t flags, const uint8_t *first_digits) {
+  return guarded(c, [&] {
+    if (rec_words != 2 && rec_words != 4) throw StatusError{KSLAM_ERR_ARG, "records of 2 or 4 words"};
+    if (n_passes > 12) throw StatusError{KSLAM_ERR_ARG, "more than 12 passes"};
+    if (n >= (1ull << 32)) throw StatusError{KSLAM_ERR_ARG, "2^32 records or more"};
+    if ((n && !recs) || (n_passes && !passes)) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+    if (flags & ~15u) throw StatusError{KSLAM_ERR_ARG, "unknown flag"};
+    if ((flags & KSLAM_SORT_FIRST_DIGITS) && !first_digits) throw StatusError{KSLAM_ERR_ARG, "first-digits flag without the digit bytes"};
+    SortPass pl[12];
+    for (uint32_t i = 0; i < n_passes; i++) {
+      const kslam_sort_pass &p = passes[i];
+      if (p.word > 2) throw StatusError{KSLAM_ERR_ARG, "pass word above 2"};
+      if (p.hi_bits > 7) throw StatusError{KSLAM_ERR_ARG, "hi_bits above 7"};
+      if ((uint64_t)p.hi_shift + p.hi_bits > 32) throw StatusError{KSLAM_ERR_ARG, "high field beyond the word"};
+      const bool key64 = rec_words == 2 && p.word == 2;     // the digit of the whole 64-bit key (radix_sort.hip: digit_of)
+      if (key64 && p.hi_bits) throw StatusError{KSLAM_ERR_ARG, "two-field digit of the 64-bit key"};
+      if ((uint64_t)p.shift + (8u - p.hi_bits) > (key64 ? 64u : 32u)) throw StatusError{KSLAM_ERR_ARG, "digit beyond the word"};
+      pl[i] = SortPass{p.word, p.shift, p.invert};
+      pl[i].hi_shift = p.hi_shift;
+      pl[i].hi_bits = p.hi_bits;
+    }
+    if (n == 0) return;
+    hipStream_t s = c->stream;
+    SortWorkspace &ws = c->sortws;
+    DevBuf a, b;
+    a.ensure(n * rec_words * sizeof(uint32_t));
+    b.ensure(n * rec_words * sizeof(uint32_t));
+    HIPCHK(hipMemcpyAsync(a.p, recs, n * rec_words * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    const bool keep_bytes = ws.use_digit_bytes, keep_first = ws.first_digits_ready, keep_runs = ws.meta_digits_in_runs;
+    struct Restore {
+      SortWorkspace &w; bool bytes, first, runs;
+      ~Restore() { w.use_digit_bytes = bytes; w.first_digits_ready = first; w.meta_digits_in_runs = runs; }
+    } restore{ws, keep_bytes, keep_first, keep_runs};
+    ws.use_digit_bytes = (flags & KSLAM_SORT_DIGIT_BYTES) != 0;
+    ws.meta_digits_in_runs = (flags & KSLAM_SORT_META_IN_RUNS) != 0;
+    // (the sort reads digit bytes only with the switch on and a second pass to write them for)
+    ws.first_digits_ready = (flags & KSLAM_SORT_FIRST_DIGITS) && ws.use_digit_bytes && n_passes > 1;
+    if (ws.first_digits_ready) {
+      ws.digits.ensure(n + 64);
+      HIPCHK(hipMemcpyAsync(ws.digits.p, first_digits, n, hipMemcpyHostToDevice, s));
+    }
+    void *sorted = radix_sort(a.p, b.p, n, (int)rec_words, pl, (int)n_passes, ws, s, nullptr, nullptr, nullptr,
+                              (flags & KSLAM_SORT_SETUP) != 0);
+    HIPCHK(hipMemcpyAsync(recs, sorted, n * rec_words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(stream_wait(s));
+  });
+}
+
+kslam_status kslam_debug_scan(kslam_ctx *c, const uint32_t *in, uint64_t n, void *out, int wide, uint32_t in_skew, uint32_t out_skew,
+                              uint64_t *total) {
+  return guarded(c, [&] {
+    if (wide != 0 && wide != 1) throw StatusError{KSLAM_ERR_ARG, "wide is 0 or 1"};
+    if (in_skew > 15 || out_skew > 15) throw StatusError{KSLAM_ERR_ARG, "skew above 15 elements"};
+    if (n >= (1ull << 32)) throw StatusError{KSLAM_ERR_ARG, "2^32 elements or more"};
+    if (n && (!in || !out)) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+    hipStream_t s = c->stream;
+    const size_t out_size = wide ? sizeof(uint64_t) : sizeof(uint32_t);
+    DevBuf d_in, d_out, d_tmp, d_tot;
+    d_in.ensure((n + in_skew + 4) * sizeof(uint32_t));
+    d_out.ensure((n + out_skew + 4) * out_size);
+    d_tmp.ensure(scan_tmp_bytes(n));
+    d_tot.ensure(sizeof(uint64_t));
+    const uint32_t *din = d_in.as<uint32_t>() + in_skew;
+    if (n) HIPCHK(hipMemcpyAsync((void *)din, in, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d_tot.p, 0xFF, sizeof(uint64_t), s));
+    uint64_t *dtot = total ? d_tot.as<uint64_t>() : nullptr;
+    void *dout = d_out.as<uint8_t>() + (size_t)out_skew * out_size;
+    if (wide) exclusive_scan_u32_to_u64(din, (uint64_t *)dout, n, dtot, d_tmp.p, s);
+    else exclusive_scan_u32(din, (uint32_t *)dout, n, dtot, d_tmp.p, s);
+    if (n) HIPCHK(hipMemcpyAsync(out, dout, n * out_size, hipMemcpyDeviceToHost, s));
+    if (total) HIPCHK(hipMemcpyAsync(total, d_tot.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(stream_wait(s));
+  });
+}
+
+kslam_status kslam_debug_partition_bins(kslam_ctx *c, const uint8_t *bins, uint64_t n, uint32_t *lists, uint32_t *counts) {
+  return guarded(c, [&] {
+    if (!counts || (n && (!bins || !lists))) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+    if (n >= (1ull << 32)) throw StatusError{KSLAM_ERR_ARG, "2^32 elements or more"};
+    for (int k = 0; k < 8; k++) counts[k] = 0;
+    if (n == 0) return;
+    hipStream_t s = c->stream;
+    DevBuf d_bins, d_lists, d_counts, pos;
+    d_bins.ensure(n);
+    d_lists.ensure(8 * n * sizeof(uint32_t));     // any list may take every element
+    d_counts.ensure(8 * sizeof(uint32_t));
+    HIPCHK(hipMemcpyAsync(d_bins.p, bins, n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d_counts.p, 0, 8 * sizeof(uint32_t), s));
+    BinLists B;
+    for (int k = 0; k < 8; k++) B.list[k] = d_lists.as<uint32_t>() + (size_t)k * n;
+    B.count = d_counts.as<uint32_t>();
+    partition_bins(d_bins.as<uint8_t>(), n, B, pos, s);
+    HIPCHK(hipMemcpyAsync(counts, d_counts.p, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(stream_wait(s));
+    uint64_t at = 0;
+    for (int k = 0; k < 8; k++) at += counts[k];
+    if (at > n) throw StatusError{KSLAM_ERR_INTERNAL, "partition_bins: the lists hold more than n elements"};
+    at = 0;
+    for (int k = 0; k < 8; k++) {
+      if (counts[k]) HIPCHK(hipMemcpyAsync(lists + at, B.list[k], (size_t)counts[k] * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      at += counts[k];
+    }
+    HIPCHK(stream_wait(s));
+  });
+}
+
 }  // extern "C"
