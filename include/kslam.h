@@ -289,7 +289,8 @@ typedef struct {
   uint64_t n_paired_initial;    /* alignment pairs out of pairing */
   uint64_t n_insert_sizes;
   uint64_t n_read_pairs;        /* read pairs (or reads) with >= 1 alignment pair left */
-  uint64_t n_pairs;             /* alignment pairs left */
+  uint64_t n_pairs;             /* alignment pairs left = the sum of the read pairs' counts (after PSEUDO_ASM on the device the
+                                   records array keeps its length: kslam_take_pairs' n_pairs is that length) */
   uint32_t max_insert_size;     /* getMaxAllowedInsertSize; UINT32_MAX when not computed */
   uint32_t stages_done;         /* KSLAM_TAIL_* bits of the stages the device ran: the host tail runs the rest
                                    (PSEUDO_ASM is left to the host when one entry holds more than 262144

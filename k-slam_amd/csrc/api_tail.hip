@@ -168,7 +168,7 @@ void fill_pair_stats(const PairResult &r, kslam_pair_stats *st) {
   if (!st) return;
   memset(st, 0, sizeof *st);
   st->n_overlaps_screened = r.n_overlaps_screened; st->n_paired_initial = r.n_paired_initial;
-  st->n_insert_sizes = r.n_insert_sizes; st->n_read_pairs = r.n_read_pairs; st->n_pairs = r.n_pairs;
+  st->n_insert_sizes = r.n_insert_sizes; st->n_read_pairs = r.n_read_pairs; st->n_pairs = r.n_pairs_left;
   st->max_insert_size = r.max_insert_size;
   st->stages_done = r.stages_done;
 }

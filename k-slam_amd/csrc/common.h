@@ -548,6 +548,7 @@ struct PairWork {
 };
 struct PairResult {
   uint64_t n_overlaps_screened, n_paired_initial, n_insert_sizes, n_read_pairs, n_pairs;
+  uint64_t n_pairs_left;                 // what the groups' counts add up to: n_pairs until the second score screen shrinks groups in place
   uint32_t max_insert_size;
   uint32_t stages_done;                  // KSLAM_TAIL_* bits of the stages the device ran
   const kslam_read_pair *d_groups;       // n_read_pairs, `first` indexes d_pairs

@@ -743,18 +743,29 @@ __global__ __launch_bounds__(64) void k_debug_wave_sort(const int32_t *__restric
 
 // screenPairedAlignmentsByScore once more, in place on the dense records (host/tail.cpp: rescreen_stage)
 __global__ __launch_bounds__(256) void k_rescreen(Rec *__restrict__ recs, kslam_read_pair *__restrict__ groups, uint64_t n_groups,
-                                                  double fraction) {
+                                                  double fraction, unsigned long long *__restrict__ n_left) {
   const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= n_groups) return;
-  const uint32_t n = (uint32_t)groups[g].count;
-  if (!n) return;
-  Rec *v = recs + groups[g].first;
-  kslam_gnu::sort(v, v + n, ByScoreDesc());
-  const unsigned top = v[0].combined_score;
-  const double bar = top * fraction;
   uint32_t k = 0;
-  while (k < n && !((double)v[k].combined_score < bar)) k++;
-  groups[g].count = k;
+  const uint32_t n = g < n_groups ? (uint32_t)groups[g].count : 0u;
+  if (n) {
+    Rec *v = recs + groups[g].first;
+    kslam_gnu::sort(v, v + n, ByScoreDesc());
+    const unsigned top = v[0].combined_score;
+    const double bar = top * fraction;
+    while (k < n && !((double)v[k].combined_score < bar)) k++;
+    groups[g].count = k;
+  }
+  // the alignment pairs left (the records stay where they are: the dense array keeps its length), one atomic per workgroup
+  __shared__ uint32_t s_left[4];
+  uint32_t tot = k;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) tot += __shfl_down(tot, d, 64);
+  if ((threadIdx.x & 63) == 0) s_left[threadIdx.x >> 6] = tot;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t b = s_left[0] + s_left[1] + s_left[2] + s_left[3];
+    if (b) atomicAdd(n_left, (unsigned long long)b);
+  }
 }
 
 }  // namespace
@@ -875,6 +886,22 @@ static bool pseudo_on_records(R *recs, uint64_t n, bool from_groups, const kslam
   return true;
 }
 
+// the second score screen on this result's groups; res->n_pairs_left = the alignment pairs the groups still count
+static void rescreen(PairWork &W, PairResult *res, double score_fraction, hipStream_t s) {
+  const uint64_t n_groups = res->n_read_pairs;
+  res->n_pairs_left = 0;
+  if (!n_groups) return;
+  W.totals.ensure(16 * sizeof(uint64_t));
+  unsigned long long *d_left = reinterpret_cast<unsigned long long *>(W.totals.as<uint64_t>() + 2);   // (slot map: pair_phase_a)
+  HIPCHK(hipMemsetAsync(d_left, 0, sizeof(uint64_t), s));
+  hipLaunchKernelGGL(k_rescreen, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, s, const_cast<Rec *>(res->d_pairs),
+                     const_cast<kslam_read_pair *>(res->d_groups), n_groups, score_fraction, d_left);
+  HIPCHK(hipGetLastError());
+  uint64_t left = 0;
+  read_back(&left, d_left, sizeof left, s);
+  res->n_pairs_left = left;
+}
+
 bool pseudo_and_rescreen(PairWork &W, PairResult *res, double score_fraction, SortWorkspace &sortws, hipStream_t s) {
   const uint64_t n = res->n_pairs, n_groups = res->n_read_pairs;
   if (n == 0) { res->stages_done |= 4u; return true; }
@@ -882,8 +909,7 @@ bool pseudo_and_rescreen(PairWork &W, PairResult *res, double score_fraction, So
   Rec *recs = const_cast<Rec *>(res->d_pairs);
   kslam_read_pair *groups = const_cast<kslam_read_pair *>(res->d_groups);
   if (!pseudo_on_records(recs, n, true, groups, n_groups, W, sortws, s)) return false;
-  hipLaunchKernelGGL(k_rescreen, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, s, recs, groups, n_groups, score_fraction);
-  HIPCHK(hipGetLastError());
+  rescreen(W, res, score_fraction, s);
   res->stages_done |= 4u;
   return true;
 }
@@ -997,7 +1023,8 @@ void pair_phase_a(const kslam_overlap *d_ov, uint64_t n, const uint32_t *d_read_
   W.totals.ensure(16 * sizeof(uint64_t));
   uint64_t *tot = W.totals.as<uint64_t>();
   HIPCHK(hipMemsetAsync(tot, 0, 16 * sizeof(uint64_t), s));
-  // tot[4] inserts, [5] kept, [6] pairs after pairing
+  // tot[2] pairs left after the second score screen (rescreen), [3] big read pairs, [4] inserts, [5] kept, [6] pairs after pairing,
+  // [7] bad rows, [8] [9] the two scans of phase B, [10] big groups, [11] gaps, [12] [13] [14] pseudo-assembly, [15] referenced rows
   if (n >= (1ull << 32)) throw StatusError{KSLAM_ERR_UNSUPPORTED, ">= 2^32 overlap records in one batch"};
   W.row_start.ensure((n_reads + 2) * sizeof(uint32_t));
   const uint32_t gap_cap = (uint32_t)(n_reads / 64 + 2);   // stretches of more than 64 reads without rows: at most that many
@@ -1067,7 +1094,7 @@ void pair_phase_b(const kslam_overlap *d_ov, uint32_t limit, double score_fracti
   HIPCHK(hipMemcpyAsync(g2, tot + 8, sizeof g2, hipMemcpyDeviceToHost, s));
   HIPCHK(stream_wait(s));
   res->n_read_pairs = g2[0];
-  res->n_pairs = g2[1];
+  res->n_pairs = res->n_pairs_left = g2[1];
   W.groups.ensure((g2[0] + 1) * sizeof(kslam_read_pair));
   W.dense.ensure((g2[1] + 1) * sizeof(Rec));
   hipLaunchKernelGGL(k_emit_groups, dim3(nb), dim3(256), 0, s, W.recs.as<Rec>(), W.base.as<uint64_t>(), W.count.as<uint32_t>(),
@@ -1098,7 +1125,7 @@ void pair_and_screen(const kslam_overlap *d_ov, uint64_t n, const uint32_t *d_re
 // an entry holds more spans than one wavefront should sort: the caller runs the stage on the host.
 bool pseudo_merged(PairWork &W, PairResult *res, void *d_all, uint64_t n_all, uint64_t own_base, double score_fraction,
                    SortWorkspace &sortws, hipStream_t s) {
-  const uint64_t n_own = res->n_pairs, n_groups = res->n_read_pairs;
+  const uint64_t n_own = res->n_pairs;
   if (own_base + n_own > n_all) throw StatusError{KSLAM_ERR_ARG, "this shard's records lie outside the gathered array"};
   if (n_all == 0) { res->stages_done |= 4u; return true; }
   if (n_all >= (1ull << 28)) return false;
@@ -1107,10 +1134,9 @@ bool pseudo_merged(PairWork &W, PairResult *res, void *d_all, uint64_t n_all, ui
   if (n_own) {
     Rec *own = const_cast<Rec *>(res->d_pairs);
     hipLaunchKernelGGL(k_take_scores, dim3((unsigned)((n_own + 255) / 256)), dim3(256), 0, s, all, own_base, n_own, own);
-    hipLaunchKernelGGL(k_rescreen, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, s, own,
-                       const_cast<kslam_read_pair *>(res->d_groups), n_groups, score_fraction);
+    HIPCHK(hipGetLastError());
+    rescreen(W, res, score_fraction, s);
   }
-  HIPCHK(hipGetLastError());
   res->stages_done |= 4u;
   return true;
 }
@@ -1196,11 +1222,9 @@ void pseudo_return(PairWork &W, PairResult *res, const uint32_t *d_scores, uint6
   if (n != res->n_pairs || n != W.route_n) throw StatusError{KSLAM_ERR_ARG, "as many scores as kslam_pseudo_route sent heads"};
   if (n) {
     Rec *own = const_cast<Rec *>(res->d_pairs);
-    const uint64_t n_groups = res->n_read_pairs;
     hipLaunchKernelGGL(k_scores_home, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_scores, (const uint2 *)W.route_sorted, n, own);
-    hipLaunchKernelGGL(k_rescreen, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, s, own,
-                       const_cast<kslam_read_pair *>(res->d_groups), n_groups, score_fraction);
     HIPCHK(hipGetLastError());
+    rescreen(W, res, score_fraction, s);
   }
   W.route_n = ~0ull;
   res->stages_done |= 4u;

@@ -324,6 +324,7 @@ def test_sharded_tail_equals_one_context(kslam, synth, bounds, pseudo):
         recs.append(kd.device_bytes(d_pairs, n * 32, dev))
         limits.append(stats["max_insert_size"])
     assert len(set(limits)) == 1 and limits[0] == st["max_insert_size"]
+    left = []        # alignment pairs left per shard after the second score screen (kslam_pair_stats.n_pairs)
     if pseudo == "routed":
         # the entries partitioned over the shards (kslam_pseudo_route / _owned / _return): entry e is shard e mod N's; the
         # "all-to-all" lays the pieces a shard receives end to end in source order, the scores go back the same way
@@ -353,6 +354,7 @@ def test_sharded_tail_equals_one_context(kslam, synth, bounds, pseudo):
             torch.cuda.synchronize()
             s2 = c.pseudo_return(mine.data_ptr() if mine.numel() else None, mine.numel() // 4, 0.95)
             assert s2["stages_done"] & 4
+            left.append(s2["n_pairs"])
     elif pseudo:
         torch.cuda.synchronize()
         base = 0
@@ -361,6 +363,7 @@ def test_sharded_tail_equals_one_context(kslam, synth, bounds, pseudo):
             torch.cuda.synchronize()
             s2 = c.pseudo_merged(all_recs.data_ptr() if all_recs.numel() else None, all_recs.numel() // 32, base, 0.95)
             assert s2["stages_done"] & 4
+            left.append(s2["n_pairs"])
             base += mine.numel() // 32
     got, g_rp, g_pr = b"", 0, 0
     for c, loc, q, names in shards:
@@ -372,6 +375,8 @@ def test_sharded_tail_equals_one_context(kslam, synth, bounds, pseudo):
     whole.close()
     assert (g_rp, g_pr) == (n_rp, n_pr) and len(exp) > 200 * n_pairs
     assert got == exp
+    if pseudo:       # the groups shrink in place: the statistic counts what is left, the same on every path
+        assert sum(left) == st["n_pairs"] and st["n_pairs"] <= n_pr
 
 
 def test_default_bench_line_keeps_the_contract(tmp_path):
