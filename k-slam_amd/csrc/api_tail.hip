@@ -528,6 +528,88 @@ kslam_status kslam_bgzf_compress(kslam_ctx *c, const void *data, uint64_t len, c
   return st;
 }
 
+// ---- BGZF input (include/kslam_inflate.h, csrc/inflate.hip; the members are found by host/inflate.cpp) ----
+namespace {
+uint64_t inflate_round() {   // members per launch round: KSLAM_INFLATE_ROUND, read once per process
+  static const uint64_t round = [] {
+    const char *e = getenv("KSLAM_INFLATE_ROUND");
+    const long long v = e ? atoll(e) : 0;
+    // at most 4096 members of at most 64 KiB: a round's bit positions stay below 2^32
+    return (uint64_t)(v >= 1 && v <= (long long)INFLATE_ROUND ? v : INFLATE_ROUND);
+  }();
+  return round;
+}
+}  // namespace
+
+kslam_status kslam_bgzf_inflate(kslam_ctx *c, const void *data, uint64_t len, char **out, uint64_t *out_len) {
+  if (out) *out = nullptr;
+  if (out_len) *out_len = 0;
+  char *h = nullptr;
+  const kslam_status st = guarded(c, [&] {
+    if (!out || !out_len || (len && !data)) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+    using kslam_host::BgzfMember;
+    std::vector<BgzfMember> ms;
+    uint64_t text = 0;
+    try {
+      kslam_host::bgzf_walk(static_cast<const uint8_t *>(data), len, &ms, nullptr, &text);
+    } catch (const kslam_host::HostError &e) {
+      kslam_host::g_err = e.msg;
+      throw StatusError{e.code, e.msg};
+    }
+    h = (char *)pinned_get(c, text + 64);
+    InflateWork &W = c->inflw;
+    W.first_bad.ensure(sizeof(uint64_t));
+    std::vector<InflateMember> desc;
+    uint64_t text_done = 0;
+    const uint64_t round = inflate_round();
+    c->inflate_kernel_ms = 0;
+    for (uint64_t m0 = 0; m0 < ms.size(); m0 += round) {
+      const uint64_t g = std::min<uint64_t>(round, ms.size() - m0);
+      const uint64_t in0 = ms[m0].at, in_bytes = ms[m0 + g - 1].at + ms[m0 + g - 1].size - in0;
+      desc.resize(g);
+      uint64_t round_text = 0;
+      for (uint64_t k = 0; k < g; k++) {
+        const BgzfMember &m = ms[m0 + k];
+        desc[k] = InflateMember{(uint32_t)(m.at - in0) + kslam_host::BGZF_HEADER, m.size - kslam_host::BGZF_HEADER - kslam_host::BGZF_TRAILER,
+                                (uint32_t)round_text, m.isize, m.crc, 0};
+        round_text += m.isize;
+      }
+      W.in.ensure(in_bytes + 64);     // the buffer starts 4-byte aligned, and the window's last word may reach behind the bytes
+      W.out.ensure(round_text + 64);
+      W.members.ensure(g * sizeof(InflateMember));
+      HIPCHK(hipMemcpyAsync(W.in.p, static_cast<const char *>(data) + in0, in_bytes, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(W.members.p, desc.data(), g * sizeof(InflateMember), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(hipMemsetAsync(W.first_bad.p, 0xff, sizeof(uint64_t), c->stream));
+      HIPCHK(hipEventRecord(c->ev[0], c->stream));
+      inflate_members_device(W.in.as<uint8_t>(), W.members.as<InflateMember>(), (uint32_t)g, W.out.as<uint8_t>(), W.first_bad.as<uint64_t>(),
+                             c->stream);
+      HIPCHK(hipEventRecord(c->ev[1], c->stream));
+      uint64_t bad = 0;
+      read_back(&bad, W.first_bad.p, sizeof bad, c->stream);   // waits: desc may be refilled, and no text leaves before it is known good
+      c->inflate_kernel_ms += ev_ms(c->ev[0], c->ev[1]);
+      if (bad != ~0ull) {
+        const uint64_t m = m0 + (bad >> 8);
+        throw StatusError{KSLAM_ERR_ARG, "BGZF member " + std::to_string(m) + " (byte offset " + std::to_string(ms[m].at) + "): " +
+                                             inflate_error_name((uint32_t)(bad & 0xffu))};
+      }
+      if (round_text) HIPCHK(hipMemcpyAsync(h + text_done, W.out.p, round_text, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(stream_wait(c->stream));   // the next round overwrites W.out
+      text_done += round_text;
+    }
+    *out = h;
+    *out_len = text;
+  });
+  if (st != KSLAM_OK && h) pinned_put(c, h);
+  if (st != KSLAM_OK && out) *out = nullptr;
+  return st;
+}
+
+kslam_status kslam_bgzf_inflate_kernel_ms(kslam_ctx *c, double *ms) {
+  if (!c || !ms) return KSLAM_ERR_ARG;
+  *ms = c->inflate_kernel_ms;
+  return KSLAM_OK;
+}
+
 kslam_status kslam_set_sam_bgzf(kslam_ctx *c, int on) {
   return guarded(c, [&] {
     if (c->in_multi) throw StatusError{KSLAM_ERR_UNSUPPORTED, "BGZF output is not available on the contexts of a kslam_multi"};

@@ -17,10 +17,12 @@
 //           when the fixed-Huffman bits would take more bytes than the stored form
 //   emit    the same walk again writes its bits: words a thread covers completely are plain stores, the (zeroed) words
 //           it shares with a neighbour take atomicOr -- OR commutes, so the bytes do not depend on the order
-// The CRC32: each thread's range by a byte table, shifted to its place by a multiplication with x^(8 * bytes after it)
-// mod P (GF(2)), XOR-reduced.  Members are written into BGZF_SLOT-byte slots; scan.hip's exclusive scan of their sizes and
+// The CRC32 (crc32.h, shared with inflate.hip): each thread's range by a byte table, shifted to its place by a multiplication
+// with x^(8 * bytes after it) mod P (GF(2)), XOR-reduced.  Members are written into BGZF_SLOT-byte slots; scan.hip's exclusive scan of their sizes and
 // a gather kernel pack them.  BGZF_ROUND members per launch: the scratch does not grow with the input.
 #include "bgzf.h"
+
+#include "crc32.h"
 
 namespace kslam {
 namespace {
@@ -32,32 +34,8 @@ constexpr uint32_t BG_MISC = 64;                            // small shared valu
 constexpr uint32_t BG_HASH_BITS = 12, BG_HASH = 1u << BG_HASH_BITS;
 constexpr uint32_t BG_WINDOW = 32768;
 constexpr uint32_t BG_HEADER = 18, BG_TRAILER = 8;
-constexpr uint32_t CRC_POLY = 0xedb88320u;
 static_assert(BG_SEG * BG_THREADS == BGZF_MEMBER_IN, "one range per thread");
 static_assert((BG_WORDS + BG_MISC + BG_HASH) * 4 <= 80 * 1024, "two workgroups per CU");
-
-// x^(2^k) mod P, P the CRC-32 polynomial in reflected form (zlib's x2n_table)
-__constant__ uint32_t X2N[32] = {
-    0x40000000u, 0x20000000u, 0x08000000u, 0x00800000u, 0x00008000u, 0xedb88320u, 0xb1e6b092u, 0xa06a2517u,
-    0xed627daeu, 0x88d14467u, 0xd7bbfe6au, 0xec447f11u, 0x8e7ea170u, 0x6427800eu, 0x4d47bae0u, 0x09fe548fu,
-    0x83852d0fu, 0x30362f1au, 0x7b5a9cc3u, 0x31fec169u, 0x9fec022au, 0x6c8dedc4u, 0x15d6874du, 0x5fde7a4eu,
-    0xbad90e37u, 0x2e4e5eefu, 0x4eaba214u, 0xa8a472c0u, 0x429a969eu, 0x148d302au, 0xc40ba6d0u, 0xc4e22c3cu};
-
-__device__ inline uint32_t multmodp(uint32_t a, uint32_t b) {   // a * b mod P
-  uint32_t p = 0;
-  for (int i = 0; i < 32; i++) {
-    if (a & (0x80000000u >> i)) p ^= b;
-    b = (b & 1u) ? (b >> 1) ^ CRC_POLY : b >> 1;
-  }
-  return p;
-}
-
-__device__ inline uint32_t x8nmodp(uint32_t n) {   // x^(8 n) mod P
-  uint32_t p = 0x80000000u;
-  for (uint32_t k = 3; n; n >>= 1, k++)
-    if (n & 1u) p = multmodp(X2N[k & 31], p);
-  return p;
-}
 
 __device__ __forceinline__ uint32_t byte_at(const uint32_t *d, uint32_t p) { return (d[p >> 2] >> ((p & 3u) * 8u)) & 0xffu; }
 __device__ __forceinline__ uint32_t word_at(const uint32_t *d, uint32_t p) {   // bytes p .. p + 3, little-endian
@@ -211,11 +189,7 @@ __global__ __launch_bounds__(BG_THREADS) void k_bgzf_member(const uint8_t *__res
 
   // ---- the CRC table where the hash table was ----
   uint32_t *crc_tab = table;
-  {
-    uint32_t c = t;
-    for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ CRC_POLY : c >> 1;
-    crc_tab[t] = c;
-  }
+  crc_tab[t] = crc_table_entry(t);
   __syncthreads();
 
   // ---- parse (bit count) + CRC of this thread's range ----

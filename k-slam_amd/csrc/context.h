@@ -13,11 +13,14 @@
 #include "common.h"
 #include "samtext.h"
 #include "bgzf.h"
+#include "inflate.h"
 #include "../../include/kslam_samtext.h"
 #include "../../include/kslam_bgzf.h"
+#include "../../include/kslam_inflate.h"
 #include "../../include/kslam_bam.h"
 #include "../../include/kslam_samseq.h"
 #include "../host/workers.hpp"
+#include "../host/inflate.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -119,6 +122,8 @@ struct kslam_ctx {
   // ---- BGZF (bgzf.hip, include/kslam_bgzf.h): the scratch, the compressed bytes, kslam_bgzf_compress's upload ----
   BgzfWork bgzfw;
   DevBuf bgzf_out, bgzf_in;
+  InflateWork inflw;              // kslam_bgzf_inflate (inflate.hip, include/kslam_inflate.h): one round's bytes, text and members
+  double inflate_kernel_ms = 0;   // device time of the last kslam_bgzf_inflate's kernels, by events around each round's launch
   bool in_multi = false;          // one of a kslam_multi's contexts
 
   // ---- device pairing / screens (pairs.hip) ----

@@ -31,6 +31,7 @@
 #include "../include/kslam_bam.h"
 #include "../include/kslam_bgzf.h"
 #include "../include/kslam_db.h"
+#include "../include/kslam_inflate.h"
 #include "../include/kslam_samseq.h"
 #include "../include/kslam_stream.h"
 
@@ -88,6 +89,7 @@ void usage(FILE *o) {
         "\tAlign paired reads from R1FILE and R2FILE against DATABASE and perform metagenomic analysis\n"
         "or\tSLAM [option] --db=DATABASE R1FILE\n"
         "\tAlign reads from R1FILE against DATABASE and perform metagenomic analysis\n"
+        "\tR1FILE and R2FILE are FASTQ text or BGZF (bgzip-style .fastq.gz, inflated on the GPU), each on its own\n"
         "Allowed options:\n"
         "  --help                                produce help message\n"
         "  --db arg                              SLAM database directory which reads will be aligned against\n"
@@ -225,10 +227,28 @@ struct FileText {   // a whole file in memory -- page-locked (DMA straight from 
     if (!ok) die("reading " + path + " failed");
     good = true;
   }
-  ~FileText() {
-    if (p && pageable) free(p);
+  void release() {
+    if (p && owner) kslam_free_pinned(owner, p);
+    else if (p && pageable) free(p);
     else if (p) kslam_host_free(p, cap);
+    p = nullptr;
+    owner = nullptr;
   }
+  // A file that starts with the gzip magic is BGZF: its members are inflated on the GPU (include/kslam_inflate.h), the
+  // compressed bytes are released, and the run goes on with the text.  Plain gzip ends the run with the scan's message.
+  kslam_ctx *owner = nullptr;   // set: p is the context's page-locked text (kslam_free_pinned)
+  void inflate_if_gzip(kslam_ctx *ctx, const std::string &path) {
+    if (!good || !kslam_bgzf_is_gzip(p, len)) return;
+    uint64_t n_members = 0, text_len = 0;
+    if (kslam_bgzf_scan(p, len, &n_members, &text_len) != KSLAM_OK) die(path + ": " + kslam_tail_last_error());
+    char *text = nullptr;
+    if (kslam_bgzf_inflate(ctx, p, len, &text, &text_len) != KSLAM_OK) die(path + ": " + kslam_last_error(ctx));
+    release();
+    p = text;
+    len = text_len;
+    owner = ctx;
+  }
+  ~FileText() { release(); }
 };
 
 bool write_file(const std::string &path, const char *p, uint64_t n) {
@@ -349,6 +369,8 @@ int run(const Options &o, const std::string &command_line) {
     t2.load(r2);
     if (!t2.good) logl("FASTQ file " + r2 + " bad");
   }
+  t1.inflate_if_gzip(ctx, r1);
+  t2.inflate_if_gzip(ctx, r2);
   // ---- outputs ----
   int sam_fd = -1, per_read_fd = -1;
   char *header = nullptr;
@@ -432,6 +454,8 @@ int run(const Options &o, const std::string &command_line) {
   kslam_free(tax_ids);
   kslam_free(header);
   if (report) kslam_taxreport_free(report);
+  t1.release();   // inflated text belongs to the context
+  t2.release();
   kslam_destroy(ctx);
   kslam_db_free(db);
   if (taxdb) kslam_taxdb_free(taxdb);
