@@ -597,6 +597,12 @@ kslam_status kslam_debug_scan(kslam_ctx *ctx, const uint32_t *in, uint64_t n, vo
  * eight lists one after the other, each ascending.  n < 2^32. */
 kslam_status kslam_debug_partition_bins(kslam_ctx *ctx, const uint8_t *bins, uint64_t n, uint32_t *lists,
                                         uint32_t *counts);
+/* Test hook, as the three above (tests/test_gpu_bgzf_dynamic.py): the code builder of the dynamic BGZF mode (kslam_bgzf.h: KSLAM_BGZF_DEFLATE_DYNAMIC; csrc/bgzf.hip: build_code), in one
+ * workgroup, on a histogram the caller supplies: lengths[s] = the length in bits of symbol s's code, 0 for a symbol the code
+ * leaves out.  counts and lengths are host arrays of n entries.  KSLAM_ERR_ARG for: a null pointer, n < 2 or n > 286,
+ * limit < 1, limit > 15 or 2^limit < n, and counts whose sum is 2^32 or more. */
+kslam_status kslam_debug_bgzf_code_lengths(kslam_ctx *ctx, const uint32_t *counts, uint32_t n, uint32_t limit,
+                                           uint8_t *lengths);
 
 #ifdef __cplusplus
 }

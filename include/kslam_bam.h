@@ -15,8 +15,8 @@
  *
  * Use:  kslam_set_sam_bam(ctx, 1) before the batches: the pipelined lanes then write BAM records instead of SAM text and
  * compress them on the device; kslam_collect_batch returns the members in sam_text / sam_text_len with KSLAM_TEXT_SAM_BGZF
- * and KSLAM_TEXT_SAM_BAM in text_flags.  BAM implies BGZF, whatever kslam_set_sam_bgzf says.  The per-read text stays
- * plain.  kslam_stream_classify (kslam_stream.h) writes the whole file when the switch is on.
+ * and KSLAM_TEXT_SAM_BAM in text_flags.  BAM implies BGZF, whatever kslam_set_sam_bgzf says; kslam_set_bgzf_deflate
+ * (kslam_bgzf.h) applies to the members of a BAM file as to any others.  The per-read text stays plain.  kslam_stream_classify (kslam_stream.h) writes the whole file when the switch is on.
  */
 #ifndef KSLAM_BAM_H_
 #define KSLAM_BAM_H_

@@ -5,7 +5,9 @@
  * A BGZF file is a series of gzip members of at most 65 536 bytes, each holding at most 65 280 input bytes, ended by the
  * 28-byte empty member KSLAM_BGZF_EOF.  zcat, gzip -d, Python's gzip module and htslib read it; every member can be
  * inflated on its own.  The library writes every member as ONE deflate block: fixed Huffman codes (LZ77 matches inside
- * the member), or stored when that is smaller.  The bytes depend on the input alone.
+ * the member), or stored when that is smaller.  With kslam_set_bgzf_deflate(ctx, KSLAM_BGZF_DEFLATE_DYNAMIC) a member may
+ * also carry Huffman codes of its own (BTYPE 10), whichever of the three forms is smallest: the same matches, a smaller
+ * file.  The bytes depend on the input and that mode alone.
  *
  * Use:  kslam_set_sam_bgzf(ctx, 1) before the batches: the pipelined lanes then compress the SAM text they format on the
  * device (kslam_set_sam_text) before it leaves the GPU; kslam_collect_batch returns the BGZF members in sam_text /
@@ -38,6 +40,18 @@ kslam_status kslam_set_sam_bgzf(kslam_ctx *ctx, int on);
 
 /* *on = the switch above */
 kslam_status kslam_get_sam_bgzf(kslam_ctx *ctx, int *on);
+
+/* How the context deflates every member it compresses: kslam_bgzf_compress, the lanes under kslam_set_sam_bgzf and
+ * kslam_set_sam_bam, and what kslam_stream_classify sends through them, the header members included. */
+#define KSLAM_BGZF_DEFLATE_FIXED 0   /* fixed codes (BTYPE 01), or stored when that is smaller; the default */
+#define KSLAM_BGZF_DEFLATE_DYNAMIC 1 /* per member the smallest of stored, fixed and dynamic (BTYPE 10): dynamic only when
+                                        strictly smaller than fixed, stored only when strictly smaller than both */
+/* Any other mode: KSLAM_ERR_ARG.  A context of a kslam_multi gets KSLAM_ERR_UNSUPPORTED.  Set it between batches, never
+ * while one is in flight: a batch is compressed with the mode that holds when its lane reaches the compressor. */
+kslam_status kslam_set_bgzf_deflate(kslam_ctx *ctx, int mode);
+
+/* *mode = the mode above */
+kslam_status kslam_get_bgzf_deflate(kslam_ctx *ctx, int *mode);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,7 @@
  * kslam_taxreport_xml (include/kslam_taxonomy.h) give <out>_abbreviated and <out>.
  *
  * With kslam_set_sam_bgzf (kslam_bgzf.h) on for ctx, the SAM file is written as BGZF: the header, every batch, an EOF marker.
+ * kslam_set_bgzf_deflate (kslam_bgzf.h) applies to every one of those members, the header's included.
  * With kslam_set_sam_bam (kslam_bam.h) on, it is written as BAM: kslam_bam_header's bytes and every batch's records, as BGZF.
  * With kslam_set_sam_seq (kslam_samseq.h) on, the rows without flag 0x100 carry SEQ and QUAL, in any of the three forms.
  * Same library as kslam.h; needs a context with an index (kslam_set_index).  Single-end data (the reference's

@@ -49,7 +49,7 @@ EXPORTS = ["kslam_abi_version", "kslam_index_build_stats", "kslam_version", "ksl
            "kslam_load_reads", "kslam_load_reads_device", "kslam_align_resident",
            "kslam_fetch_results", "kslam_take_results", "kslam_copy_results_device", "kslam_get_timings",
            "kslam_extract_kmers", "kslam_sort_kmers", "kslam_find_overlaps", "kslam_free",
-           "kslam_selftest_sort", "kslam_debug_radix_sort", "kslam_debug_scan", "kslam_debug_partition_bins",
+           "kslam_selftest_sort", "kslam_debug_radix_sort", "kslam_debug_scan", "kslam_debug_partition_bins", "kslam_debug_bgzf_code_lengths",
            "kslam_merge_shards_device", "kslam_shard_counts_device",
            "kslam_export_shard_device", "kslam_multi_create", "kslam_multi_destroy",
            "kslam_multi_last_error", "kslam_multi_set_index", "kslam_multi_align_batch", "kslam_multi_free_batch"]
@@ -195,6 +195,7 @@ def lib():
         L.kslam_debug_radix_sort.argtypes = [vp, vp, u64, u32, vp, u32, u32, vp]
         L.kslam_debug_scan.argtypes = [vp, vp, u64, vp, C.c_int, u32, u32, vp]
         L.kslam_debug_partition_bins.argtypes = [vp, vp, u64, vp, vp]
+        L.kslam_debug_bgzf_code_lengths.argtypes = [vp, vp, u32, u32, vp]
         L.kslam_merge_shards_device.argtypes = [vp, u32, vp, u64, vp, vp, vp, vp]
         L.kslam_shard_counts_device.argtypes = [vp, u64, vp]
         L.kslam_export_shard_device.argtypes = [vp, u64, u64, u64, u64, u64, vp, vp, vp, vp]
@@ -668,6 +669,13 @@ class Context:
         self._chk(self._L.kslam_debug_partition_bins(self._h, b.ctypes.data, len(b), lists.ctypes.data, counts.ctypes.data))
         edges = np.concatenate([[0], np.cumsum(counts.astype(np.int64))])
         return [lists[edges[k]:edges[k + 1]] for k in range(8)], counts
+
+    def debug_bgzf_code_lengths(self, counts, limit):
+        """kslam_debug_bgzf_code_lengths -> the code lengths, one per count"""
+        cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+        out = np.full(max(len(cnt), 1), 0xEE, dtype=np.uint8)
+        self._chk(self._L.kslam_debug_bgzf_code_lengths(self._h, cnt.ctypes.data, len(cnt), int(limit), out.ctypes.data))
+        return out[:len(cnt)].tolist()
 
     def find_overlaps(self):
         out = C.c_void_p()

@@ -368,7 +368,7 @@ kslam_status kslam_find_overlaps(kslam_ctx *c, kslam_overlap_temp **out, uint64_
 }
 
 // ---- test hooks for the shared device primitives (tests/test_gpu_sort_scan.py): radix_sort.hip with any pass list and any
-// of its switches, scan.hip's two scans at any alignment, partition_bins.  Buffers of their own: nothing of the context's
+// of its switches, scan.hip's two scans at any alignment, partition_bins; and bgzf.hip's code builder (tests/test_gpu_bgzf_dynamic.py).  Buffers of their own: nothing of the context's
 // but sortws is touched, and its switches are put back.
 kslam_status kslam_debug_radix_sort(kslam_ctx *c, uint32_t *recs, uint64_t n, uint32_t rec_words, const kslam_sort_pass *passes,
                                     uint32_t n_passes, uint32_t flags, const uint8_t *first_digits) {
@@ -415,6 +415,25 @@ kslam_status kslam_debug_radix_sort(kslam_ctx *c, uint32_t *recs, uint64_t n, ui
     void *sorted = radix_sort(a.p, b.p, n, (int)rec_words, pl, (int)n_passes, ws, s, nullptr, nullptr, nullptr,
                               (flags & KSLAM_SORT_SETUP) != 0);
     HIPCHK(hipMemcpyAsync(recs, sorted, n * rec_words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(stream_wait(s));
+  });
+}
+
+kslam_status kslam_debug_bgzf_code_lengths(kslam_ctx *c, const uint32_t *counts, uint32_t n, uint32_t limit, uint8_t *lengths) {
+  return guarded(c, [&] {
+    if (!counts || !lengths) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+    if (n < 2 || n > 286) throw StatusError{KSLAM_ERR_ARG, "2 to 286 symbols"};
+    if (limit < 1 || limit > 15 || (1u << limit) < n) throw StatusError{KSLAM_ERR_ARG, "a limit of 1 to 15 bits that the symbols fit"};
+    uint64_t sum = 0;
+    for (uint32_t s = 0; s < n; s++) sum += counts[s];
+    if (sum >= (1ull << 32)) throw StatusError{KSLAM_ERR_ARG, "counts that sum to 2^32 or more"};
+    hipStream_t s = c->stream;
+    DevBuf d_counts, d_lengths;
+    d_counts.ensure(n * sizeof(uint32_t));
+    d_lengths.ensure(n);
+    HIPCHK(hipMemcpyAsync(d_counts.p, counts, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    bgzf_code_lengths_device(d_counts.as<uint32_t>(), n, limit, d_lengths.as<uint8_t>(), s);
+    HIPCHK(hipMemcpyAsync(lengths, d_lengths.p, n, hipMemcpyDeviceToHost, s));
     HIPCHK(stream_wait(s));
   });
 }

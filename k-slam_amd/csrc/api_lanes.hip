@@ -186,7 +186,7 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
       st = guarded(c, [&] {
         sam_stage_kernels(c, primary, sam, primary->samtext.sam, primary->samtext.per_read);
         if (bgzf) {
-          bgzf_compress_device(c->samw.text.as<char>(), sam.text_bytes, c->bgzfw, c->bgzf_out, &sam.text_bytes, c->stream);
+          bgzf_compress_device(c->samw.text.as<char>(), sam.text_bytes, primary->samtext.deflate, c->bgzfw, c->bgzf_out, &sam.text_bytes, c->stream);
           sam.d_sam = c->bgzf_out.p;
         }
       });

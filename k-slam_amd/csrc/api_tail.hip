@@ -513,7 +513,7 @@ kslam_status kslam_bgzf_compress(kslam_ctx *c, const void *data, uint64_t len, c
     if (len) {
       c->bgzf_in.ensure(len + 64);
       HIPCHK(hipMemcpyAsync(c->bgzf_in.p, data, len, hipMemcpyHostToDevice, c->stream));
-      bgzf_compress_device(c->bgzf_in.as<char>(), len, c->bgzfw, c->bgzf_out, &n_out, c->stream);
+      bgzf_compress_device(c->bgzf_in.as<char>(), len, c->samtext.deflate, c->bgzfw, c->bgzf_out, &n_out, c->stream);
     }
     h = (char *)pinned_get(c, n_out + 64);
     if (n_out) {
@@ -620,6 +620,20 @@ kslam_status kslam_set_sam_bgzf(kslam_ctx *c, int on) {
 kslam_status kslam_get_sam_bgzf(kslam_ctx *c, int *on) {
   if (!c || !on) return KSLAM_ERR_ARG;
   *on = c->samtext.bgzf ? 1 : 0;
+  return KSLAM_OK;
+}
+
+kslam_status kslam_set_bgzf_deflate(kslam_ctx *c, int mode) {
+  return guarded(c, [&] {
+    if (c->in_multi) throw StatusError{KSLAM_ERR_UNSUPPORTED, "BGZF output is not available on the contexts of a kslam_multi"};
+    if (mode != KSLAM_BGZF_DEFLATE_FIXED && mode != KSLAM_BGZF_DEFLATE_DYNAMIC) throw StatusError{KSLAM_ERR_ARG, "unknown deflate mode"};
+    c->samtext.deflate = mode;
+  });
+}
+
+kslam_status kslam_get_bgzf_deflate(kslam_ctx *c, int *mode) {
+  if (!c || !mode) return KSLAM_ERR_ARG;
+  *mode = c->samtext.deflate;
   return KSLAM_OK;
 }
 

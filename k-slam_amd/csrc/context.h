@@ -114,7 +114,8 @@ struct kslam_ctx {
   std::vector<DevBuf> annot_bufs;
   bool have_annot = false;
   SamWork samw;
-  struct { bool sam = false, per_read = false, bgzf = false, bam = false, seq = false; uint32_t num_alignments = 10; int sam_xa = 0; } samtext;   // for the lanes
+  struct { bool sam = false, per_read = false, bgzf = false, bam = false, seq = false; uint32_t num_alignments = 10; int sam_xa = 0;
+           int deflate = KSLAM_BGZF_DEFLATE_FIXED; } samtext;   // for the lanes; deflate: kslam_set_bgzf_deflate, also for kslam_bgzf_compress
   const uint8_t *d_ids = nullptr;       // read identifiers of the loaded batch (fqw.ids, or ids_buf)
   const uint64_t *d_ids_off = nullptr;
   DevBuf ids_buf, ids_off_buf;

@@ -70,7 +70,8 @@ struct Options {
   uint32_t num_reads = UINT32_MAX, num_reads_at_once = 10000000, num_alignments = 10;
   double score_fraction = 0.95;
   bool sam_xa = false, just_align = false, no_pseudo = false, help = false, version = false, parse_fasta = false, sam_bgzf = false,
-       sam_bam = false, sam_seq = false;
+       sam_bam = false, sam_seq = false, sam_deflate_given = false;
+  int sam_deflate = KSLAM_BGZF_DEFLATE_FIXED;
   int device = 0;
   std::vector<std::string> inputs;
 };
@@ -110,6 +111,7 @@ void usage(FILE *o) {
         "  --no-pseudo-assembly                  do not link alignments together\n"
         "  --sam-bgzf                            write --sam-file as BGZF (blocked gzip, as bgzip writes it)\n"
         "  --sam-bam                             write --sam-file as BAM (implies --sam-bgzf)\n"
+        "  --sam-deflate arg (=fixed)            fixed or dynamic: the Huffman codes of --sam-bgzf / --sam-bam (dynamic: a smaller file)\n"
         "  --sam-seq                             write SEQ and QUAL on the primary rows of --sam-file instead of \"*\"\n"
         "\n", o);
 }
@@ -117,7 +119,7 @@ void usage(FILE *o) {
 Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
-         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ };
+         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_DEFLATE };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -133,6 +135,7 @@ Options parse(int argc, char **argv) {
       {"device", required_argument, nullptr, DEVICE},   // not in the reference: the HIP device ordinal (default 0)
       {"sam-bgzf", no_argument, nullptr, SAM_BGZF},     // not in the reference: the SAM file as BGZF (include/kslam_bgzf.h)
       {"sam-bam", no_argument, nullptr, SAM_BAM},       // not in the reference: the SAM file as BAM (include/kslam_bam.h)
+      {"sam-deflate", required_argument, nullptr, SAM_DEFLATE},   // not in the reference: kslam_set_bgzf_deflate (include/kslam_bgzf.h)
       {"sam-seq", no_argument, nullptr, SAM_SEQ},       // not in the reference: SEQ and QUAL in the SAM file (include/kslam_samseq.h)
       {nullptr, 0, nullptr, 0}};
   opterr = 0;
@@ -163,6 +166,12 @@ Options parse(int argc, char **argv) {
       case SAM_BGZF: o.sam_bgzf = true; break;
       case SAM_BAM: o.sam_bam = true; break;
       case SAM_SEQ: o.sam_seq = true; break;
+      case SAM_DEFLATE:
+        if (strcmp(optarg, "fixed") != 0 && strcmp(optarg, "dynamic") != 0)
+          die(std::string("the argument ('") + optarg + "') for option '--sam-deflate' is invalid");
+        o.sam_deflate = strcmp(optarg, "dynamic") == 0 ? KSLAM_BGZF_DEFLATE_DYNAMIC : KSLAM_BGZF_DEFLATE_FIXED;
+        o.sam_deflate_given = true;
+        break;
       case VERSION: o.version = true; break;
       case JUST: o.just_align = true; break;
       case NOPSEUDO: o.no_pseudo = true; break;
@@ -174,6 +183,7 @@ Options parse(int argc, char **argv) {
       default: die(std::string("unrecognised option '") + (optind > 0 && optind <= argc ? argv[optind - 1] : "?") + "'");
     }
   }
+  if (o.sam_deflate_given && !o.sam_bgzf && !o.sam_bam) die("option '--sam-deflate' needs '--sam-bgzf' or '--sam-bam'");
   return o;
 }
 
@@ -357,6 +367,7 @@ int run(const Options &o, const std::string &command_line) {
   if (kslam_create(&kp, &ctx) != KSLAM_OK) die(std::string("GPU context: ") + (ctx ? kslam_last_error(ctx) : "kslam_create failed"));
   if (o.sam_bgzf && want_sam && kslam_set_sam_bgzf(ctx, 1) != KSLAM_OK) die(std::string("BGZF: ") + kslam_last_error(ctx));
   if (o.sam_bam && want_sam && kslam_set_sam_bam(ctx, 1) != KSLAM_OK) die(std::string("BAM: ") + kslam_last_error(ctx));
+  if (want_sam && kslam_set_bgzf_deflate(ctx, o.sam_deflate) != KSLAM_OK) die(std::string("BGZF: ") + kslam_last_error(ctx));
   if (o.sam_seq && want_sam && kslam_set_sam_seq(ctx, 1) != KSLAM_OK) die(std::string("SEQ: ") + kslam_last_error(ctx));
   logl("Getting k-mers from index");
   if (kslam_set_index(ctx, index->n_entries, kslam_db_entry_bases(db), kslam_db_entry_lengths(db)) != KSLAM_OK)
