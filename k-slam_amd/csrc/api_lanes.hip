@@ -201,6 +201,20 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
                           (bgzf ? KSLAM_TEXT_SAM_BGZF : 0u) | (bam ? KSLAM_TEXT_SAM_BAM : 0u) | (sam.seq ? KSLAM_TEXT_SAM_SEQ : 0u);
     }
     sam_stage_free(c, sam);
+    // (kslam_set_reads_out) the records split by outcome, cut out of the text this lane uploaded.  Outside the compute token as
+    // well: a streaming copy next to the other lane's alignment kernels.  A batch whose pseudo-assembly is left to the host
+    // has no final read pairs yet: the host twin splits it.
+    const uint32_t ro_which = primary->reads_out.which;
+    if (ro_which) {
+      job->ro_on = true;
+      job->ro_supported = job->fastq_text && primary->pairing.stages != 0;
+      if (st == KSLAM_OK && job->ro_supported) {
+        if (pseudo_left) job->ro.flags = KSLAM_READS_OUT_LEFT_TO_HOST;
+        else st = guarded(c, [&] {
+          split_resident(c, job->single, c->pres.d_groups, c->pres.n_read_pairs, ro_which, primary->reads_out.bgzf, primary->samtext.deflate, &job->ro);
+        });
+      }
+    }
     t3 = now();
     // with the SAM records written on the device the host has no use for the rows, the CIGAR pool, the per-row details and
     // the MD text (0.7 GB per batch of configs[1]): they stay where they are, only their counts travel
@@ -284,6 +298,7 @@ void stop_lanes(kslam_ctx *c) {
     delete j;
   }
   c->jobs.clear();
+  c->ro_ready.clear();   // (their blocks went with the lanes' page-locked pools)
   c->as_stop = false;
 }
 
@@ -507,7 +522,16 @@ kslam_status kslam_collect_batch(kslam_ctx *c, uint64_t ticket, kslam_batch_resu
     res->consumed1 = job->consumed[0]; res->consumed2 = job->consumed[1];
     res->sam_text = job->sam_text; res->sam_text_len = job->sam_len; res->per_read_text = job->pr_text; res->per_read_len = job->pr_len;
     res->tax_ids = job->tax; res->text_flags = job->text_flags;
+    if (job->ro_on) {   // kept for kslam_collect_reads_out
+      std::lock_guard<std::mutex> lk(c->as_mu);
+      while (c->ro_ready.size() >= 16) {
+        free_reads_out(c, &c->ro_ready.begin()->second.out);
+        c->ro_ready.erase(c->ro_ready.begin());
+      }
+      c->ro_ready[ticket] = kslam_ctx::ReadsOutEntry{job->ro_supported, job->ro};
+    }
   } else {
+    free_reads_out(c, &job->ro);
     kslam_free_pinned(c, job->sam_text);
     kslam_free_pinned(c, job->pr_text);
     kslam_free_pinned(c, job->tax);

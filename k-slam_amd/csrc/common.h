@@ -561,8 +561,20 @@ void pair_and_screen(const kslam_overlap *d_ov, uint64_t n, const uint32_t *d_re
                      SortWorkspace &sortws, PairResult *res, hipStream_t s);
 
 // --------------------------------------------------------- fastq_index.hip
+// one FASTQ stream of an indexed batch: its text and line-terminator list on the device (fastq_lines.h: line_span)
+struct FqStream {
+  const uint8_t *text;   // the stream's first byte (device)
+  uint64_t len;
+  const uint64_t *ev;    // terminator positions
+  uint64_t terminated;   // their number
+  uint64_t rest_start;   // text after the last terminator
+  uint64_t n;            // records taken
+  uint64_t shift;        // position of the stream inside [r1 | r2]
+  uint64_t first;        // number of its first record in the batch
+};
 struct FastqWork {
   DevBuf tile_count, tile_base, scan_tmp, totals, ev[2], bases_at, quality_at, blen, id_at, id_len, bases_off, ids_off, ids;
+  FqStream st[2]{};      // the two streams of the last fastq_index_device: valid, like ev, until the next one (readsplit.hip)
 };
 struct FastqIndexResult {
   uint64_t n_reads, bases_total, ids_total;
@@ -610,5 +622,25 @@ void debug_wave_sort(const int32_t *keys, const uint64_t *seg_off, uint64_t n_se
 // text[quality_at[i] ..), d_off[i + 1] - d_off[i] bytes each, to d_bases / d_quality + d_off[i]
 void gather_fields(const uint8_t *d_text, const uint64_t *d_bases_at, const uint64_t *d_quality_at, const uint64_t *d_off,
                    uint64_t n_reads, uint8_t *d_bases, uint8_t *d_quality, hipStream_t s);
+
+// ----------------------------------------------------------- readsplit.hip
+// The batch's records split by outcome (include/kslam_readsplit.h): streams 0 / 1 = classified R1 / R2, 2 / 3 = unclassified.
+struct ReadSplitWork {
+  DevBuf flag, len_sel, len_unsel, src, off_sel, off_unsel, scan_tmp, totals, out[4];
+  hipEvent_t ev[4]{};          // around the flag + length + scan launches, and around the copy launches
+  float kernel_ms = 0;         // their device time, last batch (tools/readsplit_bench.py)
+  uint64_t bytes_moved = 0;    // text bytes the copy kernels read + wrote, last batch
+  ReadSplitWork() = default;
+  ReadSplitWork(const ReadSplitWork &) = delete;
+  ReadSplitWork &operator=(const ReadSplitWork &) = delete;
+  ~ReadSplitWork() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+// st: FastqWork::st of the batch; d_groups: its final read pairs; which: KSLAM_READS_OUT_* bits.  Leaves stream k in W.out[k],
+// bytes[k] long, n_records[0] classified and n_records[1] unclassified records per stream.  Waits for the stream (the sizes are read back).
+void read_split_device(const FqStream st[2], bool single, const kslam_read_pair *d_groups, uint64_t n_groups, uint32_t which,
+                       ReadSplitWork &W, uint64_t bytes[4], uint64_t n_records[2], hipStream_t s);
 
 }  // namespace kslam

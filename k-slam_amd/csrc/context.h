@@ -19,6 +19,7 @@
 #include "../../include/kslam_inflate.h"
 #include "../../include/kslam_bam.h"
 #include "../../include/kslam_samseq.h"
+#include "../../include/kslam_readsplit.h"
 #include "../host/workers.hpp"
 #include "../host/inflate.hpp"
 #include <algorithm>
@@ -126,6 +127,11 @@ struct kslam_ctx {
   InflateWork inflw;              // kslam_bgzf_inflate (inflate.hip, include/kslam_inflate.h): one round's bytes, text and members
   double inflate_kernel_ms = 0;   // device time of the last kslam_bgzf_inflate's kernels, by events around each round's launch
   bool in_multi = false;          // one of a kslam_multi's contexts
+  // ---- the reads split by outcome (readsplit.hip, include/kslam_readsplit.h) ----
+  ReadSplitWork rsw;
+  struct { uint32_t which = 0; bool bgzf = false; int fds[4] = {-1, -1, -1, -1}; } reads_out;   // for the lanes; fds: kslam_stream_set_reads_out
+  struct ReadsOutEntry { bool supported = false; kslam_reads_out out{}; };
+  std::map<uint64_t, ReadsOutEntry> ro_ready;   // by ticket: collected batches whose streams kslam_collect_reads_out has not taken (under as_mu)
 
   // ---- device pairing / screens (pairs.hip) ----
   PairWork pw;
@@ -163,6 +169,8 @@ struct kslam_ctx {
     kslam_pair_stats pstats{};
     char *sam_text = nullptr; uint64_t sam_len = 0; char *pr_text = nullptr; uint64_t pr_len = 0; uint32_t *tax = nullptr;
     uint32_t text_flags = 0;
+    bool ro_on = false, ro_supported = false;   // kslam_set_reads_out was on when the lane ran the batch; it came as FASTQ text
+    kslam_reads_out ro{};
   };
   struct AsyncLane {
     kslam_ctx *c = nullptr;
@@ -276,6 +284,12 @@ void fill_pair_stats(const PairResult &r, kslam_pair_stats *st);
 
 // ---- api_lanes.hip
 void stop_lanes(kslam_ctx *c);
+
+// ---- api_readsplit.hip
+// the split of the batch resident on c (indexed by fastq_index_device: c->fqw) by d_groups; blocks from c's page-locked pool
+void split_resident(kslam_ctx *c, bool single, const kslam_read_pair *d_groups, uint64_t n_groups, uint32_t which, bool bgzf, int deflate,
+                    kslam_reads_out *out);
+void free_reads_out(kslam_ctx *c, kslam_reads_out *out);
 
 }  // namespace kslam_api
 

@@ -18,6 +18,7 @@
 // are read, which can complete a record; `consumed` is where the reference's stream would stand.
 // The kernels here are pinned at every seam of their tiling by tests/test_gpu_fastq_index.py (texts: tests/fastq_seams.py).
 #include "common.h"
+#include "fastq_lines.h"
 
 namespace kslam {
 
@@ -120,34 +121,6 @@ __global__ __launch_bounds__(256) void k_fq_events(const uint8_t *__restrict__ t
   }
 }
 
-__device__ inline uint64_t line_after(const uint8_t *t, uint64_t len, uint64_t p) {
-  return (t[p] == '\r' && p + 1 < len && t[p + 1] == '\n') ? p + 2 : p + 1;
-}
-
-struct FqStream {
-  const uint8_t *text;   // the stream's first byte (device)
-  uint64_t len;
-  const uint64_t *ev;    // terminator positions
-  uint64_t terminated;   // their number
-  uint64_t rest_start;   // text after the last terminator
-  uint64_t n;            // records taken
-  uint64_t shift;        // position of the stream inside [r1 | r2]
-  uint64_t first;        // number of its first record in the batch
-};
-
-// line `l` of the stream: [start, end) and where the next line starts (host/fastq.cpp: index_stream)
-__device__ inline void line_span(const FqStream &s, uint64_t l, uint64_t *start, uint64_t *end, uint64_t *next) {
-  if (l < s.terminated) {
-    *start = l == 0 ? 0 : line_after(s.text, s.len, s.ev[l - 1]);
-    *end = s.ev[l];
-    *next = line_after(s.text, s.len, s.ev[l]);
-  } else if (l == s.terminated && s.rest_start < s.len) {
-    *start = s.rest_start; *end = s.len; *next = s.len;     // the unterminated rest
-  } else {
-    *start = s.len; *end = s.len; *next = s.len;            // the empty line read at end of stream
-  }
-}
-
 // first k in [0, n) with h[k] == c, or n: 16 bytes a step (one unaligned load), equal bytes found with the exact
 // zero-byte test on h ^ cccc.  Reads up to 15 bytes past h + n: the text buffer has 64 spare bytes after its end.
 struct __attribute__((packed, aligned(1))) FqBytes16 {
@@ -237,7 +210,7 @@ uint64_t index_events(const uint8_t *d_text, uint64_t scan_len, FastqWork &W, De
 void fastq_index_device(const uint8_t *d_text, uint64_t len1, uint64_t len2, const uint8_t *h_tail1, const uint8_t *h_tail2,
                         uint64_t max_pairs, bool at_eof, FastqWork &W, FastqIndexResult *res, hipStream_t s, bool single) {
   memset(res, 0, sizeof *res);
-  FqStream st[2];
+  FqStream *st = W.st;
   const uint64_t lens[2] = {len1, len2};
   const uint8_t *tails[2] = {h_tail1, h_tail2};
   for (int k = 0; k < 2; k++) {

@@ -24,6 +24,7 @@
 #include "../../include/kslam_bgzf.h"
 #include "../../include/kslam_bam.h"
 #include "../../include/kslam_samseq.h"
+#include "../../include/kslam_readsplit.h"
 #include "workers.hpp"
 
 namespace {
@@ -62,7 +63,10 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
   std::string worker_error;
   std::deque<uint64_t> tickets;
   std::vector<uint32_t> all_ids;
-  bool pairing_set = false, text_set = false;
+  bool pairing_set = false, text_set = false, reads_out_set = false;
+  int ro_fds[4] = {-1, -1, -1, -1};   // kslam_stream_set_reads_out: where the classified / unclassified records go
+  uint32_t ro_which = 0;
+  int ro_bgzf = 0;
 
   const int pool_cap = P && P->pool_threads ? (int)P->pool_threads : std::max(2, usable_cpus() - 4);
   Pool::get().add_cap(pool_cap);
@@ -83,6 +87,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       writer = nullptr;
     }
     if (text_set) kslam_set_sam_text(ctx, 0, 0, 10, 0);
+    if (reads_out_set) kslam_set_reads_out(ctx, 0);
+    if (ctx) kslam_stream_set_reads_out(ctx, nullptr);   // the descriptors held for this call alone
     if (pairing_set) kslam_set_pairing(ctx, 1, 0, 0.95, 0);
     Pool::get().remove_cap(pool_cap);
     return w;
@@ -101,6 +107,17 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     if (kslam_set_pairing(ctx, paired ? 1 : 0, P->tail.score_threshold, P->tail.score_fraction, stages) != KSLAM_OK)
       fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
     pairing_set = true;
+    // the reads themselves, split by outcome (include/kslam_readsplit.h): the lanes cut each batch's streams on the device
+    if (kslam_stream_get_reads_out(ctx, ro_fds) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    if (!paired) ro_fds[1] = ro_fds[3] = -1;
+    ro_which = ((ro_fds[0] >= 0 || ro_fds[1] >= 0) ? KSLAM_READS_OUT_CLASSIFIED : 0u) |
+               ((ro_fds[2] >= 0 || ro_fds[3] >= 0) ? KSLAM_READS_OUT_UNCLASSIFIED : 0u);
+    if (ro_which) {
+      if (kslam_set_reads_out(ctx, ro_which) != KSLAM_OK || kslam_get_reads_out_bgzf(ctx, &ro_bgzf) != KSLAM_OK)
+        fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
+      reads_out_set = true;
+    }
+    const bool host_split = getenv("KSLAM_HOST_SAM_TEXT") && getenv("KSLAM_HOST_SAM_TEXT")[0] == '1';   // (A/B: the host twin for every batch)
     // the SAM records and the per-read lines written on the GPU (include/kslam_samtext.h); KSLAM_HOST_SAM_TEXT=1 keeps the
     // host formatter for everything (A/B, and the route of a batch the device hands back without text)
     const bool device_text = !(getenv("KSLAM_HOST_SAM_TEXT") && getenv("KSLAM_HOST_SAM_TEXT")[0] == '1') && (P->sam_fd >= 0 || taxdb);
@@ -183,7 +200,33 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     //       second one at the same time.  From here on both only READ `res`; the pool shares its workers between their
     //       loops, and the serial stretches of one (offsets, buffer growth, the per-read file's write) run under the
     //       other's loops instead of leaving the workers idle.
-    auto host_stage = [&](kslam_batch_result res, Window win) {
+    // One batch's streams to their files, on the host stage's thread (batch order; not behind the SAM writer's queue).  After
+    // the stage that finishes res.read_pairs: a batch the device left without streams is split here by the host twin, and its
+    // blocks compressed like the device's, so that both routes write the same file.
+    auto write_reads_out = [&](const kslam_batch_result &res, kslam_reads_out &ro, Window win) {
+      if ((ro.flags & KSLAM_READS_OUT_LEFT_TO_HOST) || host_split) {
+        kslam_release_reads_out(ctx, &ro);
+        if (kslam_tail_split_reads(r1 + win.p1, win.e1 - win.p1, paired ? r2 + win.p2 : nullptr, paired ? win.e2 - win.p2 : 0, 0, 1,
+                                   res.read_pairs, res.n_read_pairs, ro_which, &ro) != KSLAM_OK)
+          fail(KSLAM_ERR_ARG, kslam_tail_last_error());
+      }
+      for (int k = 0; k < 4; k++) {
+        if (ro_fds[k] < 0 || !ro.len[k]) continue;
+        bool ok;
+        if (ro_bgzf && !(ro.flags & KSLAM_READS_OUT_BGZF)) {
+          char *z = nullptr;
+          uint64_t zlen = 0;
+          if (kslam_bgzf_compress(ctx, ro.data[k], ro.len[k], &z, &zlen) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+          ok = write_all(ro_fds[k], z, zlen);
+          kslam_free_pinned(ctx, z);
+        } else {
+          if (!ro_bgzf && (ro.flags & KSLAM_READS_OUT_BGZF)) fail(KSLAM_ERR_STATE, "kslam_set_reads_out_bgzf was changed while kslam_stream_classify was running");
+          ok = write_all(ro_fds[k], ro.data[k], ro.len[k]);
+        }
+        if (!ok) fail(KSLAM_ERR_ARG, std::string("writing a reads-out file failed: ") + strerror(errno));
+      }
+    };
+    auto host_stage = [&](kslam_batch_result res, kslam_reads_out ro, Window win) {
       name_thread("kslam-host");
       kslam_reads_view reads = {res.n_reads, nullptr, res.reads_bases_off, nullptr, res.reads_bases_off, res.reads_ids, res.reads_ids_off};
       kslam_status tax_status = KSLAM_OK;
@@ -247,6 +290,10 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       std::string err = s != KSLAM_OK ? g_err : std::string();
       const bool two_threads = P->host_threads != 1;
       if (s == KSLAM_OK && taxdb && two_threads) tax_thread = std::thread([&] { name_thread("kslam-tax"); tax_part(); });
+      if (s == KSLAM_OK && ro_which) {
+        s = guarded([&] { write_reads_out(res, ro, win); });
+        if (s != KSLAM_OK) err = g_err;
+      }
       if (s == KSLAM_OK && writer && (res.text_flags & KSLAM_TEXT_SAM)) {
         s = guarded([&] {   // written on the GPU: the page-locked block joins the writer's queue as it is and goes back to the
                             // context's pool once it is in the file
@@ -319,6 +366,7 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         s = tax_status;
         err = tax_error;
       }
+      kslam_release_reads_out(ctx, &ro);
       kslam_release_batch(ctx, &res);
       if (s != KSLAM_OK && worker_status == KSLAM_OK) {
         worker_status = s;
@@ -355,23 +403,36 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       if (worker.joinable()) worker.join();
       st.seconds_waiting_for_host_stage += (now_ms() - tb) * 1e-3;
       if (cs != KSLAM_OK) fail(cs, kslam_last_error(ctx));
+      kslam_reads_out ro;
+      memset(&ro, 0, sizeof ro);
+      const kslam_status rs = ro_which ? kslam_collect_reads_out(ctx, tk, &ro) : KSLAM_OK;
+      if (rs != KSLAM_OK) {
+        kslam_release_batch(ctx, &res);
+        fail(rs, kslam_last_error(ctx));
+      }
       if (worker_status != KSLAM_OK) {
+        kslam_release_reads_out(ctx, &ro);
         kslam_release_batch(ctx, &res);
         fail(worker_status, worker_error);
       }
       if (res.n_reads == 0) {          // an empty batch ends the loop (src/SLAM.h:207)
+        kslam_release_reads_out(ctx, &ro);
         kslam_release_batch(ctx, &res);
         break;
       }
       if (!res.read_pairs && res.n_overlaps) {
+        kslam_release_reads_out(ctx, &ro);
         kslam_release_batch(ctx, &res);
         fail(KSLAM_ERR_INTERNAL, "the lane returned no device pairing");
       }
-      worker = std::thread(host_stage, res, win);
+      worker = std::thread(host_stage, res, ro, win);
     }
     if (worker.joinable()) worker.join();
     if (worker_status != KSLAM_OK) fail(worker_status, worker_error);
     if (writer && bgzf && kslam_write_queued(writer, KSLAM_BGZF_EOF, KSLAM_BGZF_EOF_LEN) != 0) fail(KSLAM_ERR_ARG, "writing the BGZF EOF marker failed");
+    if (ro_which && ro_bgzf)
+      for (int k = 0; k < 4; k++)
+        if (ro_fds[k] >= 0 && !write_all(ro_fds[k], KSLAM_BGZF_EOF, KSLAM_BGZF_EOF_LEN)) fail(KSLAM_ERR_ARG, "writing a reads-out file's BGZF EOF marker failed");
   });
 
   const double t_close = now_ms();

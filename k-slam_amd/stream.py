@@ -55,9 +55,11 @@ class StreamStats(C.Structure):
 
 
 def classify_stream_native(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_batch, params, taxdb=None, report=None,
-                           sam_fd=-1, per_read_fd=-1, sam_header=None, max_pairs_total=0, depth=0, passes=1, host_threads=0, pool_threads=0):
+                           sam_fd=-1, per_read_fd=-1, sam_header=None, max_pairs_total=0, depth=0, passes=1, host_threads=0, pool_threads=0,
+                           reads_out_fds=None):
     """kslam_stream_classify: the same loop as classify_stream below, inside the library (no Python between the batches).
     Single-end data: params.paired = 0, r2_ptr = None, len2 = 0.
+    reads_out_fds: four descriptors for the classified R1 / R2 and unclassified R1 / R2 records (kslam_amd.readsplit; -1 = not wanted).
     -> dict of the statistics + tax_ids (uint32 array, empty without a taxdb)"""
     L = T.lib()
     L.kslam_stream_classify.argtypes = [C.c_void_p, C.POINTER(T.IndexView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
@@ -66,6 +68,9 @@ def classify_stream_native(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_bat
     P = StreamParams(pairs_per_batch, max_pairs_total, params, sam_fd, per_read_fd, sam_header, len(sam_header) if sam_header else 0,
                      depth, host_threads, pool_threads, passes)
     st, ids, n_ids = StreamStats(), C.c_void_p(), C.c_uint64()
+    if reads_out_fds is not None:
+        from . import readsplit as RS
+        RS.stream_set_reads_out(ctx, reads_out_fds)
     rc = L.kslam_stream_classify(ctx._h, C.byref(index.view), taxdb._h if taxdb is not None else None,
                                  report._h if report is not None else None, r1_ptr, len1, r2_ptr, len2, C.byref(P),
                                  C.byref(ids), C.byref(n_ids), C.byref(st))
@@ -132,7 +137,7 @@ def cut_batches(r1_ptr, len1, r2_ptr, len2, pairs_per_batch, max_pairs_total=0, 
 
 def classify_stream(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_batch, params, taxdb=None, report=None,
                     sam_fd=-1, per_read_fd=-1, sam_header=None, max_pairs_total=0, depth=None, host_threads=0,
-                    on_batch=None, before_batch=None, windows=None):
+                    on_batch=None, before_batch=None, windows=None, reads_out_fds=None):
     """Runs the loop above.  r1_ptr / r2_ptr: ADDRESSES of the two FASTQ texts (page-locked memory from
     kslam_amd.HostBuffer goes up by DMA), index: a kslam_amd.tail index view (e.g. kslam_amd.db.Database),
     params: kslam_amd.tail.TailParams (paired; pseudo_assembly as wanted), taxdb / report: optional
@@ -140,7 +145,10 @@ def classify_stream(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_batch, par
     batches, in order), per-batch statistics and the wall-clock split.
     Test hooks, both called on the host-stage thread: before_batch(k, ov, cg, det, md, rp, pr, pair_stats, reads) sees
     the batch as the GPU returned it (the SAM writer sorts `pr` in place afterwards); on_batch(rec, ov, cg, rp, pr,
-    reads) sees it after the host stage."""
+    reads) sees it after the host stage.
+    reads_out_fds: four descriptors for the classified R1 / R2 and unclassified R1 / R2 records (kslam_amd.readsplit; -1 = not
+    wanted): each batch's streams, cut on the GPU, are written in batch order; a batch the device left to the host is not
+    handled by this loop (KslamError) -- kslam_stream_classify runs the host twin for it."""
     paired = bool(params.paired)
     if not paired and (r2_ptr is not None or len2):
         raise KslamError(2, "classify_stream: single-end data (params.paired == 0) is ONE text: r2_ptr must be None")
@@ -148,6 +156,11 @@ def classify_stream(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_batch, par
     stages = 3 | (4 if params.pseudo_assembly else 0)
     ctx.set_pairing(paired=paired, score_threshold=params.score_threshold, score_fraction=params.score_fraction, stages=stages)
     depth = depth or 3
+    ro_which = 0
+    if reads_out_fds is not None:
+        from . import readsplit as RS
+        ro_which = (1 if reads_out_fds[0] >= 0 or reads_out_fds[1] >= 0 else 0) | (2 if reads_out_fds[2] >= 0 or reads_out_fds[3] >= 0 else 0)
+        RS.set_reads_out(ctx, ro_which)
     # the SAM text leaves through a background writer (kslam_sam_writer): the write of batch k runs under the
     # formatting of batch k + 1
     writer = T.SamWriter(sam_fd) if sam_fd >= 0 else None
@@ -220,8 +233,17 @@ def classify_stream(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_batch, par
             if not queue:
                 break
             ta = time.perf_counter()
-            ov, cg, det, md, release = ctx.collect_batch(queue.pop(0))
+            ticket = queue.pop(0)
+            ov, cg, det, md, release = ctx.collect_batch(ticket)
             pairs, reads = ctx.last_pairs, ctx.last_reads
+            if ro_which:
+                ro = RS.collect_reads_out(ctx, ticket)
+                if ro["flags"] & RS.FLAG_LEFT_TO_HOST:
+                    release()
+                    raise KslamError(4, "classify_stream: the device left this batch's reads split to the host")
+                for fd, block in zip(reads_out_fds, ro["blocks"]):
+                    if fd >= 0 and block:
+                        os.write(fd, block)
             tb = time.perf_counter()
             t_wait_gpu += tb - ta
             if worker is not None:
@@ -249,6 +271,8 @@ def classify_stream(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_batch, par
             ctx.collect_batch(tk)[4]()
         except KslamError:
             pass
+    if ro_which:
+        RS.set_reads_out(ctx, 0)
     ctx.set_pairing(stages=0)
     if writer is not None:
         try:

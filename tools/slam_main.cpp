@@ -33,6 +33,7 @@
 #include "../include/kslam_db.h"
 #include "../include/kslam_inflate.h"
 #include "../include/kslam_samseq.h"
+#include "../include/kslam_readsplit.h"
 #include "../include/kslam_stream.h"
 
 namespace {
@@ -65,7 +66,8 @@ void logl(const std::string &s) { g_log.line(s); }
 }
 
 struct Options {
-  std::string db, out, sam;
+  std::string db, out, sam, classified_out, unclassified_out;
+  bool reads_out_bgzf = false;
   uint32_t score_threshold = 0, match = 2, mismatch = 3, gap_open = 5, gap_extend = 2;
   uint32_t num_reads = UINT32_MAX, num_reads_at_once = 10000000, num_alignments = 10;
   double score_fraction = 0.95;
@@ -113,13 +115,17 @@ void usage(FILE *o) {
         "  --sam-bam                             write --sam-file as BAM (implies --sam-bgzf)\n"
         "  --sam-deflate arg (=fixed)            fixed or dynamic: the Huffman codes of --sam-bgzf / --sam-bam (dynamic: a smaller file)\n"
         "  --sam-seq                             write SEQ and QUAL on the primary rows of --sam-file instead of \"*\"\n"
+        "  --classified-out arg                  write the classified reads (with --just-align: the aligned reads) to this FASTQ file;\n"
+        "                                        with R1FILE and R2FILE arg must contain a '#', replaced by 1 and 2\n"
+        "  --unclassified-out arg                the same for the reads that are not classified\n"
+        "  --reads-out-bgzf                      write those files as BGZF (--sam-deflate applies)\n"
         "\n", o);
 }
 
 Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
-         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_DEFLATE };
+         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -137,6 +143,9 @@ Options parse(int argc, char **argv) {
       {"sam-bam", no_argument, nullptr, SAM_BAM},       // not in the reference: the SAM file as BAM (include/kslam_bam.h)
       {"sam-deflate", required_argument, nullptr, SAM_DEFLATE},   // not in the reference: kslam_set_bgzf_deflate (include/kslam_bgzf.h)
       {"sam-seq", no_argument, nullptr, SAM_SEQ},       // not in the reference: SEQ and QUAL in the SAM file (include/kslam_samseq.h)
+      // not in the reference: the reads themselves, split by outcome (include/kslam_readsplit.h; Kraken 2's option names)
+      {"classified-out", required_argument, nullptr, CLASSIFIED_OUT}, {"unclassified-out", required_argument, nullptr, UNCLASSIFIED_OUT},
+      {"reads-out-bgzf", no_argument, nullptr, READS_OUT_BGZF},
       {nullptr, 0, nullptr, 0}};
   opterr = 0;
   int c;
@@ -166,6 +175,9 @@ Options parse(int argc, char **argv) {
       case SAM_BGZF: o.sam_bgzf = true; break;
       case SAM_BAM: o.sam_bam = true; break;
       case SAM_SEQ: o.sam_seq = true; break;
+      case CLASSIFIED_OUT: o.classified_out = optarg; break;
+      case UNCLASSIFIED_OUT: o.unclassified_out = optarg; break;
+      case READS_OUT_BGZF: o.reads_out_bgzf = true; break;
       case SAM_DEFLATE:
         if (strcmp(optarg, "fixed") != 0 && strcmp(optarg, "dynamic") != 0)
           die(std::string("the argument ('") + optarg + "') for option '--sam-deflate' is invalid");
@@ -183,7 +195,7 @@ Options parse(int argc, char **argv) {
       default: die(std::string("unrecognised option '") + (optind > 0 && optind <= argc ? argv[optind - 1] : "?") + "'");
     }
   }
-  if (o.sam_deflate_given && !o.sam_bgzf && !o.sam_bam) die("option '--sam-deflate' needs '--sam-bgzf' or '--sam-bam'");
+  if (o.sam_deflate_given && !o.sam_bgzf && !o.sam_bam && !o.reads_out_bgzf) die("option '--sam-deflate' needs '--sam-bgzf' or '--sam-bam'");
   return o;
 }
 
@@ -338,6 +350,21 @@ std::string cat(const std::string &a, uint64_t v, const std::string &b) { return
 int run(const Options &o, const std::string &command_line) {
   const std::string r1 = o.inputs[0], r2 = o.inputs.size() > 1 ? o.inputs[1] : std::string();
   const bool paired = !r2.empty(), want_sam = !o.sam.empty();
+  // --classified-out / --unclassified-out: with two input files the name carries a '#' that becomes 1 and 2 (Kraken 2's rule)
+  std::string reads_out_names[4];
+  const bool want_reads_out = !o.classified_out.empty() || !o.unclassified_out.empty();
+  for (int k = 0; k < 2; k++) {
+    const std::string &name = k ? o.unclassified_out : o.classified_out;
+    if (name.empty()) continue;
+    const size_t at = name.find('#');
+    if (paired && at == std::string::npos) {
+      fprintf(stderr, "SLAM: with R1FILE and R2FILE the argument of '--%s' must contain a '#' (replaced by 1 and 2)\n", k ? "unclassified-out" : "classified-out");
+      usage(stderr);
+      exit(1);
+    }
+    reads_out_names[2 * k] = paired ? name.substr(0, at) + "1" + name.substr(at + 1) : name;
+    if (paired) reads_out_names[2 * k + 1] = name.substr(0, at) + "2" + name.substr(at + 1);
+  }
   logl("Performing metagenomic analysis");
   if (o.db.empty()) die("the option '--db' is required but missing");
   // ---- taxDB + database (src/SLAM.h:172-176) ----
@@ -367,7 +394,8 @@ int run(const Options &o, const std::string &command_line) {
   if (kslam_create(&kp, &ctx) != KSLAM_OK) die(std::string("GPU context: ") + (ctx ? kslam_last_error(ctx) : "kslam_create failed"));
   if (o.sam_bgzf && want_sam && kslam_set_sam_bgzf(ctx, 1) != KSLAM_OK) die(std::string("BGZF: ") + kslam_last_error(ctx));
   if (o.sam_bam && want_sam && kslam_set_sam_bam(ctx, 1) != KSLAM_OK) die(std::string("BAM: ") + kslam_last_error(ctx));
-  if (want_sam && kslam_set_bgzf_deflate(ctx, o.sam_deflate) != KSLAM_OK) die(std::string("BGZF: ") + kslam_last_error(ctx));
+  if (o.reads_out_bgzf && want_reads_out && kslam_set_reads_out_bgzf(ctx, 1) != KSLAM_OK) die(std::string("reads out: ") + kslam_last_error(ctx));
+  if ((want_sam || (want_reads_out && o.reads_out_bgzf)) && kslam_set_bgzf_deflate(ctx, o.sam_deflate) != KSLAM_OK) die(std::string("BGZF: ") + kslam_last_error(ctx));
   if (o.sam_seq && want_sam && kslam_set_sam_seq(ctx, 1) != KSLAM_OK) die(std::string("SEQ: ") + kslam_last_error(ctx));
   logl("Getting k-mers from index");
   if (kslam_set_index(ctx, index->n_entries, kslam_db_entry_bases(db), kslam_db_entry_lengths(db)) != KSLAM_OK)
@@ -397,6 +425,13 @@ int run(const Options &o, const std::string &command_line) {
     if (per_read_fd < 0) die("unable to open " + o.out + "_PerRead");
     if (kslam_taxreport_create(&report) != KSLAM_OK) die(kslam_tail_last_error());
   }
+  int reads_out_fds[4] = {-1, -1, -1, -1};
+  for (int k = 0; k < 4; k++) {
+    if (reads_out_names[k].empty()) continue;
+    reads_out_fds[k] = open(reads_out_names[k].c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (reads_out_fds[k] < 0) die("unable to open " + reads_out_names[k]);
+  }
+  if (want_reads_out && kslam_stream_set_reads_out(ctx, reads_out_fds) != KSLAM_OK) die(std::string("reads out: ") + kslam_last_error(ctx));
   kslam_stream_params sp;
   memset(&sp, 0, sizeof sp);
   sp.pairs_per_batch = o.num_reads_at_once;
@@ -437,6 +472,8 @@ int run(const Options &o, const std::string &command_line) {
   if (sam_fd >= 0 && (o.sam_bgzf || o.sam_bam) && fstat(sam_fd, &sam_stat) == 0) sam_file_bytes = (uint64_t)sam_stat.st_size;   // compressed
   if (sam_fd >= 0) close(sam_fd);
   if (per_read_fd >= 0) close(per_read_fd);
+  for (int fd : reads_out_fds)
+    if (fd >= 0 && close(fd) != 0) die("closing a reads-out file failed");
   logl(cat("Found ", st.n_overlaps, " k-mer overlaps"));
   logl(cat("", st.n_read_pairs_aligned, " entries have k-mer overlaps"));
   if (paired && st.n_batches) logl(cat("Screening all alignment pairs with insert size >= ", st.first_max_insert_size, ""));
