@@ -90,6 +90,7 @@ void run_extract(kslam_ctx *c, const uint8_t *d_bases, const uint64_t *d_off, ui
 std::shared_ptr<GenomeIndex> new_index(kslam_ctx *c, uint64_t n_entries) {
   c->index.reset();
   for (auto *l : c->lanes) l->c->index.reset();
+  coverage_release(c);   // (include/kslam_coverage.h) the table was laid out for the old index's entries
   auto ix = std::make_shared<GenomeIndex>();
   ix->n_entries = n_entries;
   ix->h_goff.assign(n_entries + 1, 0);

@@ -215,6 +215,11 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
         });
       }
     }
+    // (kslam_set_coverage) the batch's final alignment pairs into the owner's coverage table: bit and counter atomics on this
+    // lane's stream, outside the compute token like the split above.  A batch whose pseudo-assembly is left to the host goes
+    // in through kslam_coverage_add after the host stage.
+    if (primary->cov.on.load(std::memory_order_acquire) && st == KSLAM_OK && primary->pairing.stages && !pseudo_left && c->have_pairs)
+      st = guarded(c, [&] { coverage_mark_resident(primary, c); });
     t3 = now();
     // with the SAM records written on the device the host has no use for the rows, the CIGAR pool, the per-row details and
     // the MD text (0.7 GB per batch of configs[1]): they stay where they are, only their counts travel

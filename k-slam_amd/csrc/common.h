@@ -643,4 +643,34 @@ struct ReadSplitWork {
 void read_split_device(const FqStream st[2], bool single, const kslam_read_pair *d_groups, uint64_t n_groups, uint32_t which,
                        ReadSplitWork &W, uint64_t bytes[4], uint64_t n_records[2], hipStream_t s);
 
+// ------------------------------------------------------------ coverage.hip
+// The per-entry coverage table (include/kslam_coverage.h).  CoverageState belongs to the context the switch was set on; its
+// lanes mark into it from their own streams (every update a device-scope atomic), each with a CoverageMarkWork of its own.
+struct CoverageTable {            // what the kernels see
+  unsigned long long *bitmap;    // one bit per base; entry e's words start at word_off[e]
+  unsigned long long *rows;      // 4 per entry: alignments, unique_read_pairs, aligned_bases, covered_bases
+  unsigned long long *skipped;   // mates that contributed nothing
+  const uint64_t *word_off;      // [n_entries + 1]
+  const uint64_t *g_off;         // [n_entries + 1]: the index's entry offsets (lengths)
+  uint64_t n_entries, n_words;
+};
+struct CoverageMarkWork {
+  DevBuf gflag;                  // per read pair: bit 0 = a live record's entry differs from the first record's
+  hipEvent_t ev[2]{};            // around the mark launches
+  float ms = 0;                  // their device time, last batch
+  CoverageMarkWork() = default;
+  CoverageMarkWork(const CoverageMarkWork &) = delete;
+  CoverageMarkWork &operator=(const CoverageMarkWork &) = delete;
+  ~CoverageMarkWork() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+constexpr int COV_MARK_BLOCK = 256;   // threads per workgroup of the mark pass (one alignment-pair record each)
+// one batch into the table: d_ov the overlap records d_pairs' r1 / r2 index; waits for the stream (the events are read)
+void coverage_mark_device(const kslam_overlap *d_ov, uint64_t n_ov, const kslam_read_pair *d_groups, uint64_t n_groups,
+                          const kslam_paired_overlap *d_pairs, uint64_t n_pairs, const CoverageTable &T, CoverageMarkWork &W, hipStream_t s);
+// covered_bases of every row, counted from the bitmap (the column is cleared first); ev: two events around the launches
+void coverage_count_device(const CoverageTable &T, hipEvent_t ev[2], hipStream_t s);
+
 }  // namespace kslam

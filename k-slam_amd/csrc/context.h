@@ -20,9 +20,11 @@
 #include "../../include/kslam_bam.h"
 #include "../../include/kslam_samseq.h"
 #include "../../include/kslam_readsplit.h"
+#include "../../include/kslam_coverage.h"
 #include "../host/workers.hpp"
 #include "../host/inflate.hpp"
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -132,6 +134,19 @@ struct kslam_ctx {
   struct { uint32_t which = 0; bool bgzf = false; int fds[4] = {-1, -1, -1, -1}; } reads_out;   // for the lanes; fds: kslam_stream_set_reads_out
   struct ReadsOutEntry { bool supported = false; kslam_reads_out out{}; };
   std::map<uint64_t, ReadsOutEntry> ro_ready;   // by ticket: collected batches whose streams kslam_collect_reads_out has not taken (under as_mu)
+
+  // ---- the per-entry coverage table (coverage.hip, include/kslam_coverage.h) ----
+  struct Coverage {               // on the context the switch was set on; its lanes mark into it (lane_main)
+    std::atomic<bool> on{false};
+    uint64_t n_entries = 0, n_words = 0;
+    DevBuf bitmap, rows, skipped, word_off;
+    DevBuf up_ov, up_groups, up_pairs;   // kslam_coverage_add's uploads
+    hipEvent_t ev_count[2]{};
+    double count_ms = 0;
+    int stream_fd = -1;           // kslam_stream_set_coverage
+    std::mutex mu;                // add / take / reset / bitmap / the switch: one at a time
+  } cov;
+  CoverageMarkWork covw;          // this context's own mark passes (a lane's batches; on the primary: kslam_coverage_add)
 
   // ---- device pairing / screens (pairs.hip) ----
   PairWork pw;
@@ -290,6 +305,12 @@ void stop_lanes(kslam_ctx *c);
 void split_resident(kslam_ctx *c, bool single, const kslam_read_pair *d_groups, uint64_t n_groups, uint32_t which, bool bgzf, int deflate,
                     kslam_reads_out *out);
 void free_reads_out(kslam_ctx *c, kslam_reads_out *out);
+
+// ---- api_coverage.hip
+// frees the coverage state of c and switches it off (kslam_set_coverage(c, 0), kslam_set_index)
+void coverage_release(kslam_ctx *c);
+// the batch `lane` has just finished (lane->pres over lane->res_ov) into owner's table, on lane's stream
+void coverage_mark_resident(kslam_ctx *owner, kslam_ctx *lane);
 
 }  // namespace kslam_api
 

@@ -25,6 +25,7 @@
 #include "../../include/kslam_bam.h"
 #include "../../include/kslam_samseq.h"
 #include "../../include/kslam_readsplit.h"
+#include "../../include/kslam_coverage.h"
 #include "workers.hpp"
 
 namespace {
@@ -67,6 +68,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
   int ro_fds[4] = {-1, -1, -1, -1};   // kslam_stream_set_reads_out: where the classified / unclassified records go
   uint32_t ro_which = 0;
   int ro_bgzf = 0;
+  int cov_fd = -1;                    // kslam_stream_set_coverage: where the coverage report goes
+  bool coverage_set = false;
 
   const int pool_cap = P && P->pool_threads ? (int)P->pool_threads : std::max(2, usable_cpus() - 4);
   Pool::get().add_cap(pool_cap);
@@ -88,6 +91,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     }
     if (text_set) kslam_set_sam_text(ctx, 0, 0, 10, 0);
     if (reads_out_set) kslam_set_reads_out(ctx, 0);
+    if (coverage_set) kslam_set_coverage(ctx, 0);
+    if (ctx) kslam_stream_set_coverage(ctx, -1);          // held for this call alone, like the descriptors below
     if (ctx) kslam_stream_set_reads_out(ctx, nullptr);   // the descriptors held for this call alone
     if (pairing_set) kslam_set_pairing(ctx, 1, 0, 0.95, 0);
     Pool::get().remove_cap(pool_cap);
@@ -116,6 +121,13 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       if (kslam_set_reads_out(ctx, ro_which) != KSLAM_OK || kslam_get_reads_out_bgzf(ctx, &ro_bgzf) != KSLAM_OK)
         fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
       reads_out_set = true;
+    }
+    // the per-entry coverage table (include/kslam_coverage.h): the lanes mark what they finish; the report follows the last batch
+    if (kslam_stream_get_coverage(ctx, &cov_fd) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    if (cov_fd >= 0) {
+      if (kslam_set_coverage(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
+      coverage_set = true;
+      if (kslam_coverage_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
     }
     const bool host_split = getenv("KSLAM_HOST_SAM_TEXT") && getenv("KSLAM_HOST_SAM_TEXT")[0] == '1';   // (A/B: the host twin for every batch)
     // the SAM records and the per-read lines written on the GPU (include/kslam_samtext.h); KSLAM_HOST_SAM_TEXT=1 keeps the
@@ -294,6 +306,14 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         s = guarded([&] { write_reads_out(res, ro, win); });
         if (s != KSLAM_OK) err = g_err;
       }
+      // coverage: the lane marked the batch unless its pseudo-assembly was left to this stage, which has just finished its read pairs
+      if (s == KSLAM_OK && coverage_set && P->tail.pseudo_assembly && !(res.pair_stats.stages_done & KSLAM_TAIL_PSEUDO_ASM)) {
+        s = guarded([&] {
+          if (kslam_coverage_add(ctx, res.overlaps, res.n_overlaps, res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK)
+            fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+        });
+        if (s != KSLAM_OK) err = g_err;
+      }
       if (s == KSLAM_OK && writer && (res.text_flags & KSLAM_TEXT_SAM)) {
         s = guarded([&] {   // written on the GPU: the page-locked block joins the writer's queue as it is and goes back to the
                             // context's pool once it is in the file
@@ -433,6 +453,14 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     if (ro_which && ro_bgzf)
       for (int k = 0; k < 4; k++)
         if (ro_fds[k] >= 0 && !write_all(ro_fds[k], KSLAM_BGZF_EOF, KSLAM_BGZF_EOF_LEN)) fail(KSLAM_ERR_ARG, "writing a reads-out file's BGZF EOF marker failed");
+    if (coverage_set) {
+      kslam_entry_coverage *rows = nullptr;
+      uint64_t n_rows = 0, n_skipped = 0;
+      if (kslam_coverage_take(ctx, &rows, &n_rows, &n_skipped) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      const kslam_status w = kslam_coverage_write(index, rows, n_rows, cov_fd);
+      kslam_free_pinned(ctx, rows);
+      if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
+    }
   });
 
   const double t_close = now_ms();

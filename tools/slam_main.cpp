@@ -34,6 +34,7 @@
 #include "../include/kslam_inflate.h"
 #include "../include/kslam_samseq.h"
 #include "../include/kslam_readsplit.h"
+#include "../include/kslam_coverage.h"
 #include "../include/kslam_stream.h"
 
 namespace {
@@ -66,7 +67,7 @@ void logl(const std::string &s) { g_log.line(s); }
 }
 
 struct Options {
-  std::string db, out, sam, classified_out, unclassified_out;
+  std::string db, out, sam, classified_out, unclassified_out, coverage_out;
   bool reads_out_bgzf = false;
   uint32_t score_threshold = 0, match = 2, mismatch = 3, gap_open = 5, gap_extend = 2;
   uint32_t num_reads = UINT32_MAX, num_reads_at_once = 10000000, num_alignments = 10;
@@ -119,13 +120,15 @@ void usage(FILE *o) {
         "                                        with R1FILE and R2FILE arg must contain a '#', replaced by 1 and 2\n"
         "  --unclassified-out arg                the same for the reads that are not classified\n"
         "  --reads-out-bgzf                      write those files as BGZF (--sam-deflate applies)\n"
+        "  --coverage-out arg                    write a per-entry coverage table to this file: alignments, unique read pairs,\n"
+        "                                        aligned and covered bases, breadth and mean depth (works with --just-align)\n"
         "\n", o);
 }
 
 Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
-         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF };
+         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -146,6 +149,7 @@ Options parse(int argc, char **argv) {
       // not in the reference: the reads themselves, split by outcome (include/kslam_readsplit.h; Kraken 2's option names)
       {"classified-out", required_argument, nullptr, CLASSIFIED_OUT}, {"unclassified-out", required_argument, nullptr, UNCLASSIFIED_OUT},
       {"reads-out-bgzf", no_argument, nullptr, READS_OUT_BGZF},
+      {"coverage-out", required_argument, nullptr, COVERAGE_OUT},   // not in the reference: include/kslam_coverage.h
       {nullptr, 0, nullptr, 0}};
   opterr = 0;
   int c;
@@ -178,6 +182,7 @@ Options parse(int argc, char **argv) {
       case CLASSIFIED_OUT: o.classified_out = optarg; break;
       case UNCLASSIFIED_OUT: o.unclassified_out = optarg; break;
       case READS_OUT_BGZF: o.reads_out_bgzf = true; break;
+      case COVERAGE_OUT: o.coverage_out = optarg; break;
       case SAM_DEFLATE:
         if (strcmp(optarg, "fixed") != 0 && strcmp(optarg, "dynamic") != 0)
           die(std::string("the argument ('") + optarg + "') for option '--sam-deflate' is invalid");
@@ -432,6 +437,12 @@ int run(const Options &o, const std::string &command_line) {
     if (reads_out_fds[k] < 0) die("unable to open " + reads_out_names[k]);
   }
   if (want_reads_out && kslam_stream_set_reads_out(ctx, reads_out_fds) != KSLAM_OK) die(std::string("reads out: ") + kslam_last_error(ctx));
+  int coverage_fd = -1;
+  if (!o.coverage_out.empty()) {
+    coverage_fd = open(o.coverage_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (coverage_fd < 0) die("unable to open " + o.coverage_out);
+    if (kslam_stream_set_coverage(ctx, coverage_fd) != KSLAM_OK) die(std::string("coverage: ") + kslam_last_error(ctx));
+  }
   kslam_stream_params sp;
   memset(&sp, 0, sizeof sp);
   sp.pairs_per_batch = o.num_reads_at_once;
@@ -474,6 +485,7 @@ int run(const Options &o, const std::string &command_line) {
   if (per_read_fd >= 0) close(per_read_fd);
   for (int fd : reads_out_fds)
     if (fd >= 0 && close(fd) != 0) die("closing a reads-out file failed");
+  if (coverage_fd >= 0 && close(coverage_fd) != 0) die("closing the coverage file failed");
   logl(cat("Found ", st.n_overlaps, " k-mer overlaps"));
   logl(cat("", st.n_read_pairs_aligned, " entries have k-mer overlaps"));
   if (paired && st.n_batches) logl(cat("Screening all alignment pairs with insert size >= ", st.first_max_insert_size, ""));
