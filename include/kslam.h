@@ -238,6 +238,10 @@ typedef struct {
 } kslam_row_detail;
 kslam_status kslam_load_qualities(kslam_ctx *ctx, const char *concat_quality);
 kslam_status kslam_load_qualities_device(kslam_ctx *ctx, const void *d_concat_quality);
+/* The walk reads the entry bases of every record that has a CIGAR.  On a context without an index
+ * (kslam_set_index never called: one that only took rows through kslam_adopt_results_device) both forms
+ * return KSLAM_ERR_STATE, naming kslam_set_index, when the result's CIGAR pool is not empty; nothing is
+ * launched.  A result without any CIGAR needs no index: every record comes back zero, with no MD text. */
 kslam_status kslam_row_details(kslam_ctx *ctx, uint64_t *n_md);
 /* the same after kslam_pair_screen, for the overlap records its surviving alignment pairs refer to only (what the
  * SAM writer will ask for: about a third of the rows); the other rows' records are zero and have no MD text.

@@ -31,10 +31,12 @@ void sam_stage_plan(kslam_ctx *c, const kslam_ctx *owner, int paired, uint32_t n
   if (!owner->have_annot) throw StatusError{KSLAM_ERR_STATE, "kslam_set_sam_annotations has not been called"};
   if (owner->annot.n_entries != c->need_index().n_entries) throw StatusError{KSLAM_ERR_STATE, "the annotations belong to another index"};
   if (!c->have_ids) throw StatusError{KSLAM_ERR_STATE, "the batch has no read identifiers on the device (kslam_load_read_ids)"};
-  if (c->prm.report_cigar && c->n_cig && !c->have_details)
+  // rows that carry CIGARs are walked whether or not the CIGAR column is reported: NM and the mapping qualities come from
+  // the walk (src/SAM.h:298, 343-346); a context that aligns without report_cigar has none, adopted rows may
+  if (c->n_cig && !c->have_details)
     throw StatusError{KSLAM_ERR_STATE, "kslam_row_details_of_pairs has not been called for this result"};
   S.in.ov = c->res_ov.as<kslam_overlap>();
-  S.in.pool = (c->prm.report_cigar && c->n_cig) ? c->res_cig.as<uint32_t>() : nullptr;
+  S.in.pool = c->n_cig ? c->res_cig.as<uint32_t>() : nullptr;
   S.in.det = c->have_details ? c->res_det.as<kslam_row_detail>() : nullptr;
   S.in.md_pool = c->d_md_pool;
   S.in.ids = c->d_ids;
@@ -211,6 +213,9 @@ static kslam_status row_details_impl(kslam_ctx *c, uint64_t *n_md, bool of_pairs
     if (of_pairs && !(c->have_pairs && c->pairs_of_result))
       throw StatusError{KSLAM_ERR_STATE, "kslam_pair_screen has not been called for this result (pairs of records handed "
                                          "in through kslam_pair_screen_overlaps do not refer to its rows)"};
+    // the walk reads the entry bases of every row that has a CIGAR: a context that only adopted rows may have no index
+    if (!c->index.get() && c->n_cig != 0)
+      throw StatusError{KSLAM_ERR_STATE, "kslam_set_index first: the adopted result holds CIGARs, and their walk reads the entry bases"};
     if (!c->d_tables.p) {
       // matchTable / misMatchTable of src/SAM.h:33-48, with the host's libm (the values the host tail uses)
       double t[200];

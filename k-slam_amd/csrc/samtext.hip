@@ -413,13 +413,14 @@ __device__ inline void put_line(Sink &o, const SamInputs &in, const SamAnnot &A,
     LIT(o, "\t*\t*");
   }
   if (r.mapped) {
-    uint32_t nm = 0;
+    // NM is the walk's whether or not CIGAR and MD are reported (src/SAM.h:298)
+    const bool was_walked = walked(in, r.ov);
+    const uint32_t nm = was_walked ? in.det[r.ov].nm : 0u;
     if (P.report_cigar) {
       LIT(o, "\tMD:Z:");
-      if (walked(in, r.ov)) {
+      if (was_walked) {
         const kslam_row_detail &d = in.det[r.ov];
         o.bytes(in.md_pool + d.md_off, d.md_len);
-        nm = d.nm;
       }
     }
     LIT(o, "\tAS:i:");
@@ -524,13 +525,13 @@ __device__ inline void record_body(Sink &o, const SamInputs &in, const SamAnnot 
   }
   if (seq) put_seq_bam(o, sc);
   if (r.mapped) {
-    uint32_t nm = 0;
+    const bool was_walked = walked(in, r.ov);
+    const uint32_t nm = was_walked ? in.det[r.ov].nm : 0u;
     if (P.report_cigar) {
       LIT(o, "MDZ");
-      if (walked(in, r.ov)) {
+      if (was_walked) {
         const kslam_row_detail &d = in.det[r.ov];
         o.bytes(in.md_pool + d.md_off, d.md_len);
-        nm = d.nm;
       }
       o.ch(0);
     }

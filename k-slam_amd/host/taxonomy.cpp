@@ -337,7 +337,7 @@ kslam_status kslam_tail_classify(const kslam_tail_params *params, const kslam_re
                                  const kslam_paired_overlap *pairs, uint64_t n_pairs, uint32_t *tax_ids,
                                  char **per_read_text, uint64_t *per_read_len) {
   return guarded([&] {
-    if (!params || !reads || !index || !db || !tax_ids || (n_read_pairs && (!read_pairs || !pairs)))
+    if (!params || !reads || !index || !db || !tax_ids || (n_read_pairs && !read_pairs) || (n_pairs && !pairs))   // (read pairs may all have lost their records)
       fail(KSLAM_ERR_ARG, "null argument");
     if (!index->taxonomy_id) fail(KSLAM_ERR_ARG, "index view needs taxonomy_id");
     if (per_read_text && (!per_read_len || !reads->ids || !reads->ids_off))
