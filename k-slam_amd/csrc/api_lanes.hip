@@ -183,6 +183,7 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
       const bool bgzf = primary->samtext.sam && (primary->samtext.bgzf || bam);
       sam.bam = bam;
       sam.seq = primary->samtext.sam && primary->samtext.seq;   // (kslam_set_sam_seq) SEQ and QUAL on the primary rows
+      sam.unmapped = primary->samtext.sam && primary->samtext.unmapped;   // (kslam_set_sam_unmapped) rows for the reads without alignment
       st = guarded(c, [&] {
         sam_stage_kernels(c, primary, sam, primary->samtext.sam, primary->samtext.per_read);
         if (bgzf) {
@@ -198,7 +199,9 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
         });
       if (st == KSLAM_OK)
         job->text_flags = (primary->samtext.sam ? (KSLAM_TEXT_PAIRS_SORTED | KSLAM_TEXT_SAM) : 0u) | (primary->samtext.per_read ? KSLAM_TEXT_PER_READ : 0u) |
-                          (bgzf ? KSLAM_TEXT_SAM_BGZF : 0u) | (bam ? KSLAM_TEXT_SAM_BAM : 0u) | (sam.seq ? KSLAM_TEXT_SAM_SEQ : 0u);
+                          (bgzf ? KSLAM_TEXT_SAM_BGZF : 0u) | (bam ? KSLAM_TEXT_SAM_BAM : 0u) | (sam.seq ? KSLAM_TEXT_SAM_SEQ : 0u) |
+                          (sam.unmapped ? KSLAM_TEXT_SAM_UNMAPPED : 0u);
+      if (st == KSLAM_OK && sam.unmapped) unmapped_note(primary, c);
     }
     sam_stage_free(c, sam);
     // (kslam_set_reads_out) the records split by outcome, cut out of the text this lane uploaded.  Outside the compute token as

@@ -105,8 +105,24 @@ void sam_stage_kernels(kslam_ctx *c, const kslam_ctx *owner, SamStage &S, bool w
       sq.bases = c->r_bases.as<uint8_t>();
       sq.qual = c->have_qual ? c->r_qual.as<uint8_t>() : nullptr;
     }
+    // (kslam_set_sam_unmapped) the rows of the reads without alignment: their lengths first, so that the text buffer is sized
+    // once from both totals, then the mapped rows, then these directly behind them
+    const bool paired = S.P.paired != 0;
+    const uint64_t n_records = paired ? c->n_reads / 2 : c->n_reads;
+    uint64_t unmapped_bytes = 0;
+    uint32_t bad_unmapped = 0xFFFFFFFFu;
+    if (S.unmapped) {
+      if (!c->have_reads) throw StatusError{KSLAM_ERR_STATE, "no resident read batch to take the reads without alignment from"};
+      sam_unmapped_plan(S.d_groups, c->samw.plan.as<SamPlan>(), S.n_groups, n_records, paired, S.in, S.bam, S.seq ? &sq : nullptr, c->sumw,
+                        &unmapped_bytes, &bad_unmapped, s);
+    }
     sam_format(S.d_recs, S.d_groups, S.n_groups, S.in, owner->annot, S.P, c->samw, &S.text_bytes, s, S.bam, &bad_read,
-               S.seq ? &sq : nullptr);
+               S.seq ? &sq : nullptr, unmapped_bytes, bad_unmapped != 0xFFFFFFFFu);   // (a refusal there: this one's lengths alone)
+    bad_read = std::min(bad_read, bad_unmapped);   // the lowest read across both writers
+    if (S.unmapped && bad_read == 0xFFFFFFFFu) {
+      sam_unmapped_write(n_records, paired, S.in, S.bam, S.seq ? &sq : nullptr, c->sumw, c->samw.text.as<uint8_t>() + S.text_bytes, s);
+      S.text_bytes += unmapped_bytes;
+    }
     if (bad_read != 0xFFFFFFFFu) {   // BAM: an id longer than l_read_name can say; name it
       uint64_t off[2];
       read_back(off, S.in.ids_off + bad_read, sizeof off, s);
@@ -122,6 +138,7 @@ void sam_stage_kernels(kslam_ctx *c, const kslam_ctx *owner, SamStage &S, bool w
     per_read_device(S.d_recs, S.d_groups, S.n_groups, S.in, owner->annot, c->samw, &S.pr_bytes, s);
   }
   HIPCHK(stream_wait(s));
+  if (want_sam && S.unmapped) sam_unmapped_timing(c->sumw);
 }
 // ... and everything copied to page-locked memory (outside the lanes' compute token: the copy engine's work)
 void sam_stage_fetch(kslam_ctx *c, SamStage &S, bool want_sam, bool want_per_read, char **sam_text, uint64_t *sam_len, char **pr_text,
@@ -154,6 +171,14 @@ void sam_stage_fetch(kslam_ctx *c, SamStage &S, bool want_sam, bool want_per_rea
   if (pr_len) *pr_len = pr_bytes;
   if (tax) *tax = hx; else if (hx) pinned_put(c, hx);
   if (n_tax) *n_tax = want_per_read ? S.n_groups : 0;
+}
+
+// the batch `lane` has just formatted, for the owner's kslam_sam_unmapped_kernel_ms
+void unmapped_note(kslam_ctx *owner, const kslam_ctx *lane) {
+  std::lock_guard<std::mutex> lk(owner->as_mu);
+  owner->unmapped_last.ms = lane->sumw.kernel_ms;
+  owner->unmapped_last.bytes = lane->sumw.bytes;
+  owner->unmapped_last.n_rows = lane->sumw.n_rows;
 }
 
 template <typename T>
@@ -497,10 +522,12 @@ kslam_status kslam_sam_text(kslam_ctx *c, int paired, uint32_t num_alignments, i
     if (sam_text && !sam_len) throw StatusError{KSLAM_ERR_ARG, "sam_text without sam_len"};
     if ((per_read_text && !per_read_len) || (tax_ids && !n_tax_ids)) throw StatusError{KSLAM_ERR_ARG, "an output without its length"};
     S.seq = c->samtext.seq;
+    S.unmapped = c->samtext.unmapped;
     sam_stage_plan(c, c, paired, num_alignments, sam_xa, sam_text != nullptr, S);
     sam_stage_mapq(S);
     const bool want_sam = sam_text != nullptr, want_pr = per_read_text != nullptr || tax_ids != nullptr;
     sam_stage_kernels(c, c, S, want_sam, want_pr);
+    if (want_sam && S.unmapped) unmapped_note(c, c);
     sam_stage_fetch(c, S, want_sam, want_pr, sam_text, sam_len, per_read_text, per_read_len, tax_ids, n_tax_ids);
   });
   if (c) sam_stage_free(c, S);
@@ -670,6 +697,29 @@ kslam_status kslam_get_sam_seq(kslam_ctx *c, int *on) {
   return KSLAM_OK;
 }
 
+// ---- rows for the reads without alignment (include/kslam_samunmapped.h; samunmapped.hip) ----
+kslam_status kslam_set_sam_unmapped(kslam_ctx *c, int on) {
+  return guarded(c, [&] {
+    if (c->in_multi) throw StatusError{KSLAM_ERR_UNSUPPORTED, "rows for unaligned reads are not available on the contexts of a kslam_multi"};
+    c->samtext.unmapped = on != 0;
+  });
+}
+
+kslam_status kslam_get_sam_unmapped(kslam_ctx *c, int *on) {
+  if (!c || !on) return KSLAM_ERR_ARG;
+  *on = c->samtext.unmapped ? 1 : 0;
+  return KSLAM_OK;
+}
+
+kslam_status kslam_sam_unmapped_kernel_ms(kslam_ctx *c, double *ms, uint64_t *bytes_written, uint64_t *n_rows) {
+  if (!c || !ms || !bytes_written || !n_rows) return KSLAM_ERR_ARG;
+  std::lock_guard<std::mutex> lk(c->as_mu);
+  *ms = c->unmapped_last.ms;
+  *bytes_written = c->unmapped_last.bytes;
+  *n_rows = c->unmapped_last.n_rows;
+  return KSLAM_OK;
+}
+
 kslam_status kslam_sam_bam(kslam_ctx *c, int paired, uint32_t num_alignments, int sam_xa, char **bam, uint64_t *len) {
   if (bam) *bam = nullptr;
   if (len) *len = 0;
@@ -678,9 +728,11 @@ kslam_status kslam_sam_bam(kslam_ctx *c, int paired, uint32_t num_alignments, in
     if (!bam || !len) throw StatusError{KSLAM_ERR_ARG, "null argument"};
     S.bam = true;
     S.seq = c->samtext.seq;
+    S.unmapped = c->samtext.unmapped;
     sam_stage_plan(c, c, paired, num_alignments, sam_xa, true, S);
     sam_stage_mapq(S);
     sam_stage_kernels(c, c, S, true, false);
+    if (S.unmapped) unmapped_note(c, c);
     sam_stage_fetch(c, S, true, false, bam, len, nullptr, nullptr, nullptr, nullptr);
   });
   if (c) sam_stage_free(c, S);

@@ -19,6 +19,7 @@
 #include "../../include/kslam_inflate.h"
 #include "../../include/kslam_bam.h"
 #include "../../include/kslam_samseq.h"
+#include "../../include/kslam_samunmapped.h"
 #include "../../include/kslam_readsplit.h"
 #include "../../include/kslam_coverage.h"
 #include "../host/workers.hpp"
@@ -117,8 +118,12 @@ struct kslam_ctx {
   std::vector<DevBuf> annot_bufs;
   bool have_annot = false;
   SamWork samw;
-  struct { bool sam = false, per_read = false, bgzf = false, bam = false, seq = false; uint32_t num_alignments = 10; int sam_xa = 0;
+  struct { bool sam = false, per_read = false, bgzf = false, bam = false, seq = false, unmapped = false; uint32_t num_alignments = 10; int sam_xa = 0;
            int deflate = KSLAM_BGZF_DEFLATE_FIXED; } samtext;   // for the lanes; deflate: kslam_set_bgzf_deflate, also for kslam_bgzf_compress
+  // the rows of the reads without alignment (samunmapped.hip, include/kslam_samunmapped.h): this context's own passes, and what
+  // kslam_sam_unmapped_kernel_ms reports -- the last batch formatted here or on one of this context's lanes (under as_mu)
+  SamUnmappedWork sumw;
+  struct { double ms = 0; uint64_t bytes = 0, n_rows = 0; } unmapped_last;
   const uint8_t *d_ids = nullptr;       // read identifiers of the loaded batch (fqw.ids, or ids_buf)
   const uint64_t *d_ids_off = nullptr;
   DevBuf ids_buf, ids_off_buf;
@@ -283,6 +288,7 @@ struct SamStage {   // one batch's way through the stage
   const void *d_sam = nullptr;    // where sam_stage_fetch copies the SAM bytes from (nullptr: samw.text)
   bool bam = false;               // BAM records instead of SAM lines (include/kslam_bam.h)
   bool seq = false;               // SEQ and QUAL on the rows without flag 0x100 (include/kslam_samseq.h)
+  bool unmapped = false;          // rows for the reads without alignment behind the others (include/kslam_samunmapped.h)
   double *h_vals = nullptr;       // pinned
   uint32_t *h_seg = nullptr;      // pinned
   uint8_t *h_mapq = nullptr;      // pinned
@@ -296,6 +302,7 @@ void sam_stage_kernels(kslam_ctx *c, const kslam_ctx *owner, SamStage &S, bool w
 void sam_stage_fetch(kslam_ctx *c, SamStage &S, bool want_sam, bool want_per_read, char **sam_text, uint64_t *sam_len, char **pr_text,
                      uint64_t *pr_len, uint32_t **tax, uint64_t *n_tax);
 void fill_pair_stats(const PairResult &r, kslam_pair_stats *st);
+void unmapped_note(kslam_ctx *owner, const kslam_ctx *lane);
 
 // ---- api_lanes.hip
 void stop_lanes(kslam_ctx *c);

@@ -52,6 +52,21 @@ struct SamWork {
   DevBuf tax_ids, pr_len, pr_off, pr_text;
 };
 
+struct SamUnmappedWork {   // samunmapped.hip: the rows of the reads without alignment (include/kslam_samunmapped.h)
+  DevBuf has_row, len, off, scan_tmp, totals;
+  hipEvent_t ev[4]{};          // around the flag + length + scan launches, and around the write launch
+  float kernel_ms = 0;         // their device time, last batch (tools/samunmapped_bench.py)
+  uint64_t bytes = 0, n_rows = 0;   // what the last batch's rows came to
+  bool write_pending = false;  // the write pass's time has not been read yet
+  SamUnmappedWork() = default;
+  SamUnmappedWork(const SamUnmappedWork &) = delete;
+  SamUnmappedWork &operator=(const SamUnmappedWork &) = delete;
+  ~SamUnmappedWork() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 // First half: sorts every read pair's alignment pairs IN PLACE (the reference's per-pair std::sort), plans the rows and
 // compacts the log-probabilities the host must turn into mapping qualities: W.vals (double, n_vals), W.seg_len (u32, n_segs).
 // err_flags: bits of kslam_row_detail.flags met on a row that is reported (2) or whose probability matters (1).
@@ -61,9 +76,23 @@ void sam_plan(kslam_paired_overlap *d_recs, const kslam_read_pair *d_groups, uin
 // (include/kslam_bam.h) instead of SAM lines; when a read id is too long for one, *bad_read = the lowest such read,
 // *text_bytes = 0 and nothing is written (otherwise *bad_read = 0xFFFFFFFF).  seq: not nullptr = the rows without flag
 // 0x100 carry SEQ and QUAL from these columns (their own kernel instantiations; nullptr runs the ones without).
+// room_behind: bytes W.text is to hold behind the rows (sam_unmapped_write's), so that the buffer is sized once, from both totals.
+// lengths_only: stop after the length pass and its refusal (the caller already knows that the batch fails): nothing is sized or written.
 void sam_format(const kslam_paired_overlap *d_recs, const kslam_read_pair *d_groups, uint64_t n_groups, const SamInputs &in,
                 const SamAnnot &A, const SamParams &P, SamWork &W, uint64_t *text_bytes, hipStream_t s, bool bam = false,
-                uint32_t *bad_read = nullptr, const SamSeq *seq = nullptr);
+                uint32_t *bad_read = nullptr, const SamSeq *seq = nullptr, uint64_t room_behind = 0, bool lengths_only = false);
+// The rows of the reads without alignment (include/kslam_samunmapped.h), in two halves around sam_format.  After sam_plan:
+// d_plan = W.plan of the batch's n_groups read pairs (unused when n_groups == 0); n_pairs = the batch's records, read pairs laid
+// out [R1 block | R2 block] when paired.  *bytes = what the rows come to; BAM with an id longer than 254 bytes among them:
+// *bad_read = the lowest such read and *bytes = 0 (otherwise 0xFFFFFFFF).  Waits for the stream (the sizes are read back).
+void sam_unmapped_plan(const kslam_read_pair *d_groups, const SamPlan *d_plan, uint64_t n_groups, uint64_t n_pairs, bool paired,
+                       const SamInputs &in, bool bam, const SamSeq *seq, SamUnmappedWork &U, uint64_t *bytes, uint32_t *bad_read,
+                       hipStream_t s);
+// ... and the rows themselves into d_out[0 .. *bytes), same arguments.  Does not wait.
+void sam_unmapped_write(uint64_t n_pairs, bool paired, const SamInputs &in, bool bam, const SamSeq *seq, SamUnmappedWork &U, uint8_t *d_out,
+                        hipStream_t s);
+// once the stream has been waited for: adds the write pass's device time to U.kernel_ms
+void sam_unmapped_timing(SamUnmappedWork &U);
 // per-read LCA into W.tax_ids (u32 per read pair) and the <out>_PerRead lines into W.pr_text
 void per_read_device(const kslam_paired_overlap *d_recs, const kslam_read_pair *d_groups, uint64_t n_groups, const SamInputs &in,
                      const SamAnnot &A, SamWork &W, uint64_t *text_bytes, hipStream_t s);

@@ -24,6 +24,7 @@
 #include "../../include/kslam_bgzf.h"
 #include "../../include/kslam_bam.h"
 #include "../../include/kslam_samseq.h"
+#include "../../include/kslam_samunmapped.h"
 #include "../../include/kslam_readsplit.h"
 #include "../../include/kslam_coverage.h"
 #include "workers.hpp"
@@ -141,8 +142,9 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     }
     // BGZF (include/kslam_bgzf.h): every SAM byte goes to the writer compressed -- the lanes compress what they format, the
     // header and any host-formatted batch go through kslam_bgzf_compress here; the EOF marker ends the file
-    int bgzf = 0, bam = 0, seq = 0;
-    if (kslam_get_sam_bgzf(ctx, &bgzf) != KSLAM_OK || kslam_get_sam_bam(ctx, &bam) != KSLAM_OK || kslam_get_sam_seq(ctx, &seq) != KSLAM_OK)
+    int bgzf = 0, bam = 0, seq = 0, unmapped = 0;
+    if (kslam_get_sam_bgzf(ctx, &bgzf) != KSLAM_OK || kslam_get_sam_bam(ctx, &bam) != KSLAM_OK || kslam_get_sam_seq(ctx, &seq) != KSLAM_OK ||
+        kslam_get_sam_unmapped(ctx, &unmapped) != KSLAM_OK)
       fail(KSLAM_ERR_ARG, "null context");
     // BAM (include/kslam_bam.h): the same file framing, with kslam_bam_header's bytes and BAM records inside the members
     if (bam) bgzf = 1;
@@ -322,6 +324,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
             fail(KSLAM_ERR_STATE, "kslam_set_sam_bam was switched on while a batch was in flight");
           if ((seq != 0) != ((res.text_flags & KSLAM_TEXT_SAM_SEQ) != 0))   // (host-formatted batches follow `seq`: one file, one form)
             fail(KSLAM_ERR_STATE, "kslam_set_sam_seq was changed while kslam_stream_classify was running");
+          if ((unmapped != 0) != ((res.text_flags & KSLAM_TEXT_SAM_UNMAPPED) != 0))   // (host-formatted batches follow `unmapped`)
+            fail(KSLAM_ERR_STATE, "kslam_set_sam_unmapped was changed while kslam_stream_classify was running");
           if (bgzf && !(res.text_flags & KSLAM_TEXT_SAM_BGZF)) {   // (the switch went on after the batch was formatted)
             st.sam_bytes += enqueue_compressed(res.sam_text, res.sam_text_len);
           } else {
@@ -375,6 +379,17 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
                         &host_sorted, &reads, index, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, res.details, res.md_pool,
                         res.n_md, res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs, wr, wu, &ts);
           if (a != KSLAM_OK) fail(a, kslam_tail_last_error());
+          // (include/kslam_samunmapped.h) the rows of the reads without alignment behind the batch's rows, by the host twin
+          if (unmapped) {
+            char *rows = nullptr;
+            uint64_t rows_len = 0;
+            const kslam_status u = kslam_tail_sam_unmapped(&P->tail, &seq_reads, res.read_pairs, res.n_read_pairs,
+                                                           paired ? res.n_reads / 2 : res.n_reads, bam, seq, &rows, &rows_len);
+            if (u != KSLAM_OK) fail(u, kslam_tail_last_error());
+            std::unique_ptr<char, decltype(&kslam_free)> own(rows, &kslam_free);
+            if (rows_len && wr(wu, rows, rows_len) != 0) fail(KSLAM_ERR_ARG, "writing the SAM rows of the unaligned reads failed");
+            if (!bgzf) ts.sam_bytes += rows_len;
+          }
           st.sam_bytes += bgzf ? enqueue_compressed(text.data(), text.size()) : ts.sam_bytes;
           st.seconds_sam_text += (now_ms() - t0) * 1e-3;
         });

@@ -33,6 +33,7 @@
 #include "../include/kslam_db.h"
 #include "../include/kslam_inflate.h"
 #include "../include/kslam_samseq.h"
+#include "../include/kslam_samunmapped.h"
 #include "../include/kslam_readsplit.h"
 #include "../include/kslam_coverage.h"
 #include "../include/kslam_stream.h"
@@ -73,7 +74,7 @@ struct Options {
   uint32_t num_reads = UINT32_MAX, num_reads_at_once = 10000000, num_alignments = 10;
   double score_fraction = 0.95;
   bool sam_xa = false, just_align = false, no_pseudo = false, help = false, version = false, parse_fasta = false, sam_bgzf = false,
-       sam_bam = false, sam_seq = false, sam_deflate_given = false;
+       sam_bam = false, sam_seq = false, sam_unmapped = false, sam_deflate_given = false;
   int sam_deflate = KSLAM_BGZF_DEFLATE_FIXED;
   int device = 0;
   std::vector<std::string> inputs;
@@ -116,6 +117,8 @@ void usage(FILE *o) {
         "  --sam-bam                             write --sam-file as BAM (implies --sam-bgzf)\n"
         "  --sam-deflate arg (=fixed)            fixed or dynamic: the Huffman codes of --sam-bgzf / --sam-bam (dynamic: a smaller file)\n"
         "  --sam-seq                             write SEQ and QUAL on the primary rows of --sam-file instead of \"*\"\n"
+        "  --sam-unmapped                        after each batch's rows, write a FLAG-4 row to --sam-file for every read without an\n"
+        "                                        alignment; with --sam-seq the file is then a full copy of the reads\n"
         "  --classified-out arg                  write the classified reads (with --just-align: the aligned reads) to this FASTQ file;\n"
         "                                        with R1FILE and R2FILE arg must contain a '#', replaced by 1 and 2\n"
         "  --unclassified-out arg                the same for the reads that are not classified\n"
@@ -128,7 +131,7 @@ void usage(FILE *o) {
 Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
-         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT };
+         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -146,6 +149,7 @@ Options parse(int argc, char **argv) {
       {"sam-bam", no_argument, nullptr, SAM_BAM},       // not in the reference: the SAM file as BAM (include/kslam_bam.h)
       {"sam-deflate", required_argument, nullptr, SAM_DEFLATE},   // not in the reference: kslam_set_bgzf_deflate (include/kslam_bgzf.h)
       {"sam-seq", no_argument, nullptr, SAM_SEQ},       // not in the reference: SEQ and QUAL in the SAM file (include/kslam_samseq.h)
+      {"sam-unmapped", no_argument, nullptr, SAM_UNMAPPED},   // not in the reference: rows for the reads without alignment (include/kslam_samunmapped.h)
       // not in the reference: the reads themselves, split by outcome (include/kslam_readsplit.h; Kraken 2's option names)
       {"classified-out", required_argument, nullptr, CLASSIFIED_OUT}, {"unclassified-out", required_argument, nullptr, UNCLASSIFIED_OUT},
       {"reads-out-bgzf", no_argument, nullptr, READS_OUT_BGZF},
@@ -179,6 +183,7 @@ Options parse(int argc, char **argv) {
       case SAM_BGZF: o.sam_bgzf = true; break;
       case SAM_BAM: o.sam_bam = true; break;
       case SAM_SEQ: o.sam_seq = true; break;
+      case SAM_UNMAPPED: o.sam_unmapped = true; break;
       case CLASSIFIED_OUT: o.classified_out = optarg; break;
       case UNCLASSIFIED_OUT: o.unclassified_out = optarg; break;
       case READS_OUT_BGZF: o.reads_out_bgzf = true; break;
@@ -201,6 +206,7 @@ Options parse(int argc, char **argv) {
     }
   }
   if (o.sam_deflate_given && !o.sam_bgzf && !o.sam_bam && !o.reads_out_bgzf) die("option '--sam-deflate' needs '--sam-bgzf' or '--sam-bam'");
+  if (o.sam_unmapped && o.sam.empty()) die("option '--sam-unmapped' needs '--sam-file'");
   return o;
 }
 
@@ -402,6 +408,7 @@ int run(const Options &o, const std::string &command_line) {
   if (o.reads_out_bgzf && want_reads_out && kslam_set_reads_out_bgzf(ctx, 1) != KSLAM_OK) die(std::string("reads out: ") + kslam_last_error(ctx));
   if ((want_sam || (want_reads_out && o.reads_out_bgzf)) && kslam_set_bgzf_deflate(ctx, o.sam_deflate) != KSLAM_OK) die(std::string("BGZF: ") + kslam_last_error(ctx));
   if (o.sam_seq && want_sam && kslam_set_sam_seq(ctx, 1) != KSLAM_OK) die(std::string("SEQ: ") + kslam_last_error(ctx));
+  if (o.sam_unmapped && kslam_set_sam_unmapped(ctx, 1) != KSLAM_OK) die(std::string("unmapped rows: ") + kslam_last_error(ctx));
   logl("Getting k-mers from index");
   if (kslam_set_index(ctx, index->n_entries, kslam_db_entry_bases(db), kslam_db_entry_lengths(db)) != KSLAM_OK)
     die(std::string("index: ") + kslam_last_error(ctx));
