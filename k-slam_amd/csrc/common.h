@@ -673,4 +673,57 @@ void coverage_mark_device(const kslam_overlap *d_ov, uint64_t n_ov, const kslam_
 // covered_bases of every row, counted from the bitmap (the column is cleared first); ev: two events around the launches
 void coverage_count_device(const CoverageTable &T, hipEvent_t ev[2], hipStream_t s);
 
+// ------------------------------------------------------------ variants.hip
+// The SNV table (include/kslam_variants.h).  The state -- three arrays of 8-byte keys -- belongs to the context the switch was
+// set on (context.h: kslam_ctx::Variants); each lane counts its batch with a VariantEmitWork of its own and appends under the
+// state's lock.
+struct VariantInputs {            // one batch as the kernels see it
+  const kslam_overlap *ov;
+  uint64_t n_ov;
+  const kslam_read_pair *groups;
+  uint64_t n_groups;
+  const kslam_paired_overlap *pairs;
+  uint64_t n_pairs;
+  const uint32_t *pool;          // the CIGAR pool
+  uint64_t n_cig;
+  const uint8_t *rbases;         // read i: rbases[roff[i] .. roff[i + 1])
+  const uint64_t *roff;
+  uint64_t n_reads;
+  const uint8_t *gbases;         // the index's entries
+  const uint64_t *goff;
+  uint64_t n_entries;
+};
+struct VariantEmitWork {
+  DevBuf flag, pos, list;        // u32 per overlap record: named by a live pair, its place in the list; the list
+  DevBuf cnt_ev, cnt_iv;         // u32 per listed record
+  DevBuf off_ev, off_iv;         // u64 per listed record: its first slot
+  DevBuf scan_tmp, totals;
+  uint64_t n_list = 0, n_ev = 0, n_iv = 0, n_skipped = 0;   // of the batch counted last
+  hipEvent_t ev[2]{};            // before the first pass, after the last
+  float ms = 0;
+  VariantEmitWork() = default;
+  VariantEmitWork(const VariantEmitWork &) = delete;
+  VariantEmitWork &operator=(const VariantEmitWork &) = delete;
+  ~VariantEmitWork() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+struct VariantTakeWork {
+  SortWorkspace sortws;
+  DevBuf alt;                    // the sort's second buffer
+  DevBuf head, run;              // u32 per event: starts a (g, alt) run; the run's number
+  DevBuf starts, fwd, rev, depth, keep, out_at;   // u32 per run
+  DevBuf rows, scan_tmp, totals;
+};
+// passes 1-4: flags, list, counting walk, scans; fills W.n_list / n_ev / n_iv / n_skipped (waits for the stream)
+void variants_count_device(const VariantInputs &in, VariantEmitWork &W, hipStream_t s);
+// pass 6: the keys of the batch counted last, from d_events / d_begins / d_ends on (the caller made room for W.n_ev / W.n_iv);
+// waits for the stream and fills W.ms
+void variants_write_device(const VariantInputs &in, VariantEmitWork &W, uint64_t *d_events, uint64_t *d_begins, uint64_t *d_ends, hipStream_t s);
+// sorts the three arrays in place unless `sorted`, then the rows that pass the filter into T.rows (device); waits for the stream
+void variants_take_device(VariantTakeWork &T, DevBuf &events, uint64_t n_ev, DevBuf &begins, DevBuf &ends, uint64_t n_iv, bool sorted,
+                          const uint64_t *d_goff, const uint8_t *d_gbases, uint64_t n_entries, uint64_t total_bases, uint32_t min_alt,
+                          uint32_t min_depth, uint64_t *n_sites_out, uint64_t *n_rows_out, hipStream_t s);
+
 }  // namespace kslam

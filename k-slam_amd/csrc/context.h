@@ -22,6 +22,7 @@
 #include "../../include/kslam_samunmapped.h"
 #include "../../include/kslam_readsplit.h"
 #include "../../include/kslam_coverage.h"
+#include "../../include/kslam_variants.h"
 #include "../host/workers.hpp"
 #include "../host/inflate.hpp"
 #include <algorithm>
@@ -152,6 +153,23 @@ struct kslam_ctx {
     std::mutex mu;                // add / take / reset / bitmap / the switch: one at a time
   } cov;
   CoverageMarkWork covw;          // this context's own mark passes (a lane's batches; on the primary: kslam_coverage_add)
+
+  // ---- the SNV table (variants.hip, include/kslam_variants.h) ----
+  struct Variants {               // on the context the switch was set on; its lanes append to it (lane_main)
+    std::atomic<bool> on{false};
+    uint64_t n_entries = 0, total_bases = 0;
+    DevBuf events, begins, ends;  // u64 keys, append-only between two resets; n_ev / n_iv of them are in use
+    uint64_t n_ev = 0, n_iv = 0, n_records = 0, n_skipped = 0;
+    bool sorted = false;          // nothing was appended since kslam_variants_take sorted the arrays
+    VariantTakeWork tw;
+    DevBuf up_ov, up_groups, up_pairs, up_pool, up_rbases, up_roff;   // kslam_variants_add's uploads
+    hipEvent_t ev_take[2]{};
+    double take_ms = 0;
+    int stream_fd = -1;           // kslam_stream_set_variants
+    uint32_t stream_min_alt = 2, stream_min_depth = 1;
+    std::mutex mu;                // append / take / reset / the switch: one at a time
+  } var;
+  VariantEmitWork varw;           // this context's own emit passes (a lane's batches; on the primary: kslam_variants_add)
 
   // ---- device pairing / screens (pairs.hip) ----
   PairWork pw;
@@ -318,6 +336,12 @@ void free_reads_out(kslam_ctx *c, kslam_reads_out *out);
 void coverage_release(kslam_ctx *c);
 // the batch `lane` has just finished (lane->pres over lane->res_ov) into owner's table, on lane's stream
 void coverage_mark_resident(kslam_ctx *owner, kslam_ctx *lane);
+
+// ---- api_variants.hip
+// frees the variants state of c and switches it off (kslam_set_variants(c, 0), kslam_set_index)
+void variants_release(kslam_ctx *c);
+// the batch `lane` has just finished (lane->pres over lane->res_ov, lane->res_cig and lane's reads) into owner's state, on lane's stream
+void variants_emit_resident(kslam_ctx *owner, kslam_ctx *lane);
 
 }  // namespace kslam_api
 

@@ -27,6 +27,7 @@
 #include "../../include/kslam_samunmapped.h"
 #include "../../include/kslam_readsplit.h"
 #include "../../include/kslam_coverage.h"
+#include "../../include/kslam_variants.h"
 #include "workers.hpp"
 
 namespace {
@@ -71,6 +72,9 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
   int ro_bgzf = 0;
   int cov_fd = -1;                    // kslam_stream_set_coverage: where the coverage report goes
   bool coverage_set = false;
+  int var_fd = -1;                    // kslam_stream_set_variants: where the VCF file goes
+  uint32_t var_min_alt = 2, var_min_depth = 1;
+  bool variants_set = false;
 
   const int pool_cap = P && P->pool_threads ? (int)P->pool_threads : std::max(2, usable_cpus() - 4);
   Pool::get().add_cap(pool_cap);
@@ -94,6 +98,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     if (reads_out_set) kslam_set_reads_out(ctx, 0);
     if (coverage_set) kslam_set_coverage(ctx, 0);
     if (ctx) kslam_stream_set_coverage(ctx, -1);          // held for this call alone, like the descriptors below
+    if (variants_set) kslam_set_variants(ctx, 0);
+    if (ctx) kslam_stream_set_variants(ctx, -1, 2, 1);
     if (ctx) kslam_stream_set_reads_out(ctx, nullptr);   // the descriptors held for this call alone
     if (pairing_set) kslam_set_pairing(ctx, 1, 0, 0.95, 0);
     Pool::get().remove_cap(pool_cap);
@@ -129,6 +135,13 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       if (kslam_set_coverage(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
       coverage_set = true;
       if (kslam_coverage_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+    }
+    // the SNV table (include/kslam_variants.h): the lanes pile up what they finish; the VCF file follows the last batch
+    if (kslam_stream_get_variants(ctx, &var_fd, &var_min_alt, &var_min_depth) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    if (var_fd >= 0) {
+      if (kslam_set_variants(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
+      variants_set = true;
+      if (kslam_variants_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
     }
     const bool host_split = getenv("KSLAM_HOST_SAM_TEXT") && getenv("KSLAM_HOST_SAM_TEXT")[0] == '1';   // (A/B: the host twin for every batch)
     // the SAM records and the per-read lines written on the GPU (include/kslam_samtext.h); KSLAM_HOST_SAM_TEXT=1 keeps the
@@ -316,6 +329,25 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         });
         if (s != KSLAM_OK) err = g_err;
       }
+      // the variants likewise; the lanes keep the read bases on the device, so the batch's window is parsed into columns first
+      if (s == KSLAM_OK && variants_set && P->tail.pseudo_assembly && !(res.pair_stats.stages_done & KSLAM_TAIL_PSEUDO_ASM)) {
+        s = guarded([&] {
+          kslam_reads_columns cols;
+          memset(&cols, 0, sizeof cols);
+          struct Release { kslam_reads_columns *c; ~Release() { kslam_reads_free(c); } } release{&cols};
+          uint64_t c1 = 0, c2 = 0;
+          const kslam_status q = paired ? kslam_fastq_parse_pair(r1 + win.p1, win.e1 - win.p1, r2 + win.p2, win.e2 - win.p2, 0, 1,
+                                                                 P->tail.threads, &cols, &c1, &c2)
+                                        : kslam_fastq_parse(r1 + win.p1, win.e1 - win.p1, 0, 1, P->tail.threads, &cols, &c1);
+          if (q != KSLAM_OK) fail(q, kslam_tail_last_error());
+          if (cols.n_reads != res.n_reads || memcmp(cols.bases_off, res.reads_bases_off, sizeof(uint64_t) * (res.n_reads + 1)) != 0)
+            fail(KSLAM_ERR_INTERNAL, "the host's parse of a batch differs from the device's index");
+          if (kslam_variants_add(ctx, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, cols.bases, cols.bases_off, cols.n_reads,
+                                 res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK)
+            fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+        });
+        if (s != KSLAM_OK) err = g_err;
+      }
       if (s == KSLAM_OK && writer && (res.text_flags & KSLAM_TEXT_SAM)) {
         s = guarded([&] {   // written on the GPU: the page-locked block joins the writer's queue as it is and goes back to the
                             // context's pool once it is in the file
@@ -473,6 +505,15 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       uint64_t n_rows = 0, n_skipped = 0;
       if (kslam_coverage_take(ctx, &rows, &n_rows, &n_skipped) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
       const kslam_status w = kslam_coverage_write(index, rows, n_rows, cov_fd);
+      kslam_free_pinned(ctx, rows);
+      if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
+    }
+    if (variants_set) {
+      kslam_variant_row *rows = nullptr;
+      uint64_t n_rows = 0;
+      kslam_variant_stats vs;
+      if (kslam_variants_take(ctx, var_min_alt, var_min_depth, &rows, &n_rows, &vs) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      const kslam_status w = kslam_variants_write(index, rows, n_rows, &vs, var_fd);
       kslam_free_pinned(ctx, rows);
       if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
     }

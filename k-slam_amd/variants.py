@@ -1,0 +1,180 @@
+"""ctypes plumbing for include/kslam_variants.h: the SNV table piled up on the GPU (one row per entry, position and alternate
+base with its observations by strand and the depth), its host twin, the VCF writer and a parser for the file."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import OVERLAP_DT
+from . import tail as _T
+
+# every symbol include/kslam_variants.h declares
+EXPORTS = ["kslam_get_variants", "kslam_set_variants", "kslam_stream_get_variants", "kslam_stream_set_variants", "kslam_tail_variants",
+           "kslam_variants_add", "kslam_variants_kernel_ms", "kslam_variants_reset", "kslam_variants_take", "kslam_variants_write"]
+ROW_DT = np.dtype([("entry", "<u4"), ("pos", "<u4"), ("ref", "u1"), ("alt", "u1"), ("pad", "u1", (2,)), ("alt_fwd", "<u4"), ("alt_rev", "<u4"),
+                   ("depth", "<u4")])
+STAT_NAMES = ("n_records", "n_skipped", "n_intervals", "n_events", "n_sites")
+COLUMNS = b"#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n"
+_ready = False
+
+
+class Stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in STAT_NAMES]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in STAT_NAMES}
+
+
+def lib():
+    global _ready
+    L = _T.lib()
+    if not _ready:
+        vp, u64, u32, P = C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER
+        batch = [vp, u64, vp, u64, vp, vp, u64, vp, u64, vp, u64]   # overlaps, pool, read bases + offsets, read pairs, pairs
+        L.kslam_set_variants.argtypes = [vp, C.c_int]
+        L.kslam_get_variants.argtypes = [vp, P(C.c_int)]
+        L.kslam_variants_reset.argtypes = [vp]
+        L.kslam_variants_add.argtypes = [vp] + batch
+        L.kslam_variants_take.argtypes = [vp, u32, u32, P(vp), P(u64), P(Stats)]
+        L.kslam_variants_kernel_ms.argtypes = [vp, P(C.c_double), P(C.c_double)]
+        L.kslam_tail_variants.argtypes = [vp, vp, u64] + batch + [u32, u32, P(vp), P(u64), P(Stats)]
+        L.kslam_variants_write.argtypes = [P(_T.IndexView), vp, u64, P(Stats), C.c_int]
+        L.kslam_stream_set_variants.argtypes = [vp, C.c_int, u32, u32]
+        L.kslam_stream_get_variants.argtypes = [vp, P(C.c_int), P(u32), P(u32)]
+        L.kslam_free_pinned.argtypes = [vp, vp]
+        L.kslam_free_pinned.restype = None
+        L.kslam_free.argtypes = [vp]
+        L.kslam_free.restype = None
+        _ready = True
+    return L
+
+
+def _arrays(overlaps, cigar_pool, read_bases, read_offsets, read_pairs, pairs):
+    ov = np.ascontiguousarray(overlaps, dtype=OVERLAP_DT)
+    cg = np.ascontiguousarray(cigar_pool, dtype=np.uint32)
+    rb = np.ascontiguousarray(np.frombuffer(read_bases, dtype=np.uint8) if isinstance(read_bases, (bytes, bytearray)) else read_bases, dtype=np.uint8)
+    ro = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+    rp = np.ascontiguousarray(read_pairs, dtype=_T.READ_PAIR_DT)
+    pr = np.ascontiguousarray(pairs, dtype=_T.PAIRED_OVERLAP_DT)
+    ptr = lambda a: a.ctypes.data if len(a) else None   # noqa: E731
+    n_reads = max(len(ro) - 1, 0)
+    return (ov, cg, rb, ro, rp, pr), (ptr(ov), len(ov), ptr(cg), len(cg), ptr(rb), ro.ctypes.data if n_reads else None, n_reads, ptr(rp), len(rp),
+                                      ptr(pr), len(pr))
+
+
+def set_variants(ctx, on=True):
+    """kslam_set_variants: needs an index, ctx.set_pairing and a context with report_cigar; off frees the state"""
+    ctx._chk(lib().kslam_set_variants(ctx._h, int(on)))
+
+
+def get_variants(ctx):
+    on = C.c_int()
+    ctx._chk(lib().kslam_get_variants(ctx._h, C.byref(on)))
+    return bool(on.value)
+
+
+def reset(ctx):
+    ctx._chk(lib().kslam_variants_reset(ctx._h))
+
+
+def add(ctx, overlaps, cigar_pool, read_bases, read_offsets, read_pairs, pairs):
+    """kslam_variants_add: one batch's arrays from the host (OVERLAP_DT, uint32 pool, the reads' bases with their n + 1 offsets,
+    READ_PAIR_DT, PAIRED_OVERLAP_DT)"""
+    keep, args = _arrays(overlaps, cigar_pool, read_bases, read_offsets, read_pairs, pairs)
+    ctx._chk(lib().kslam_variants_add(ctx._h, *args))
+
+
+def take(ctx, min_alt=2, min_depth=1):
+    """kslam_variants_take -> (rows: ROW_DT array, stats: dict)"""
+    L = lib()
+    rows, n, st = C.c_void_p(), C.c_uint64(), Stats()
+    ctx._chk(L.kslam_variants_take(ctx._h, int(min_alt), int(min_depth), C.byref(rows), C.byref(n), C.byref(st)))
+    out = np.frombuffer(C.string_at(rows.value, n.value * ROW_DT.itemsize), dtype=ROW_DT).copy() if n.value else np.zeros(0, dtype=ROW_DT)
+    L.kslam_free_pinned(ctx._h, rows)
+    return out, st.as_dict()
+
+
+def kernel_ms(ctx):
+    """(device ms of the last kslam_variants_add's emit passes, of the last take)"""
+    a, b = C.c_double(), C.c_double()
+    ctx._chk(lib().kslam_variants_kernel_ms(ctx._h, C.byref(a), C.byref(b)))
+    return float(a.value), float(b.value)
+
+
+def tail_variants(entry_bases, entry_offsets, overlaps, cigar_pool, read_bases, read_offsets, read_pairs, pairs, min_alt=2, min_depth=1):
+    """kslam_tail_variants (host twin) -> (rows, stats)"""
+    L = lib()
+    gb = np.ascontiguousarray(np.frombuffer(entry_bases, dtype=np.uint8) if isinstance(entry_bases, (bytes, bytearray)) else entry_bases, dtype=np.uint8)
+    go = np.ascontiguousarray(entry_offsets, dtype=np.uint64)
+    keep, args = _arrays(overlaps, cigar_pool, read_bases, read_offsets, read_pairs, pairs)
+    rows, n, st = C.c_void_p(), C.c_uint64(), Stats()
+    n_entries = max(len(go) - 1, 0)
+    _T._chk(L.kslam_tail_variants(gb.ctypes.data if len(gb) else None, go.ctypes.data if n_entries else None, n_entries, *args, int(min_alt),
+                                  int(min_depth), C.byref(rows), C.byref(n), C.byref(st)))
+    out = np.frombuffer(C.string_at(rows.value, n.value * ROW_DT.itemsize), dtype=ROW_DT).copy() if n.value else np.zeros(0, dtype=ROW_DT)
+    L.kslam_free(rows)
+    return out, st.as_dict()
+
+
+def write(index, rows, fd, stats=None):
+    """kslam_variants_write: index a kslam_amd.tail index view (e.g. kslam_amd.db.Database), rows a ROW_DT array"""
+    r = np.ascontiguousarray(rows, dtype=ROW_DT)
+    st = None
+    if stats is not None:
+        st = Stats(*[int(stats[n]) for n in STAT_NAMES])
+    _T._chk(lib().kslam_variants_write(C.byref(index.view), r.ctypes.data if len(r) else None, len(r), C.byref(st) if st is not None else None, int(fd)))
+
+
+def report_bytes(index, rows, stats=None):
+    """the VCF file as bytes (through a pipe-free temporary descriptor)"""
+    fd = os.memfd_create("kslam_variants")
+    try:
+        write(index, rows, fd, stats)
+        os.lseek(fd, 0, os.SEEK_SET)
+        out = b""
+        while True:
+            piece = os.read(fd, 1 << 20)
+            if not piece:
+                return out
+            out += piece
+    finally:
+        os.close(fd)
+
+
+def stream_set_variants(ctx, fd, min_alt=2, min_depth=1):
+    """kslam_stream_set_variants: the descriptor the NEXT kslam_stream_classify on ctx writes its VCF file to (-1: none)"""
+    ctx._chk(lib().kslam_stream_set_variants(ctx._h, int(fd) if fd is not None else -1, int(min_alt), int(min_depth)))
+
+
+def parse_vcf(text):
+    """the file's lines -> (meta: list of the ## lines without the marker, rows: list of dicts with chrom, pos (1-based), ref, alt
+    as str and DP, AO, SAF, SAR as int, AF as float); raises ValueError when the column line is missing or a line has other fields"""
+    if isinstance(text, bytes):
+        text = text.decode()
+    lines = text.split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    meta, rows, seen_columns = [], [], False
+    for line in lines:
+        if line.startswith("##"):
+            if seen_columns:
+                raise ValueError("a ## line after the column line")
+            meta.append(line[2:])
+        elif line.startswith("#"):
+            if line + "\n" != COLUMNS.decode() or seen_columns:
+                raise ValueError("not the column line of a sites-only VCF file")
+            seen_columns = True
+        else:
+            if not seen_columns:
+                raise ValueError("a record before the column line")
+            f = line.split("\t")
+            if len(f) != 8:
+                raise ValueError("a VCF line has %d fields" % len(f))
+            info = dict(kv.split("=", 1) for kv in f[7].split(";"))
+            if sorted(info) != ["AF", "AO", "DP", "SAF", "SAR"] or f[2] != "." or f[5] != "." or f[6] != ".":
+                raise ValueError("a VCF line of another kind: " + line)
+            rows.append({"chrom": f[0], "pos": int(f[1]), "ref": f[3], "alt": f[4], "DP": int(info["DP"]), "AO": int(info["AO"]),
+                         "SAF": int(info["SAF"]), "SAR": int(info["SAR"]), "AF": float(info["AF"])})
+    if not seen_columns or not meta or meta[0] != "fileformat=VCFv4.2":
+        raise ValueError("not a VCF 4.2 file")
+    return meta, rows

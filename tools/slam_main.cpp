@@ -36,6 +36,7 @@
 #include "../include/kslam_samunmapped.h"
 #include "../include/kslam_readsplit.h"
 #include "../include/kslam_coverage.h"
+#include "../include/kslam_variants.h"
 #include "../include/kslam_stream.h"
 
 namespace {
@@ -68,7 +69,9 @@ void logl(const std::string &s) { g_log.line(s); }
 }
 
 struct Options {
-  std::string db, out, sam, classified_out, unclassified_out, coverage_out;
+  std::string db, out, sam, classified_out, unclassified_out, coverage_out, variants_out;
+  uint32_t variants_min_alt = 2, variants_min_depth = 1;
+  bool variants_min_alt_given = false, variants_min_depth_given = false;
   bool reads_out_bgzf = false;
   uint32_t score_threshold = 0, match = 2, mismatch = 3, gap_open = 5, gap_extend = 2;
   uint32_t num_reads = UINT32_MAX, num_reads_at_once = 10000000, num_alignments = 10;
@@ -125,13 +128,18 @@ void usage(FILE *o) {
         "  --reads-out-bgzf                      write those files as BGZF (--sam-deflate applies)\n"
         "  --coverage-out arg                    write a per-entry coverage table to this file: alignments, unique read pairs,\n"
         "                                        aligned and covered bases, breadth and mean depth (works with --just-align)\n"
+        "  --variants-out arg                    write the single-base differences between the reads and the entries to this file as\n"
+        "                                        VCF 4.2 (sites only: DP, AO, SAF, SAR, AF); works with --just-align, needs no --sam-file\n"
+        "  --variants-min-alt arg (=2)           report a site only when at least arg reads carry the alternate base\n"
+        "  --variants-min-depth arg (=1)         report a site only when at least arg reads cover it\n"
         "\n", o);
 }
 
 Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
-         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT };
+         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT,
+         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -154,6 +162,9 @@ Options parse(int argc, char **argv) {
       {"classified-out", required_argument, nullptr, CLASSIFIED_OUT}, {"unclassified-out", required_argument, nullptr, UNCLASSIFIED_OUT},
       {"reads-out-bgzf", no_argument, nullptr, READS_OUT_BGZF},
       {"coverage-out", required_argument, nullptr, COVERAGE_OUT},   // not in the reference: include/kslam_coverage.h
+      // not in the reference: include/kslam_variants.h
+      {"variants-out", required_argument, nullptr, VARIANTS_OUT}, {"variants-min-alt", required_argument, nullptr, VARIANTS_MIN_ALT},
+      {"variants-min-depth", required_argument, nullptr, VARIANTS_MIN_DEPTH},
       {nullptr, 0, nullptr, 0}};
   opterr = 0;
   int c;
@@ -188,6 +199,9 @@ Options parse(int argc, char **argv) {
       case UNCLASSIFIED_OUT: o.unclassified_out = optarg; break;
       case READS_OUT_BGZF: o.reads_out_bgzf = true; break;
       case COVERAGE_OUT: o.coverage_out = optarg; break;
+      case VARIANTS_OUT: o.variants_out = optarg; break;
+      case VARIANTS_MIN_ALT: o.variants_min_alt = to_u32(optarg, "variants-min-alt"); o.variants_min_alt_given = true; break;
+      case VARIANTS_MIN_DEPTH: o.variants_min_depth = to_u32(optarg, "variants-min-depth"); o.variants_min_depth_given = true; break;
       case SAM_DEFLATE:
         if (strcmp(optarg, "fixed") != 0 && strcmp(optarg, "dynamic") != 0)
           die(std::string("the argument ('") + optarg + "') for option '--sam-deflate' is invalid");
@@ -207,6 +221,8 @@ Options parse(int argc, char **argv) {
   }
   if (o.sam_deflate_given && !o.sam_bgzf && !o.sam_bam && !o.reads_out_bgzf) die("option '--sam-deflate' needs '--sam-bgzf' or '--sam-bam'");
   if (o.sam_unmapped && o.sam.empty()) die("option '--sam-unmapped' needs '--sam-file'");
+  if (o.variants_min_alt_given && o.variants_out.empty()) die("option '--variants-min-alt' needs '--variants-out'");
+  if (o.variants_min_depth_given && o.variants_out.empty()) die("option '--variants-min-depth' needs '--variants-out'");
   return o;
 }
 
@@ -399,7 +415,8 @@ int run(const Options &o, const std::string &command_line) {
   kp.gap_open = o.gap_open;
   kp.gap_extend = o.gap_extend;
   kp.score_threshold = o.score_threshold;
-  kp.report_cigar = want_sam ? 1 : 0;   // reportCigar = a SAM file was asked for (src/SLAM.h:169)
+  // reportCigar = a SAM file was asked for (src/SLAM.h:169); the variants walk the CIGARs too (the SAM text follows sp.tail.report_cigar)
+  kp.report_cigar = (want_sam || !o.variants_out.empty()) ? 1 : 0;
   kp.device = o.device;
   kslam_ctx *ctx = nullptr;
   if (kslam_create(&kp, &ctx) != KSLAM_OK) die(std::string("GPU context: ") + (ctx ? kslam_last_error(ctx) : "kslam_create failed"));
@@ -450,6 +467,12 @@ int run(const Options &o, const std::string &command_line) {
     if (coverage_fd < 0) die("unable to open " + o.coverage_out);
     if (kslam_stream_set_coverage(ctx, coverage_fd) != KSLAM_OK) die(std::string("coverage: ") + kslam_last_error(ctx));
   }
+  int variants_fd = -1;
+  if (!o.variants_out.empty()) {
+    variants_fd = open(o.variants_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (variants_fd < 0) die("unable to open " + o.variants_out);
+    if (kslam_stream_set_variants(ctx, variants_fd, o.variants_min_alt, o.variants_min_depth) != KSLAM_OK) die(std::string("variants: ") + kslam_last_error(ctx));
+  }
   kslam_stream_params sp;
   memset(&sp, 0, sizeof sp);
   sp.pairs_per_batch = o.num_reads_at_once;
@@ -493,6 +516,7 @@ int run(const Options &o, const std::string &command_line) {
   for (int fd : reads_out_fds)
     if (fd >= 0 && close(fd) != 0) die("closing a reads-out file failed");
   if (coverage_fd >= 0 && close(coverage_fd) != 0) die("closing the coverage file failed");
+  if (variants_fd >= 0 && close(variants_fd) != 0) die("closing the variants file failed");
   logl(cat("Found ", st.n_overlaps, " k-mer overlaps"));
   logl(cat("", st.n_read_pairs_aligned, " entries have k-mer overlaps"));
   if (paired && st.n_batches) logl(cat("Screening all alignment pairs with insert size >= ", st.first_max_insert_size, ""));
