@@ -608,6 +608,43 @@ kslam_status kslam_debug_partition_bins(kslam_ctx *ctx, const uint8_t *bins, uin
 kslam_status kslam_debug_bgzf_code_lengths(kslam_ctx *ctx, const uint32_t *counts, uint32_t n, uint32_t limit,
                                            uint8_t *lengths);
 
+/* ---- test hooks for the k-mer join and the overlap dedupe (csrc/join.hip; tests/test_gpu_join_seams.py) ----
+ * Both work on buffers of their own: nothing of the context's index, reads or results is touched, and the context is usable
+ * after a refusal.  Every argument is checked on the host; KSLAM_ERR_ARG comes before any kernel runs.
+ * The packed overlap key: read << (bits_entry + bits_rel + 1) | entry << (bits_rel + 1) | (rel + rel_bias) << 1 | revComp.
+ * Both hooks take bits_read <= 31, bits_entry <= 30, bits_rel in 1..31, a key of at most 63 bits and rel_bias < 2^bits_rel. */
+typedef struct {
+  uint32_t bits_read, bits_entry, bits_rel, rel_bias;
+} kslam_overlap_layout;
+#define KSLAM_DEBUG_SENTINEL_BYTE 0xEE /* every byte of what the two hooks fill before a kernel writes: no key of 63 bits, no flag */
+/* The join alone.  genome: n_g records {kmer, meta, offset} ascending by kmer; they are split into the key column and the
+ * {meta, offset} column with the allocation sizes of kslam_set_index (the key column's padding word holds all ones), and the
+ * bucket table over the top bucket_bits (8..16) key bits is built as there.  reads: n_r records of the same shape, their id
+ * indexing read_len[0 .. n_reads).  route 0: the probe (k_join_fill), read records in any order.  route 1: the merge
+ * (k_join_merge), read records ordered by their top min(sorted_top_bits, bucket_bits) key bits.  out: cap + 64 words, filled
+ * with the sentinel first -- the join writes nothing from out[cap] on, and nothing at all from a workgroup whose range does
+ * not fit; *cursor ends as the number of overlaps whatever cap is.  bucket_table: NULL or 2^bucket_bits + 1 words.
+ * KSLAM_ERR_ARG for: a null pointer that is needed, a layout as above, bucket_bits outside 8..16, a route other than 0 / 1,
+ * n_g, n_r or n_reads >= 2^24, cap >= 2^28, genome keys that are not ascending, a genome id beyond bits_entry, a read id
+ * outside read_len or beyond bits_read, a read record with offset + 32 > read_len[id], offsets and lengths for which some
+ * rel + rel_bias could leave [0, 2^bits_rel), and on route 1 sorted_top_bits outside 1..64 or read records out of order. */
+kslam_status kslam_debug_join(kslam_ctx *ctx, const kslam_kmer *genome, uint64_t n_g, uint32_t bucket_bits,
+                              const kslam_kmer *reads, uint64_t n_r, uint32_t sorted_top_bits, const uint32_t *read_len,
+                              uint64_t n_reads, const kslam_overlap_layout *layout, int route, uint64_t cap,
+                              uint64_t *cursor, uint64_t *out, uint32_t *bucket_table);
+/* From n packed overlap keys to the unique rows ("within 3 of the last kept", src/Overlap.h:79-85 of the reference).
+ * route 0: keys fully sorted; dedupe_flags, exclusive_scan_u32, dedupe_compact.  route 1: keys ordered by the bits above
+ * rel and revComp only; group_order, then scan and compact unless it raised *big (a (read, entry) group of more than 64
+ * keys): then *n_rows is 0 and ordered / flags are incomplete.  The device's flags and ordered-key buffers are filled with
+ * the sentinel first.  keys_after (NULL or n words): the device's input keys after the kernels; ordered (n): the keys the
+ * compaction reads (route 0: the input); flags (n); rows: room for n rows, *n_rows written, read = key's read +
+ * read_id_base, every field beyond revcomp zero.  KSLAM_ERR_ARG for: a null pointer that is needed, a layout as above, a
+ * route other than 0 / 1, n >= 2^28, a key wider than the layout, read + read_id_base beyond 32 bits, and keys not ordered
+ * as the route needs. */
+kslam_status kslam_debug_overlap_unique(kslam_ctx *ctx, const uint64_t *keys, uint64_t n, const kslam_overlap_layout *layout,
+                                        uint32_t read_id_base, int route, uint64_t *keys_after, uint64_t *ordered,
+                                        uint32_t *flags, uint32_t *big, uint64_t *n_rows, kslam_overlap *rows);
+
 #ifdef __cplusplus
 }
 #endif

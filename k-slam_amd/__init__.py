@@ -49,7 +49,7 @@ EXPORTS = ["kslam_abi_version", "kslam_index_build_stats", "kslam_version", "ksl
            "kslam_load_reads", "kslam_load_reads_device", "kslam_align_resident",
            "kslam_fetch_results", "kslam_take_results", "kslam_copy_results_device", "kslam_get_timings",
            "kslam_extract_kmers", "kslam_sort_kmers", "kslam_find_overlaps", "kslam_free",
-           "kslam_selftest_sort", "kslam_debug_radix_sort", "kslam_debug_scan", "kslam_debug_partition_bins", "kslam_debug_bgzf_code_lengths",
+           "kslam_selftest_sort", "kslam_debug_radix_sort", "kslam_debug_scan", "kslam_debug_partition_bins", "kslam_debug_bgzf_code_lengths", "kslam_debug_join", "kslam_debug_overlap_unique",
            "kslam_merge_shards_device", "kslam_shard_counts_device",
            "kslam_export_shard_device", "kslam_multi_create", "kslam_multi_destroy",
            "kslam_multi_last_error", "kslam_multi_set_index", "kslam_multi_align_batch", "kslam_multi_free_batch"]
@@ -103,6 +103,13 @@ class IndexStats(C.Structure):
     _fields_ = [("n_genome_kmers", C.c_uint64), ("sort_passes", C.c_uint32), ("n_entries", C.c_uint32),
                 ("ms_encode_extract", C.c_float), ("ms_sort", C.c_float), ("ms_tables", C.c_float), ("ms_total", C.c_float)]
 
+
+class OverlapLayout(C.Structure):
+    """kslam_overlap_layout: read | entry | rel + rel_bias | revComp, the packed overlap key of csrc/join.hip"""
+    _fields_ = [("bits_read", C.c_uint32), ("bits_entry", C.c_uint32), ("bits_rel", C.c_uint32), ("rel_bias", C.c_uint32)]
+
+
+DEBUG_SENTINEL_BYTE = 0xEE        # kslam.h: KSLAM_DEBUG_SENTINEL_BYTE
 
 # kslam_debug_radix_sort flags
 SORT_SETUP, SORT_DIGIT_BYTES, SORT_META_IN_RUNS, SORT_FIRST_DIGITS = 1, 2, 4, 8
@@ -196,6 +203,9 @@ def lib():
         L.kslam_debug_scan.argtypes = [vp, vp, u64, vp, C.c_int, u32, u32, vp]
         L.kslam_debug_partition_bins.argtypes = [vp, vp, u64, vp, vp]
         L.kslam_debug_bgzf_code_lengths.argtypes = [vp, vp, u32, u32, vp]
+        L.kslam_debug_join.argtypes = [vp, vp, u64, u32, vp, u64, u32, vp, u64, C.POINTER(OverlapLayout), C.c_int, u64, C.POINTER(u64), vp, vp]
+        L.kslam_debug_overlap_unique.argtypes = [vp, vp, u64, C.POINTER(OverlapLayout), u32, C.c_int, vp, vp, vp, C.POINTER(u32),
+                                                 C.POINTER(u64), vp]
         L.kslam_merge_shards_device.argtypes = [vp, u32, vp, u64, vp, vp, vp, vp]
         L.kslam_shard_counts_device.argtypes = [vp, u64, vp]
         L.kslam_export_shard_device.argtypes = [vp, u64, u64, u64, u64, u64, vp, vp, vp, vp]
@@ -676,6 +686,40 @@ class Context:
         out = np.full(max(len(cnt), 1), 0xEE, dtype=np.uint8)
         self._chk(self._L.kslam_debug_bgzf_code_lengths(self._h, cnt.ctypes.data, len(cnt), int(limit), out.ctypes.data))
         return out[:len(cnt)].tolist()
+
+    def debug_join(self, genome, bucket_bits, reads, sorted_top_bits, read_len, layout, route, cap, want_table=False):
+        """kslam_debug_join: genome / reads as KMER_DT records (genome ascending by kmer), read_len uint32 per read id,
+        layout = (bits_read, bits_entry, bits_rel, rel_bias), route 0 probe / 1 merge
+        -> (cursor, the cap + 64 output words, the bucket table of 2^bucket_bits + 1 words or None)"""
+        g = np.ascontiguousarray(genome, dtype=KMER_DT)
+        r = np.ascontiguousarray(reads, dtype=KMER_DT)
+        rl = np.ascontiguousarray(read_len, dtype=np.uint32)
+        lay = OverlapLayout(*[int(v) for v in layout])
+        out = np.zeros((int(cap) if 0 <= int(cap) < (1 << 28) else 0) + 64, dtype=np.uint64)     # (a cap beyond that is refused before anything is written)
+        table = np.zeros((1 << int(bucket_bits)) + 1, dtype=np.uint32) if want_table and 0 <= int(bucket_bits) <= 24 else None
+        cur = C.c_uint64(0)
+        self._chk(self._L.kslam_debug_join(self._h, g.ctypes.data, len(g), int(bucket_bits), r.ctypes.data, len(r), int(sorted_top_bits),
+                                           rl.ctypes.data, len(rl), C.byref(lay), int(route), int(cap), C.byref(cur), out.ctypes.data,
+                                           None if table is None else table.ctypes.data))
+        return int(cur.value), out, table
+
+    def debug_overlap_unique(self, keys, layout, read_id_base, route):
+        """kslam_debug_overlap_unique: keys uint64 (route 0: fully sorted; route 1: ordered by the bits above rel and
+        revComp), layout = (bits_read, bits_entry, bits_rel, rel_bias)
+        -> dict(keys_after, ordered, flags, big, rows): the device's input keys after the kernels, the keys the compaction
+        read, the keep flags, "a group of more than 64 keys" and the OVERLAP_DT rows (none when big)"""
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        n = len(k)
+        lay = OverlapLayout(*[int(v) for v in layout])
+        after, ordered = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        flags = np.zeros(max(n, 1), dtype=np.uint32)
+        rows = np.zeros(max(n, 1), dtype=OVERLAP_DT)
+        big, m = C.c_uint32(0), C.c_uint64(0)
+        self._chk(self._L.kslam_debug_overlap_unique(self._h, k.ctypes.data, n, C.byref(lay), int(read_id_base), int(route),
+                                                     after.ctypes.data, ordered.ctypes.data, flags.ctypes.data, C.byref(big),
+                                                     C.byref(m), rows.ctypes.data))
+        return {"keys_after": after[:n], "ordered": ordered[:n], "flags": flags[:n], "big": int(big.value),
+                "rows": rows[:int(m.value)]}
 
     def find_overlaps(self):
         out = C.c_void_p()

@@ -498,4 +498,151 @@ kslam_status kslam_debug_partition_bins(kslam_ctx *c, const uint8_t *bins, uint6
   });
 }
 
+// ---- test hooks for join.hip (tests/test_gpu_join_seams.py): the k-mer join on either route over records the caller supplies,
+// and the two routes from sorted overlap keys to the unique rows.  Buffers of their own: nothing of the context's index, reads
+// or results is touched.  Everything a kernel would index with is checked on the host first.
+static OverlapKeyLayout debug_layout(const kslam_overlap_layout *layout) {
+  if (!layout) throw StatusError{KSLAM_ERR_ARG, "null layout"};
+  if (layout->bits_read > 31 || layout->bits_entry > 30 || layout->bits_rel < 1 || layout->bits_rel > 31)
+    throw StatusError{KSLAM_ERR_ARG, "layout: bits_read <= 31, bits_entry <= 30, bits_rel in 1..31"};
+  if (layout->bits_read + layout->bits_entry + layout->bits_rel + 1 > 63) throw StatusError{KSLAM_ERR_ARG, "an overlap key wider than 63 bits"};
+  if (layout->rel_bias >= (1u << layout->bits_rel)) throw StatusError{KSLAM_ERR_ARG, "rel_bias beyond bits_rel"};
+  OverlapKeyLayout lay;
+  lay.bits_read = layout->bits_read; lay.bits_entry = layout->bits_entry; lay.bits_rel = layout->bits_rel;
+  lay.rel_bias = layout->rel_bias;
+  return lay;
+}
+
+kslam_status kslam_debug_join(kslam_ctx *c, const kslam_kmer *genome, uint64_t n_g, uint32_t bucket_bits, const kslam_kmer *reads,
+                              uint64_t n_r, uint32_t sorted_top_bits, const uint32_t *read_len, uint64_t n_reads,
+                              const kslam_overlap_layout *layout, int route, uint64_t cap, uint64_t *cursor, uint64_t *out,
+                              uint32_t *bucket_table) {
+  return guarded(c, [&] {
+    const OverlapKeyLayout lay = debug_layout(layout);
+    if (!cursor || !out || (n_g && !genome) || (n_r && !reads) || (n_reads && !read_len)) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+    if (bucket_bits < 8 || bucket_bits > 16) throw StatusError{KSLAM_ERR_ARG, "bucket_bits in 8..16"};
+    if (route != 0 && route != 1) throw StatusError{KSLAM_ERR_ARG, "route is 0 (probe) or 1 (merge)"};
+    if (n_g >= (1ull << 24) || n_r >= (1ull << 24) || n_reads >= (1ull << 24) || cap >= (1ull << 28))
+      throw StatusError{KSLAM_ERR_ARG, "2^24 records or reads or more, or a cap of 2^28 or more"};
+    if (route == 1 && (sorted_top_bits == 0 || sorted_top_bits > 64)) throw StatusError{KSLAM_ERR_ARG, "the merge needs sorted_top_bits in 1..64"};
+    // the genome side: ascending keys, ids the entry field holds
+    int64_t goff_min = INT64_MAX, goff_max = -1;
+    for (uint64_t i = 0; i < n_g; i++) {
+      if (i && genome[i].kmer < genome[i - 1].kmer) throw StatusError{KSLAM_ERR_ARG, "genome keys are not ascending"};
+      if ((uint64_t)(genome[i].meta & 0x3FFFFFFFu) >> lay.bits_entry) throw StatusError{KSLAM_ERR_ARG, "a genome id beyond bits_entry"};
+      goff_min = std::min<int64_t>(goff_min, genome[i].offset);
+      goff_max = std::max<int64_t>(goff_max, genome[i].offset);
+    }
+    // the read side: ids inside the length array and the read field, the k-mer inside its read
+    const uint32_t gb = std::min(sorted_top_bits, bucket_bits);
+    int64_t off_min = INT64_MAX, off_max = -1;
+    for (uint64_t i = 0; i < n_r; i++) {
+      const uint32_t id = reads[i].meta & 0x3FFFFFFFu;
+      if (id >= n_reads) throw StatusError{KSLAM_ERR_ARG, "a read id outside the read-length array"};
+      if ((uint64_t)id >> lay.bits_read) throw StatusError{KSLAM_ERR_ARG, "a read id beyond bits_read"};
+      if ((uint64_t)reads[i].offset + KSLAM_K > read_len[id]) throw StatusError{KSLAM_ERR_ARG, "a read k-mer that ends beyond its read"};
+      const int64_t fwd = reads[i].offset, rev = (int64_t)read_len[id] - reads[i].offset - KSLAM_K;   // Overlap.h:185-189, either strand of the genome record
+      off_min = std::min(off_min, std::min(fwd, rev));
+      off_max = std::max(off_max, std::max(fwd, rev));
+      if (route == 1 && i && (reads[i].kmer >> (64 - gb)) < (reads[i - 1].kmer >> (64 - gb)))
+        throw StatusError{KSLAM_ERR_ARG, "the merge needs read records ordered by their top min(sorted_top_bits, bucket_bits) key bits"};
+    }
+    if (n_g && n_r && (goff_min - off_max + (int64_t)lay.rel_bias < 0 || goff_max - off_min + (int64_t)lay.rel_bias >= (int64_t)(1ull << lay.bits_rel)))
+      throw StatusError{KSLAM_ERR_ARG, "offsets and read lengths whose rel + rel_bias the rel field cannot hold"};
+    hipStream_t s = c->stream;
+    const uint64_t nb = 1ull << bucket_bits;
+    // the columns and the table, with the allocation sizes of build_index; the key column's padding word holds all ones, the
+    // worst an allocation may hold there
+    DevBuf d_g, d_key, d_mo, d_bucket, d_r, d_len, d_out, d_cur;
+    d_g.ensure((n_g + 1) * sizeof(uint4));
+    d_key.ensure((n_g + 1) * sizeof(uint64_t));
+    d_mo.ensure((n_g + 1) * sizeof(uint2));
+    d_bucket.ensure((nb + 2) * sizeof(uint32_t));
+    d_r.ensure((n_r + 1) * sizeof(uint4));
+    d_len.ensure((n_reads + 1) * sizeof(uint32_t));
+    d_out.ensure((cap + 64) * sizeof(uint64_t));
+    d_cur.ensure(8 * sizeof(uint64_t));
+    HIPCHK(hipMemsetAsync(d_key.p, 0xFF, (n_g + 1) * sizeof(uint64_t), s));
+    HIPCHK(hipMemsetAsync(d_out.p, KSLAM_DEBUG_SENTINEL_BYTE, (cap + 64) * sizeof(uint64_t), s));
+    if (n_g) HIPCHK(hipMemcpyAsync(d_g.p, genome, n_g * sizeof(uint4), hipMemcpyHostToDevice, s));
+    if (n_r) HIPCHK(hipMemcpyAsync(d_r.p, reads, n_r * sizeof(uint4), hipMemcpyHostToDevice, s));
+    if (n_reads) HIPCHK(hipMemcpyAsync(d_len.p, read_len, n_reads * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if (n_g) hipLaunchKernelGGL(k_split_soa, dim3((unsigned)((n_g + 255) / 256)), dim3(256), 0, s, d_g.as<uint4>(), (uint32_t)n_g,
+                                d_key.as<uint64_t>(), d_mo.as<uint2>());
+    build_bucket_table(d_key.as<uint64_t>(), (uint32_t)n_g, bucket_bits, d_bucket.as<uint32_t>(), s);
+    GenomeIndexDev g;
+    g.key = d_key.as<uint64_t>(); g.mo = d_mo.as<uint2>(); g.bucket = d_bucket.as<uint32_t>();
+    g.bucket_bits = bucket_bits; g.n = (uint32_t)n_g;
+    if (route == 1)
+      join_fill_merge(d_r.as<uint4>(), (uint32_t)n_r, g, sorted_top_bits, d_len.as<uint32_t>(), d_cur.as<uint64_t>(), cap, lay,
+                      d_out.as<uint64_t>(), s);
+    else
+      join_fill_single_pass(d_r.as<uint4>(), (uint32_t)n_r, g, d_len.as<uint32_t>(), d_cur.as<uint64_t>(), cap, lay, d_out.as<uint64_t>(), s);
+    HIPCHK(hipMemcpyAsync(cursor, d_cur.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, d_out.p, (cap + 64) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (bucket_table) HIPCHK(hipMemcpyAsync(bucket_table, d_bucket.p, (nb + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(stream_wait(s));
+  });
+}
+
+kslam_status kslam_debug_overlap_unique(kslam_ctx *c, const uint64_t *keys, uint64_t n, const kslam_overlap_layout *layout,
+                                        uint32_t read_id_base, int route, uint64_t *keys_after, uint64_t *ordered, uint32_t *flags,
+                                        uint32_t *big, uint64_t *n_rows, kslam_overlap *rows) {
+  return guarded(c, [&] {
+    const OverlapKeyLayout lay = debug_layout(layout);
+    if (!big || !n_rows || (n && (!keys || !ordered || !flags || !rows))) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+    if (route != 0 && route != 1) throw StatusError{KSLAM_ERR_ARG, "route is 0 (sorted keys) or 1 (keys grouped by their high bits)"};
+    if (n >= (1ull << 28)) throw StatusError{KSLAM_ERR_ARG, "2^28 keys or more"};
+    const uint32_t width = lay.bits_read + lay.bits_entry + lay.bits_rel + 1, low = lay.bits_rel + 1;
+    for (uint64_t i = 0; i < n; i++) {
+      if (keys[i] >> width) throw StatusError{KSLAM_ERR_ARG, "a key wider than the layout"};
+      if ((keys[i] >> (lay.bits_entry + low)) + read_id_base > 0xFFFFFFFFull) throw StatusError{KSLAM_ERR_ARG, "read + read_id_base beyond 32 bits"};
+      if (i == 0) continue;
+      if (route == 0 && keys[i] < keys[i - 1]) throw StatusError{KSLAM_ERR_ARG, "route 0 needs fully sorted keys"};
+      if (route == 1 && (keys[i] >> low) < (keys[i - 1] >> low)) throw StatusError{KSLAM_ERR_ARG, "route 1 needs keys ordered by the bits above rel and revComp"};
+    }
+    *big = 0;
+    *n_rows = 0;
+    if (n == 0) return;
+    hipStream_t s = c->stream;
+    DevBuf d_in, d_ord, d_flags, d_pos, d_tmp, d_tot, d_rows;
+    d_in.ensure((n + 1) * sizeof(uint64_t));
+    d_ord.ensure((n + 1) * sizeof(uint64_t));
+    d_flags.ensure((n + 1) * sizeof(uint32_t));
+    d_pos.ensure((n + 1) * sizeof(uint32_t));
+    d_tmp.ensure(scan_tmp_bytes(n));
+    d_tot.ensure(8 * sizeof(uint64_t));
+    HIPCHK(hipMemcpyAsync(d_in.p, keys, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d_ord.p, KSLAM_DEBUG_SENTINEL_BYTE, (n + 1) * sizeof(uint64_t), s));
+    HIPCHK(hipMemsetAsync(d_flags.p, KSLAM_DEBUG_SENTINEL_BYTE, (n + 1) * sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(d_tot.p, 0, 8 * sizeof(uint64_t), s));
+    uint64_t *d_total = d_tot.as<uint64_t>();
+    uint32_t *d_big = reinterpret_cast<uint32_t *>(d_total + 3);
+    const uint64_t *d_keys = d_in.as<uint64_t>();
+    uint64_t back[4] = {0, 0, 0, 0};
+    if (route == 1) {
+      group_order(d_in.as<uint64_t>(), n, lay, d_ord.as<uint64_t>(), d_flags.as<uint32_t>(), d_big, s);
+      d_keys = d_ord.as<uint64_t>();
+      read_back(back, d_total, sizeof back, s);
+    } else {
+      dedupe_flags(d_keys, n, lay, d_flags.as<uint32_t>(), s);
+    }
+    if (back[3] == 0) {
+      exclusive_scan_u32(d_flags.as<uint32_t>(), d_pos.as<uint32_t>(), n, d_total, d_tmp.p, s);
+      read_back(back, d_total, sizeof back, s);
+      const uint64_t m = back[0];
+      if (m > n) throw StatusError{KSLAM_ERR_INTERNAL, "more survivors than keys"};
+      d_rows.ensure((m + 1) * sizeof(kslam_overlap));
+      dedupe_compact(d_keys, d_flags.as<uint32_t>(), d_pos.as<uint32_t>(), n, lay, read_id_base, d_rows.as<kslam_overlap>(), s);
+      if (m) HIPCHK(hipMemcpyAsync(rows, d_rows.p, m * sizeof(kslam_overlap), hipMemcpyDeviceToHost, s));
+      *n_rows = m;
+    }
+    *big = (uint32_t)back[3];
+    if (keys_after) HIPCHK(hipMemcpyAsync(keys_after, d_in.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ordered, route == 1 ? d_ord.p : d_in.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(flags, d_flags.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(stream_wait(s));
+  });
+}
+
 }  // extern "C"
