@@ -202,6 +202,11 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
                           (bgzf ? KSLAM_TEXT_SAM_BGZF : 0u) | (bam ? KSLAM_TEXT_SAM_BAM : 0u) | (sam.seq ? KSLAM_TEXT_SAM_SEQ : 0u) |
                           (sam.unmapped ? KSLAM_TEXT_SAM_UNMAPPED : 0u);
       if (st == KSLAM_OK && sam.unmapped) unmapped_note(primary, c);
+      // (kslam_set_kreport) this lane has just made the batch's taxonomy ids: they go into the owner's per-taxon counters from
+      // where they lie, on this lane's stream and outside the compute token like the marks below.  A batch without the
+      // per-read stage gets its ids on the host, which hands them to kslam_kreport_add.
+      if (st == KSLAM_OK && primary->samtext.per_read && primary->kr.on.load(std::memory_order_acquire))
+        st = guarded(c, [&] { kreport_count_resident(primary, c, sam.n_groups); });
     }
     sam_stage_free(c, sam);
     // (kslam_set_reads_out) the records split by outcome, cut out of the text this lane uploaded.  Outside the compute token as

@@ -673,6 +673,43 @@ void coverage_mark_device(const kslam_overlap *d_ov, uint64_t n_ov, const kslam_
 // covered_bases of every row, counted from the bitmap (the column is cleared first); ev: two events around the launches
 void coverage_count_device(const CoverageTable &T, hipEvent_t ev[2], hipStream_t s);
 
+// ------------------------------------------------------------- kreport.hip
+// The Kraken-style report's counts (include/kslam_kreport.h).  The state belongs to the context the switch was set on
+// (context.h: kslam_ctx::Kreport); its lanes count into it from their own streams (every update a device-scope atomic), each
+// with a KreportCountWork of its own, and append their unknown-id items under the state's lock.
+struct KreportTable {             // what the count pass sees
+  unsigned long long *direct;    // [n_nodes] reads whose id is this node's
+  const uint32_t *keys;          // [n_nodes] the tree's taxonomy ids, ascending
+  const uint32_t *nodes;         // [n_nodes] the node of keys[i]
+  uint64_t n_nodes;
+};
+struct KreportCountWork {
+  DevBuf items, cursor;          // the call's unknown-id items (id << 32 | count), and how many there are
+  uint64_t n_new = 0;            // ... read back
+  hipEvent_t ev[2]{};            // around the count launches
+  float ms = 0;                  // their device time, last batch
+  KreportCountWork() = default;
+  KreportCountWork(const KreportCountWork &) = delete;
+  KreportCountWork &operator=(const KreportCountWork &) = delete;
+  ~KreportCountWork() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+struct KreportTakeWork {
+  SortWorkspace sortws;
+  DevBuf clade, flag, pos;       // per node: u64 clade sum, u32 clade > 0, u32 place among the rows
+  DevBuf keys_a, keys_b, head, run;   // per unknown-id item: the sort's two buffers, run head, heads before it
+  DevBuf rows, scan_tmp, totals;
+};
+// n ids into the table; the unknown ids' items into W.items[0 .. W.n_new).  dry: nothing is written but W.n_new (what the call
+// WOULD append).  Waits for the stream (the cursor and the events are read).
+void kreport_count_device(const uint32_t *d_ids, uint64_t n, const KreportTable &T, KreportCountWork &W, bool dry, hipStream_t s);
+// clade sums, then the rows (kslam_kreport_row) into W.rows: *n_known rows of nodes in node order, *n_unknown of unknown ids in id
+// order behind them.  ev: two events around the launches.  Waits for the stream for the two counts, not for the row kernels.
+void kreport_take_device(const KreportTable &T, const uint32_t *d_up, const uint32_t *d_depth, const uint32_t *d_node_tax, const uint64_t *d_items,
+                         uint64_t n_items, KreportTakeWork &W, uint64_t *n_known, uint64_t *n_unknown, hipEvent_t ev[2], hipStream_t s);
+
 // ------------------------------------------------------------ variants.hip
 // The SNV table (include/kslam_variants.h).  The state -- three arrays of 8-byte keys -- belongs to the context the switch was
 // set on (context.h: kslam_ctx::Variants); each lane counts its batch with a VariantEmitWork of its own and appends under the

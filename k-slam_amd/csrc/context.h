@@ -23,6 +23,7 @@
 #include "../../include/kslam_readsplit.h"
 #include "../../include/kslam_coverage.h"
 #include "../../include/kslam_variants.h"
+#include "../../include/kslam_kreport.h"
 #include "../host/workers.hpp"
 #include "../host/inflate.hpp"
 #include <algorithm>
@@ -170,6 +171,22 @@ struct kslam_ctx {
     std::mutex mu;                // append / take / reset / the switch: one at a time
   } var;
   VariantEmitWork varw;           // this context's own emit passes (a lane's batches; on the primary: kslam_variants_add)
+
+  // ---- the Kraken-style report's counts (kreport.hip, include/kslam_kreport.h) ----
+  struct Kreport {                // on the context the switch was set on; its lanes count into it (lane_main)
+    std::atomic<bool> on{false};
+    uint64_t n_nodes = 0;         // of the device tree the state was laid out for
+    DevBuf direct, keys, nodes;   // u64 per node; the id -> node table
+    DevBuf items;                 // u64 (id << 32 | count) per unknown-id item; n_items of them are in use
+    uint64_t n_items = 0;
+    DevBuf up_ids;                // kslam_kreport_add's upload
+    KreportTakeWork tw;
+    hipEvent_t ev_take[2]{};
+    double take_ms = 0;
+    int stream_fd = -1;           // kslam_stream_set_kreport
+    std::mutex mu;                // add / take / reset / the lanes' appends / the switch: one at a time
+  } kr;
+  KreportCountWork krw;           // this context's own count passes (a lane's batches; on the primary: kslam_kreport_add)
 
   // ---- device pairing / screens (pairs.hip) ----
   PairWork pw;
@@ -342,6 +359,12 @@ void coverage_mark_resident(kslam_ctx *owner, kslam_ctx *lane);
 void variants_release(kslam_ctx *c);
 // the batch `lane` has just finished (lane->pres over lane->res_ov, lane->res_cig and lane's reads) into owner's state, on lane's stream
 void variants_emit_resident(kslam_ctx *owner, kslam_ctx *lane);
+
+// ---- api_kreport.hip
+// frees the report state of c and switches it off (kslam_set_kreport(c, 0), kslam_set_sam_annotations, kslam_set_index)
+void kreport_release(kslam_ctx *c);
+// the n taxonomy ids `lane` has just computed (lane->samw.tax_ids) into owner's state, on lane's stream
+void kreport_count_resident(kslam_ctx *owner, kslam_ctx *lane, uint64_t n);
 
 }  // namespace kslam_api
 

@@ -27,6 +27,7 @@
 #include "../../include/kslam_samunmapped.h"
 #include "../../include/kslam_readsplit.h"
 #include "../../include/kslam_coverage.h"
+#include "../../include/kslam_kreport.h"
 #include "../../include/kslam_variants.h"
 #include "workers.hpp"
 
@@ -75,6 +76,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
   int var_fd = -1;                    // kslam_stream_set_variants: where the VCF file goes
   uint32_t var_min_alt = 2, var_min_depth = 1;
   bool variants_set = false;
+  int kr_fd = -1;                     // kslam_stream_set_kreport: where the Kraken-style report goes
+  bool kreport_set = false;
 
   const int pool_cap = P && P->pool_threads ? (int)P->pool_threads : std::max(2, usable_cpus() - 4);
   Pool::get().add_cap(pool_cap);
@@ -100,6 +103,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     if (ctx) kslam_stream_set_coverage(ctx, -1);          // held for this call alone, like the descriptors below
     if (variants_set) kslam_set_variants(ctx, 0);
     if (ctx) kslam_stream_set_variants(ctx, -1, 2, 1);
+    if (kreport_set) kslam_set_kreport(ctx, 0);
+    if (ctx) kslam_stream_set_kreport(ctx, -1);
     if (ctx) kslam_stream_set_reads_out(ctx, nullptr);   // the descriptors held for this call alone
     if (pairing_set) kslam_set_pairing(ctx, 1, 0, 0.95, 0);
     Pool::get().remove_cap(pool_cap);
@@ -152,6 +157,16 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
           kslam_set_sam_text(ctx, P->sam_fd >= 0 ? 1 : 0, taxdb ? 1 : 0, P->tail.num_sam_alignments, P->tail.sam_xa) != KSLAM_OK)
         fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
       text_set = true;
+    }
+    // the Kraken-style report (include/kslam_kreport.h): the lanes count the taxonomy ids they make, the batches classified here
+    // go in through kslam_kreport_add; the file follows the last batch.  Behind the annotations: they bring the device tree.
+    if (kslam_stream_get_kreport(ctx, &kr_fd) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    if (kr_fd >= 0) {
+      if (!taxdb) fail(KSLAM_ERR_STATE, "the Kraken-style report needs a taxonomy tree (not available with --just-align)");
+      if (!device_text && kslam_set_sam_annotations(ctx, index, taxdb) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      if (kslam_set_kreport(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
+      kreport_set = true;
+      if (kslam_kreport_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
     }
     // BGZF (include/kslam_bgzf.h): every SAM byte goes to the writer compressed -- the lanes compress what they format, the
     // header and any host-formatted batch go through kslam_bgzf_compress here; the EOF marker ends the file
@@ -259,6 +274,7 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       kslam_status tax_status = KSLAM_OK;
       std::string tax_error;
       std::thread tax_thread;
+      const uint32_t *host_ids = nullptr;   // the batch's taxonomy ids when kslam_tail_classify made them here
       auto tax_part = [&] {
           tax_status = guarded([&] {
             const double t1 = now_ms();
@@ -275,6 +291,7 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
               const kslam_status b = kslam_tail_classify(&host_write, &reads, index, taxdb, res.read_pairs, res.n_read_pairs, res.pairs,
                                                          res.n_pairs, all_ids.data() + base, &text, &tlen);
               if (b != KSLAM_OK) fail(b, kslam_tail_last_error());
+              host_ids = all_ids.data() + base;
               wrote = P->per_read_fd < 0 || write_all(P->per_read_fd, text, tlen);
               kslam_free(text);
             }
@@ -433,6 +450,13 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         s = tax_status;
         err = tax_error;
       }
+      // the report: a lane counted the batch unless its ids were made by the classification above
+      if (s == KSLAM_OK && kreport_set && host_ids) {
+        s = guarded([&] {
+          if (kslam_kreport_add(ctx, host_ids, res.n_read_pairs) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+        });
+        if (s != KSLAM_OK) err = g_err;
+      }
       kslam_release_reads_out(ctx, &ro);
       kslam_release_batch(ctx, &res);
       if (s != KSLAM_OK && worker_status == KSLAM_OK) {
@@ -505,6 +529,15 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       uint64_t n_rows = 0, n_skipped = 0;
       if (kslam_coverage_take(ctx, &rows, &n_rows, &n_skipped) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
       const kslam_status w = kslam_coverage_write(index, rows, n_rows, cov_fd);
+      kslam_free_pinned(ctx, rows);
+      if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
+    }
+    if (kreport_set) {
+      kslam_kreport_row *rows = nullptr;
+      uint64_t n_rows = 0;
+      kslam_kreport_stats ks;
+      if (kslam_kreport_take(ctx, &rows, &n_rows, &ks) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      const kslam_status w = kslam_kreport_write(taxdb, rows, n_rows, st.n_pairs, kr_fd);
       kslam_free_pinned(ctx, rows);
       if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
     }

@@ -36,6 +36,7 @@
 #include "../include/kslam_samunmapped.h"
 #include "../include/kslam_readsplit.h"
 #include "../include/kslam_coverage.h"
+#include "../include/kslam_kreport.h"
 #include "../include/kslam_variants.h"
 #include "../include/kslam_stream.h"
 
@@ -69,7 +70,7 @@ void logl(const std::string &s) { g_log.line(s); }
 }
 
 struct Options {
-  std::string db, out, sam, classified_out, unclassified_out, coverage_out, variants_out;
+  std::string db, out, sam, classified_out, unclassified_out, coverage_out, variants_out, kraken_report;
   uint32_t variants_min_alt = 2, variants_min_depth = 1;
   bool variants_min_alt_given = false, variants_min_depth_given = false;
   bool reads_out_bgzf = false;
@@ -128,6 +129,8 @@ void usage(FILE *o) {
         "  --reads-out-bgzf                      write those files as BGZF (--sam-deflate applies)\n"
         "  --coverage-out arg                    write a per-entry coverage table to this file: alignments, unique read pairs,\n"
         "                                        aligned and covered bases, breadth and mean depth (works with --just-align)\n"
+        "  --kraken-report arg                   write a Kraken-style report to this file: percent, clade reads, direct reads, rank code,\n"
+        "                                        taxonomy id and indented name per taxon, as Bracken, Pavian, Krona and MultiQC read it\n"
         "  --variants-out arg                    write the single-base differences between the reads and the entries to this file as\n"
         "                                        VCF 4.2 (sites only: DP, AO, SAF, SAR, AF); works with --just-align, needs no --sam-file\n"
         "  --variants-min-alt arg (=2)           report a site only when at least arg reads carry the alternate base\n"
@@ -139,7 +142,7 @@ Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
          PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT,
-         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH };
+         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, KRAKEN_REPORT };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -165,6 +168,7 @@ Options parse(int argc, char **argv) {
       // not in the reference: include/kslam_variants.h
       {"variants-out", required_argument, nullptr, VARIANTS_OUT}, {"variants-min-alt", required_argument, nullptr, VARIANTS_MIN_ALT},
       {"variants-min-depth", required_argument, nullptr, VARIANTS_MIN_DEPTH},
+      {"kraken-report", required_argument, nullptr, KRAKEN_REPORT},   // not in the reference: include/kslam_kreport.h (Kraken 2's --report)
       {nullptr, 0, nullptr, 0}};
   opterr = 0;
   int c;
@@ -200,6 +204,7 @@ Options parse(int argc, char **argv) {
       case READS_OUT_BGZF: o.reads_out_bgzf = true; break;
       case COVERAGE_OUT: o.coverage_out = optarg; break;
       case VARIANTS_OUT: o.variants_out = optarg; break;
+      case KRAKEN_REPORT: o.kraken_report = optarg; break;
       case VARIANTS_MIN_ALT: o.variants_min_alt = to_u32(optarg, "variants-min-alt"); o.variants_min_alt_given = true; break;
       case VARIANTS_MIN_DEPTH: o.variants_min_depth = to_u32(optarg, "variants-min-depth"); o.variants_min_depth_given = true; break;
       case SAM_DEFLATE:
@@ -221,6 +226,7 @@ Options parse(int argc, char **argv) {
   }
   if (o.sam_deflate_given && !o.sam_bgzf && !o.sam_bam && !o.reads_out_bgzf) die("option '--sam-deflate' needs '--sam-bgzf' or '--sam-bam'");
   if (o.sam_unmapped && o.sam.empty()) die("option '--sam-unmapped' needs '--sam-file'");
+  if (!o.kraken_report.empty() && o.just_align) die("option '--kraken-report' cannot be combined with '--just-align': the report counts taxonomy ids");
   if (o.variants_min_alt_given && o.variants_out.empty()) die("option '--variants-min-alt' needs '--variants-out'");
   if (o.variants_min_depth_given && o.variants_out.empty()) die("option '--variants-min-depth' needs '--variants-out'");
   return o;
@@ -467,6 +473,12 @@ int run(const Options &o, const std::string &command_line) {
     if (coverage_fd < 0) die("unable to open " + o.coverage_out);
     if (kslam_stream_set_coverage(ctx, coverage_fd) != KSLAM_OK) die(std::string("coverage: ") + kslam_last_error(ctx));
   }
+  int kreport_fd = -1;
+  if (!o.kraken_report.empty()) {
+    kreport_fd = open(o.kraken_report.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (kreport_fd < 0) die("unable to open " + o.kraken_report);
+    if (kslam_stream_set_kreport(ctx, kreport_fd) != KSLAM_OK) die(std::string("Kraken-style report: ") + kslam_last_error(ctx));
+  }
   int variants_fd = -1;
   if (!o.variants_out.empty()) {
     variants_fd = open(o.variants_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
@@ -517,6 +529,7 @@ int run(const Options &o, const std::string &command_line) {
     if (fd >= 0 && close(fd) != 0) die("closing a reads-out file failed");
   if (coverage_fd >= 0 && close(coverage_fd) != 0) die("closing the coverage file failed");
   if (variants_fd >= 0 && close(variants_fd) != 0) die("closing the variants file failed");
+  if (kreport_fd >= 0 && close(kreport_fd) != 0) die("closing the Kraken-style report failed");
   logl(cat("Found ", st.n_overlaps, " k-mer overlaps"));
   logl(cat("", st.n_read_pairs_aligned, " entries have k-mer overlaps"));
   if (paired && st.n_batches) logl(cat("Screening all alignment pairs with insert size >= ", st.first_max_insert_size, ""));
