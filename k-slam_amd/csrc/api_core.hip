@@ -244,6 +244,7 @@ void kslam_destroy(kslam_ctx *c) {
     for (auto &ev : c->cov.ev_count) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->var.ev_take) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->kr.ev_take) if (ev) (void)hipEventDestroy(ev);
+    for (auto &ev : c->tr.ev_mask) if (ev) (void)hipEventDestroy(ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
   }
   delete c;   // every DevBuf frees itself, the index with the last context that holds it

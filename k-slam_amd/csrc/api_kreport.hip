@@ -49,6 +49,24 @@ void count_locked(kslam_ctx *owner, const uint32_t *d_ids, uint64_t n, KreportCo
 
 }  // namespace
 
+// the id -> node table of c's device tree: the tree's ids sorted ascending with their nodes (once per switch-on, on the host);
+// for the report's count pass and for the reads of chosen taxa (api_taxreads.hip), each into buffers of its own
+void id_node_table(kslam_ctx *c, DevBuf &d_keys, DevBuf &d_nodes) {
+  const uint64_t N = c->annot.n_nodes;
+  if (N >= (1ull << 32)) throw StatusError{KSLAM_ERR_UNSUPPORTED, "2^32 or more taxonomy nodes"};
+  std::vector<uint32_t> tax(N + 1), order(N + 1), keys(N + 1);
+  if (N) HIPCHK(hipMemcpyAsync(tax.data(), c->annot.node_tax, N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(stream_wait(c->stream));
+  for (uint64_t n = 0; n < N; n++) order[n] = (uint32_t)n;
+  std::sort(order.begin(), order.begin() + N, [&](uint32_t a, uint32_t b) { return tax[a] != tax[b] ? tax[a] < tax[b] : a < b; });
+  for (uint64_t n = 0; n < N; n++) keys[n] = tax[order[n]];
+  d_keys.ensure((N + 1) * sizeof(uint32_t));
+  d_nodes.ensure((N + 1) * sizeof(uint32_t));
+  if (N) HIPCHK(hipMemcpyAsync(d_keys.p, keys.data(), N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  if (N) HIPCHK(hipMemcpyAsync(d_nodes.p, order.data(), N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(stream_wait(c->stream));   // (the vectors may go)
+}
+
 void kreport_release(kslam_ctx *c) {
   kslam_ctx::Kreport &v = c->kr;
   std::lock_guard<std::mutex> lk(v.mu);
@@ -86,21 +104,11 @@ kslam_status kslam_set_kreport(kslam_ctx *c, int on) {
     if (v.on.load(std::memory_order_acquire)) return;
     const uint64_t N = c->annot.n_nodes;
     if (N >= (1ull << 32)) throw StatusError{KSLAM_ERR_UNSUPPORTED, "2^32 or more taxonomy nodes"};
-    // the id -> node table: the tree's ids sorted ascending with their nodes (once per switch-on, on the host)
-    std::vector<uint32_t> tax(N + 1), order(N + 1), keys(N + 1);
-    if (N) HIPCHK(hipMemcpyAsync(tax.data(), c->annot.node_tax, N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(stream_wait(c->stream));
-    for (uint64_t n = 0; n < N; n++) order[n] = (uint32_t)n;
-    std::sort(order.begin(), order.begin() + N, [&](uint32_t a, uint32_t b) { return tax[a] != tax[b] ? tax[a] < tax[b] : a < b; });
-    for (uint64_t n = 0; n < N; n++) keys[n] = tax[order[n]];
     v.n_nodes = N;
     try {
       v.direct.ensure((N + 1) * sizeof(uint64_t));
-      v.keys.ensure((N + 1) * sizeof(uint32_t));
-      v.nodes.ensure((N + 1) * sizeof(uint32_t));
-      if (N) HIPCHK(hipMemcpyAsync(v.keys.p, keys.data(), N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-      if (N) HIPCHK(hipMemcpyAsync(v.nodes.p, order.data(), N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-      zero_state(c);   // (waits: the vectors may go)
+      id_node_table(c, v.keys, v.nodes);
+      zero_state(c);
       if (!v.ev_take[0])
         for (auto &e : v.ev_take) HIPCHK(hipEventCreate(&e));
     } catch (...) {

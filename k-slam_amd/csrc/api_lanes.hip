@@ -208,6 +208,23 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
       if (st == KSLAM_OK && primary->samtext.per_read && primary->kr.on.load(std::memory_order_acquire))
         st = guarded(c, [&] { kreport_count_resident(primary, c, sam.n_groups); });
     }
+    // (kslam_set_taxon_reads) the records of the read pairs whose taxonomy id is in the chosen set, cut out of the text this lane
+    // uploaded: on this lane's stream and outside the compute token, like the split below.  The flag pass reads samw.tax_ids
+    // and the groups k_lca saw (sam.d_groups); both are device buffers of this lane that live until its next batch
+    // (sam_stage_free hands back only the page-locked host blocks), but the call stands in front of it all the same.  A batch
+    // whose ids this lane did not make -- pseudo-assembly left to the host, the host's text, no per-read stage -- is left to
+    // the host twin.
+    if (primary->tr.on.load(std::memory_order_acquire)) {
+      job->tr_on = true;
+      job->tr_supported = job->fastq_text && primary->pairing.stages != 0;
+      if (st == KSLAM_OK && job->tr_supported) {
+        if (!(sam_planned && primary->samtext.per_read)) job->tr.flags = KSLAM_READS_OUT_LEFT_TO_HOST;
+        else st = guarded(c, [&] {
+          taxreads_resident(primary, c, job->single, sam.d_groups, c->samw.tax_ids.as<uint32_t>(), sam.n_groups, primary->reads_out.bgzf,
+                            primary->samtext.deflate, &job->tr);
+        });
+      }
+    }
     sam_stage_free(c, sam);
     // (kslam_set_reads_out) the records split by outcome, cut out of the text this lane uploaded.  Outside the compute token as
     // well: a streaming copy next to the other lane's alignment kernels.  A batch whose pseudo-assembly is left to the host
@@ -316,6 +333,7 @@ void stop_lanes(kslam_ctx *c) {
   }
   c->jobs.clear();
   c->ro_ready.clear();   // (their blocks went with the lanes' page-locked pools)
+  c->tr_ready.clear();
   c->as_stop = false;
 }
 
@@ -547,8 +565,17 @@ kslam_status kslam_collect_batch(kslam_ctx *c, uint64_t ticket, kslam_batch_resu
       }
       c->ro_ready[ticket] = kslam_ctx::ReadsOutEntry{job->ro_supported, job->ro};
     }
+    if (job->tr_on) {   // kept for kslam_collect_taxon_reads
+      std::lock_guard<std::mutex> lk(c->as_mu);
+      while (c->tr_ready.size() >= 16) {
+        free_reads_out(c, &c->tr_ready.begin()->second.out);
+        c->tr_ready.erase(c->tr_ready.begin());
+      }
+      c->tr_ready[ticket] = kslam_ctx::ReadsOutEntry{job->tr_supported, job->tr};
+    }
   } else {
     free_reads_out(c, &job->ro);
+    free_reads_out(c, &job->tr);
     kslam_free_pinned(c, job->sam_text);
     kslam_free_pinned(c, job->pr_text);
     kslam_free_pinned(c, job->tax);

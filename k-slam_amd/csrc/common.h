@@ -642,6 +642,54 @@ struct ReadSplitWork {
 // bytes[k] long, n_records[0] classified and n_records[1] unclassified records per stream.  Waits for the stream (the sizes are read back).
 void read_split_device(const FqStream st[2], bool single, const kslam_read_pair *d_groups, uint64_t n_groups, uint32_t which,
                        ReadSplitWork &W, uint64_t bytes[4], uint64_t n_records[2], hipStream_t s);
+// The same in two halves, for a caller that flags the records itself (taxreads.hip): read_split_prepare sizes the buffers,
+// zeroes W.flag (one byte per record of the batch, [R1 | R2]) and the totals and returns the number of records; the caller
+// records W.ev[0], runs its flag pass on s and calls read_split_flagged for the lengths, scans and copy (flagged records are
+// the "classified" streams).
+uint64_t read_split_prepare(const FqStream st[2], bool single, ReadSplitWork &W, hipStream_t s);
+void read_split_flagged(const FqStream st[2], bool single, uint32_t which, ReadSplitWork &W, uint64_t bytes[4], uint64_t n_records[2],
+                        hipStream_t s);
+
+// ------------------------------------------------------------ taxreads.hip
+// The reads of chosen taxa (include/kslam_taxreads.h).  The selection belongs to the context kslam_set_taxon_reads was called
+// on (context.h: kslam_ctx::TaxReads); its lanes only read it.
+struct TaxReadsSel {               // what the flag pass sees
+  const uint32_t *keys;           // [n_nodes] the tree's taxonomy ids, ascending
+  const uint32_t *nodes;          // [n_nodes] the node of keys[i]
+  uint64_t n_nodes;
+  const uint8_t *mask;            // [n_nodes] 1: the node's id is in S
+  const uint32_t *unknown;        // [n_unknown] the chosen ids the tree does not know, ascending and distinct
+  uint64_t n_unknown;
+  int all_nonzero;                // id 1 chosen with CHILDREN: every non-zero id is in S
+};
+struct TaxReadsMaskWork {
+  SortWorkspace sortws;
+  DevBuf ids, seed, items_a, items_b, head, run, cursor, scan_tmp, totals;
+};
+struct TaxReadsFlagWork {
+  DevBuf count;                   // matched read pairs of the batch: 32 counters on cache lines of their own, and their sum
+  hipEvent_t ev[2]{};             // around the flag launch
+  float ms = 0;                   // its device time, last batch
+  uint64_t n_matched = 0;
+  TaxReadsFlagWork() = default;
+  TaxReadsFlagWork(const TaxReadsFlagWork &) = delete;
+  TaxReadsFlagWork &operator=(const TaxReadsFlagWork &) = delete;
+  ~TaxReadsFlagWork() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+// S from n chosen ids (host memory, none of them 0): d_mask[0 .. n_nodes) is written, the unknown chosen ids go to `unknown`
+// (u32, ascending, distinct; *n_unknown of them), *all_nonzero as in TaxReadsSel.  ev: two events around the launches.  Waits
+// for the stream.
+void taxreads_mask_device(const uint32_t *h_ids, uint64_t n, uint32_t mode, const uint32_t *d_keys, const uint32_t *d_nodes, uint64_t n_nodes,
+                          const uint32_t *d_up, const uint32_t *d_depth, TaxReadsMaskWork &W, uint8_t *d_mask, DevBuf &unknown,
+                          uint64_t *n_unknown, int *all_nonzero, hipEvent_t ev[2], hipStream_t s);
+// flag[r1_read] = flag[r2_read] = 1 for every read pair g whose d_ids[g] is in S; n_total: the records of the batch (the
+// flag array's length).  Does not wait: W.n_matched and W.ms are read by taxreads_flag_finish once the stream has been waited for.
+void taxreads_flag_device(const kslam_read_pair *d_groups, const uint32_t *d_ids, uint64_t n_groups, int paired, uint64_t n_total,
+                          const TaxReadsSel &S, uint8_t *d_flag, TaxReadsFlagWork &W, hipStream_t s);
+void taxreads_flag_finish(TaxReadsFlagWork &W, hipStream_t s);
 
 // ------------------------------------------------------------ coverage.hip
 // The per-entry coverage table (include/kslam_coverage.h).  CoverageState belongs to the context the switch was set on; its

@@ -24,6 +24,7 @@
 #include "../../include/kslam_coverage.h"
 #include "../../include/kslam_variants.h"
 #include "../../include/kslam_kreport.h"
+#include "../../include/kslam_taxreads.h"
 #include "../host/workers.hpp"
 #include "../host/inflate.hpp"
 #include <algorithm>
@@ -188,6 +189,28 @@ struct kslam_ctx {
   } kr;
   KreportCountWork krw;           // this context's own count passes (a lane's batches; on the primary: kslam_kreport_add)
 
+  // ---- the reads of chosen taxa (taxreads.hip, include/kslam_taxreads.h) ----
+  struct TaxReads {               // on the context kslam_set_taxon_reads was called on; its lanes read it (lane_main)
+    std::atomic<bool> on{false};
+    std::vector<uint32_t> ids;    // the chosen ids as they were set
+    uint32_t mode = 0;
+    uint64_t n_nodes = 0;         // of the device tree the mask was laid out for
+    DevBuf keys, nodes;           // the id -> node table
+    DevBuf mask, unknown;         // one byte per node; the unknown chosen ids (u32, ascending, distinct), n_unknown of them
+    uint64_t n_unknown = 0;
+    int all_nonzero = 0;
+    TaxReadsMaskWork mw;
+    DevBuf up_groups, up_ids;     // kslam_taxon_reads_text's uploads
+    hipEvent_t ev_mask[2]{};
+    double mask_ms = 0, flag_ms = 0, copy_ms = 0;   // kslam_taxon_reads_kernel_ms
+    uint64_t bytes_moved = 0;
+    int fds[2] = {-1, -1};        // kslam_stream_set_taxon_reads
+    std::mutex mu;                // the switch and the mask's read-back: one at a time
+  } tr;
+  ReadSplitWork tr_rsw;           // this context's own selections (a lane's batches; on the primary: kslam_taxon_reads_text):
+  TaxReadsFlagWork trw;           // apart from rsw, so that the split and the selection of one batch do not share a buffer
+  std::map<uint64_t, ReadsOutEntry> tr_ready;   // by ticket, as ro_ready: for kslam_collect_taxon_reads (under as_mu)
+
   // ---- device pairing / screens (pairs.hip) ----
   PairWork pw;
   PairResult pres{};
@@ -226,6 +249,8 @@ struct kslam_ctx {
     uint32_t text_flags = 0;
     bool ro_on = false, ro_supported = false;   // kslam_set_reads_out was on when the lane ran the batch; it came as FASTQ text
     kslam_reads_out ro{};
+    bool tr_on = false, tr_supported = false;   // the same for kslam_set_taxon_reads
+    kslam_reads_out tr{};
   };
   struct AsyncLane {
     kslam_ctx *c = nullptr;
@@ -365,6 +390,16 @@ void variants_emit_resident(kslam_ctx *owner, kslam_ctx *lane);
 void kreport_release(kslam_ctx *c);
 // the n taxonomy ids `lane` has just computed (lane->samw.tax_ids) into owner's state, on lane's stream
 void kreport_count_resident(kslam_ctx *owner, kslam_ctx *lane, uint64_t n);
+// the id -> node table of c's device tree (c->annot), uploaded into the two buffers; waits for c's stream
+void id_node_table(kslam_ctx *c, DevBuf &d_keys, DevBuf &d_nodes);
+
+// ---- api_taxreads.hip
+// frees the selection of c and switches it off (kslam_set_taxon_reads(c, NULL, 0, 0), kslam_set_sam_annotations, kslam_set_index)
+void taxreads_release(kslam_ctx *c);
+// the batch resident on c (indexed by fastq_index_device: c->fqw) selected by owner's S: d_ids[g] is the taxonomy id of
+// d_groups[g].  Blocks from c's page-locked pool: out->data[0] / [1] the selected R1 / R2.
+void taxreads_resident(kslam_ctx *owner, kslam_ctx *c, bool single, const kslam_read_pair *d_groups, const uint32_t *d_ids, uint64_t n_groups,
+                       bool bgzf, int deflate, kslam_reads_out *out);
 
 }  // namespace kslam_api
 

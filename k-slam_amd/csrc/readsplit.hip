@@ -12,6 +12,9 @@
 //                    the others line by line with a "\n" after each.  A span moves as aligned 16-byte stores fed by
 //                    16-byte loads at whatever alignment the source has, with a byte head and tail.
 // A pure streaming copy: 2 bytes of traffic per output byte, plus 25 bytes of index per record.
+// Steps 2 to 4 also serve a caller that flags the records by a rule of its own (taxreads.hip: the reads of chosen taxa):
+// read_split_prepare sizes and zeroes, the caller flags, read_split_flagged does the rest; read_split_device is the two
+// around k_rs_flags.
 #include "common.h"
 #include "fastq_lines.h"
 #include "../../include/kslam_readsplit.h"
@@ -110,13 +113,9 @@ __global__ __launch_bounds__(256) void k_rs_copy(FqStream s, const uint8_t *__re
 
 }  // namespace
 
-void read_split_device(const FqStream st[2], bool single, const kslam_read_pair *d_groups, uint64_t n_groups, uint32_t which,
-                       ReadSplitWork &W, uint64_t bytes[4], uint64_t n_records[2], hipStream_t s) {
-  const int n_streams = single ? 1 : 2;
+uint64_t read_split_prepare(const FqStream st[2], bool single, ReadSplitWork &W, hipStream_t s) {
   const uint64_t n = st[0].n + (single ? 0 : st[1].n);
   if (n >= (1ull << 32)) throw StatusError{KSLAM_ERR_UNSUPPORTED, "2^32 or more records in one batch"};
-  for (int k = 0; k < 4; k++) bytes[k] = 0;
-  n_records[0] = n_records[1] = 0;
   W.kernel_ms = 0;
   W.bytes_moved = 0;
   if (!W.ev[0])
@@ -129,13 +128,29 @@ void read_split_device(const FqStream st[2], bool single, const kslam_read_pair 
   W.off_unsel.ensure((n + 1) * sizeof(uint64_t));
   W.scan_tmp.ensure(scan_tmp_bytes(std::max<uint64_t>(n, 1)));
   W.totals.ensure(8 * sizeof(uint64_t));
-  uint64_t *tot = W.totals.as<uint64_t>();   // [k] selected bytes of stream k, [2 + k] unselected, [4 + k] selected records, [6] errors
-  HIPCHK(hipMemsetAsync(tot, 0, 8 * sizeof(uint64_t), s));
+  HIPCHK(hipMemsetAsync(W.totals.p, 0, 8 * sizeof(uint64_t), s));
   HIPCHK(hipMemsetAsync(W.flag.p, 0, n + 16, s));
+  return n;
+}
+
+void read_split_device(const FqStream st[2], bool single, const kslam_read_pair *d_groups, uint64_t n_groups, uint32_t which,
+                       ReadSplitWork &W, uint64_t bytes[4], uint64_t n_records[2], hipStream_t s) {
+  for (int k = 0; k < 4; k++) bytes[k] = 0;
+  n_records[0] = n_records[1] = 0;
+  const uint64_t n = read_split_prepare(st, single, W, s);
   HIPCHK(hipEventRecord(W.ev[0], s));
   if (n_groups)
     hipLaunchKernelGGL(k_rs_flags, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, s, d_groups, n_groups, single ? 0 : 1, n,
                        W.flag.as<uint8_t>());
+  read_split_flagged(st, single, which, W, bytes, n_records, s);
+}
+
+void read_split_flagged(const FqStream st[2], bool single, uint32_t which, ReadSplitWork &W, uint64_t bytes[4], uint64_t n_records[2],
+                        hipStream_t s) {
+  const int n_streams = single ? 1 : 2;
+  for (int k = 0; k < 4; k++) bytes[k] = 0;
+  n_records[0] = n_records[1] = 0;
+  uint64_t *tot = W.totals.as<uint64_t>();   // [k] selected bytes of stream k, [2 + k] unselected, [4 + k] selected records, [6] errors
   for (int k = 0; k < n_streams; k++) {
     if (!st[k].n) continue;
     hipLaunchKernelGGL(k_rs_lengths, dim3((unsigned)((st[k].n + 255) / 256)), dim3(256), 0, s, st[k], W.flag.as<uint8_t>(),

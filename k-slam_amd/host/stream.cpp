@@ -28,6 +28,7 @@
 #include "../../include/kslam_readsplit.h"
 #include "../../include/kslam_coverage.h"
 #include "../../include/kslam_kreport.h"
+#include "../../include/kslam_taxreads.h"
 #include "../../include/kslam_variants.h"
 #include "workers.hpp"
 
@@ -78,6 +79,11 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
   bool variants_set = false;
   int kr_fd = -1;                     // kslam_stream_set_kreport: where the Kraken-style report goes
   bool kreport_set = false;
+  int tr_fds[2] = {-1, -1};           // kslam_stream_set_taxon_reads: where the selected R1 / R2 records go
+  bool taxreads_on = false, taxreads_set = false;
+  std::vector<uint32_t> tr_ids;       // the chosen ids and the mode, as kslam_set_taxon_reads was given them before this call
+  uint32_t tr_mode = 0;
+  int tr_bgzf = 0;
 
   const int pool_cap = P && P->pool_threads ? (int)P->pool_threads : std::max(2, usable_cpus() - 4);
   Pool::get().add_cap(pool_cap);
@@ -105,6 +111,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     if (ctx) kslam_stream_set_variants(ctx, -1, 2, 1);
     if (kreport_set) kslam_set_kreport(ctx, 0);
     if (ctx) kslam_stream_set_kreport(ctx, -1);
+    if (taxreads_set) kslam_set_taxon_reads(ctx, nullptr, 0, 0);
+    if (ctx) kslam_stream_set_taxon_reads(ctx, nullptr);
     if (ctx) kslam_stream_set_reads_out(ctx, nullptr);   // the descriptors held for this call alone
     if (pairing_set) kslam_set_pairing(ctx, 1, 0, 0.95, 0);
     Pool::get().remove_cap(pool_cap);
@@ -133,6 +141,21 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       if (kslam_set_reads_out(ctx, ro_which) != KSLAM_OK || kslam_get_reads_out_bgzf(ctx, &ro_bgzf) != KSLAM_OK)
         fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
       reads_out_set = true;
+    }
+    // the reads of chosen taxa (include/kslam_taxreads.h): the ids are read NOW -- the annotations set below drop the selection
+    // with the old tree -- and set again behind them
+    if (kslam_stream_get_taxon_reads(ctx, tr_fds) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    if (!paired) tr_fds[1] = -1;
+    taxreads_on = tr_fds[0] >= 0 || tr_fds[1] >= 0;
+    if (taxreads_on) {
+      if (!taxdb) fail(KSLAM_ERR_STATE, "the reads of chosen taxa need a taxonomy tree (not available with --just-align)");
+      uint32_t *ids = nullptr;
+      uint64_t n_ids = 0;
+      if (kslam_get_taxon_reads(ctx, &ids, &n_ids, &tr_mode) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      tr_ids.assign(ids, ids + n_ids);
+      kslam_free(ids);
+      if (tr_ids.empty()) fail(KSLAM_ERR_STATE, "kslam_stream_set_taxon_reads without chosen ids: call kslam_set_taxon_reads first");
+      if (kslam_get_reads_out_bgzf(ctx, &tr_bgzf) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
     }
     // the per-entry coverage table (include/kslam_coverage.h): the lanes mark what they finish; the report follows the last batch
     if (kslam_stream_get_coverage(ctx, &cov_fd) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
@@ -163,10 +186,19 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     if (kslam_stream_get_kreport(ctx, &kr_fd) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
     if (kr_fd >= 0) {
       if (!taxdb) fail(KSLAM_ERR_STATE, "the Kraken-style report needs a taxonomy tree (not available with --just-align)");
-      if (!device_text && kslam_set_sam_annotations(ctx, index, taxdb) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+    }
+    if ((kr_fd >= 0 || taxreads_on) && !device_text && kslam_set_sam_annotations(ctx, index, taxdb) != KSLAM_OK)
+      fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+    if (kr_fd >= 0) {
       if (kslam_set_kreport(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
       kreport_set = true;
       if (kslam_kreport_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+    }
+    // the chosen taxa again, on the tree that is on the device now: the lanes select the batches whose ids they make, the others
+    // go through kslam_tail_taxon_reads behind the classification on this side
+    if (taxreads_on) {
+      if (kslam_set_taxon_reads(ctx, tr_ids.data(), tr_ids.size(), tr_mode) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
+      taxreads_set = true;
     }
     // BGZF (include/kslam_bgzf.h): every SAM byte goes to the writer compressed -- the lanes compress what they format, the
     // header and any host-formatted batch go through kslam_bgzf_compress here; the EOF marker ends the file
@@ -268,8 +300,33 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         if (!ok) fail(KSLAM_ERR_ARG, std::string("writing a reads-out file failed: ") + strerror(errno));
       }
     };
-    auto host_stage = [&](kslam_batch_result res, kslam_reads_out ro, Window win) {
+    // The selected records of one batch to their files, likewise; `ids`: the batch's taxonomy ids, final by now.
+    auto write_taxon_reads = [&](const kslam_batch_result &res, kslam_reads_out &tro, Window win, const uint32_t *ids) {
+      if ((tro.flags & KSLAM_READS_OUT_LEFT_TO_HOST) || host_split) {
+        kslam_release_reads_out(ctx, &tro);
+        if (kslam_tail_taxon_reads(taxdb, tr_ids.data(), tr_ids.size(), tr_mode, r1 + win.p1, win.e1 - win.p1, paired ? r2 + win.p2 : nullptr,
+                                   paired ? win.e2 - win.p2 : 0, 0, 1, res.read_pairs, ids, res.n_read_pairs, &tro) != KSLAM_OK)
+          fail(KSLAM_ERR_ARG, kslam_tail_last_error());
+      }
+      for (int k = 0; k < 2; k++) {
+        if (tr_fds[k] < 0 || !tro.len[k]) continue;
+        bool ok;
+        if (tr_bgzf && !(tro.flags & KSLAM_READS_OUT_BGZF)) {
+          char *z = nullptr;
+          uint64_t zlen = 0;
+          if (kslam_bgzf_compress(ctx, tro.data[k], tro.len[k], &z, &zlen) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+          ok = write_all(tr_fds[k], z, zlen);
+          kslam_free_pinned(ctx, z);
+        } else {
+          if (!tr_bgzf && (tro.flags & KSLAM_READS_OUT_BGZF)) fail(KSLAM_ERR_STATE, "kslam_set_reads_out_bgzf was changed while kslam_stream_classify was running");
+          ok = write_all(tr_fds[k], tro.data[k], tro.len[k]);
+        }
+        if (!ok) fail(KSLAM_ERR_ARG, std::string("writing a file of selected reads failed: ") + strerror(errno));
+      }
+    };
+    auto host_stage = [&](kslam_batch_result res, kslam_reads_out ro, kslam_reads_out tro, Window win) {
       name_thread("kslam-host");
+      const size_t ids_base = all_ids.size();   // where tax_part puts this batch's ids
       kslam_reads_view reads = {res.n_reads, nullptr, res.reads_bases_off, nullptr, res.reads_bases_off, res.reads_ids, res.reads_ids_off};
       kslam_status tax_status = KSLAM_OK;
       std::string tax_error;
@@ -457,6 +514,12 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         });
         if (s != KSLAM_OK) err = g_err;
       }
+      // the selection: behind the classification, whose ids the host twin needs for a batch no lane selected
+      if (s == KSLAM_OK && taxreads_set) {
+        s = guarded([&] { write_taxon_reads(res, tro, win, all_ids.data() + ids_base); });
+        if (s != KSLAM_OK) err = g_err;
+      }
+      kslam_release_reads_out(ctx, &tro);
       kslam_release_reads_out(ctx, &ro);
       kslam_release_batch(ctx, &res);
       if (s != KSLAM_OK && worker_status == KSLAM_OK) {
@@ -501,22 +564,33 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         kslam_release_batch(ctx, &res);
         fail(rs, kslam_last_error(ctx));
       }
+      kslam_reads_out tro;
+      memset(&tro, 0, sizeof tro);
+      const kslam_status ts = taxreads_set ? kslam_collect_taxon_reads(ctx, tk, &tro) : KSLAM_OK;
+      if (ts != KSLAM_OK) {
+        kslam_release_reads_out(ctx, &ro);
+        kslam_release_batch(ctx, &res);
+        fail(ts, kslam_last_error(ctx));
+      }
       if (worker_status != KSLAM_OK) {
+        kslam_release_reads_out(ctx, &tro);
         kslam_release_reads_out(ctx, &ro);
         kslam_release_batch(ctx, &res);
         fail(worker_status, worker_error);
       }
       if (res.n_reads == 0) {          // an empty batch ends the loop (src/SLAM.h:207)
+        kslam_release_reads_out(ctx, &tro);
         kslam_release_reads_out(ctx, &ro);
         kslam_release_batch(ctx, &res);
         break;
       }
       if (!res.read_pairs && res.n_overlaps) {
+        kslam_release_reads_out(ctx, &tro);
         kslam_release_reads_out(ctx, &ro);
         kslam_release_batch(ctx, &res);
         fail(KSLAM_ERR_INTERNAL, "the lane returned no device pairing");
       }
-      worker = std::thread(host_stage, res, ro, win);
+      worker = std::thread(host_stage, res, ro, tro, win);
     }
     if (worker.joinable()) worker.join();
     if (worker_status != KSLAM_OK) fail(worker_status, worker_error);
@@ -524,6 +598,9 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     if (ro_which && ro_bgzf)
       for (int k = 0; k < 4; k++)
         if (ro_fds[k] >= 0 && !write_all(ro_fds[k], KSLAM_BGZF_EOF, KSLAM_BGZF_EOF_LEN)) fail(KSLAM_ERR_ARG, "writing a reads-out file's BGZF EOF marker failed");
+    if (taxreads_set && tr_bgzf)
+      for (int k = 0; k < 2; k++)
+        if (tr_fds[k] >= 0 && !write_all(tr_fds[k], KSLAM_BGZF_EOF, KSLAM_BGZF_EOF_LEN)) fail(KSLAM_ERR_ARG, "writing the BGZF EOF marker of a file of selected reads failed");
     if (coverage_set) {
       kslam_entry_coverage *rows = nullptr;
       uint64_t n_rows = 0, n_skipped = 0;

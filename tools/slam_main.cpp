@@ -37,6 +37,8 @@
 #include "../include/kslam_readsplit.h"
 #include "../include/kslam_coverage.h"
 #include "../include/kslam_kreport.h"
+#include "../include/kslam_samtext.h"
+#include "../include/kslam_taxreads.h"
 #include "../include/kslam_variants.h"
 #include "../include/kslam_stream.h"
 
@@ -74,6 +76,9 @@ struct Options {
   uint32_t variants_min_alt = 2, variants_min_depth = 1;
   bool variants_min_alt_given = false, variants_min_depth_given = false;
   bool reads_out_bgzf = false;
+  std::string extract_out;                 // --extract-out (include/kslam_taxreads.h)
+  std::vector<uint32_t> extract_taxids;    // --extract-taxid, repeatable and comma lists
+  bool extract_children = false, extract_parents = false, extract_exclude = false;
   uint32_t score_threshold = 0, match = 2, mismatch = 3, gap_open = 5, gap_extend = 2;
   uint32_t num_reads = UINT32_MAX, num_reads_at_once = 10000000, num_alignments = 10;
   double score_fraction = 0.95;
@@ -131,6 +136,13 @@ void usage(FILE *o) {
         "                                        aligned and covered bases, breadth and mean depth (works with --just-align)\n"
         "  --kraken-report arg                   write a Kraken-style report to this file: percent, clade reads, direct reads, rank code,\n"
         "                                        taxonomy id and indented name per taxon, as Bracken, Pavian, Krona and MultiQC read it\n"
+        "  --extract-taxid arg                   choose a taxonomy id (repeatable; a comma list is accepted): the reads classified to it go\n"
+        "                                        to --extract-out, as KrakenTools' extract_kraken_reads.py -t writes them\n"
+        "  --extract-out arg                     the FASTQ file for the reads of the chosen taxa; with R1FILE and R2FILE arg must contain\n"
+        "                                        a '#', replaced by 1 and 2 (--reads-out-bgzf and --sam-deflate apply)\n"
+        "  --extract-include-children            also the reads of every taxon below a chosen one\n"
+        "  --extract-include-parents             also the reads of every taxon on the way from a chosen one up to the root\n"
+        "  --extract-exclude                     write every read that does NOT match instead (reads without alignment included)\n"
         "  --variants-out arg                    write the single-base differences between the reads and the entries to this file as\n"
         "                                        VCF 4.2 (sites only: DP, AO, SAF, SAR, AF); works with --just-align, needs no --sam-file\n"
         "  --variants-min-alt arg (=2)           report a site only when at least arg reads carry the alternate base\n"
@@ -142,7 +154,7 @@ Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
          PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT,
-         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, KRAKEN_REPORT };
+         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -169,6 +181,10 @@ Options parse(int argc, char **argv) {
       {"variants-out", required_argument, nullptr, VARIANTS_OUT}, {"variants-min-alt", required_argument, nullptr, VARIANTS_MIN_ALT},
       {"variants-min-depth", required_argument, nullptr, VARIANTS_MIN_DEPTH},
       {"kraken-report", required_argument, nullptr, KRAKEN_REPORT},   // not in the reference: include/kslam_kreport.h (Kraken 2's --report)
+      // not in the reference: include/kslam_taxreads.h (KrakenTools' extract_kraken_reads.py)
+      {"extract-taxid", required_argument, nullptr, EXTRACT_TAXID}, {"extract-out", required_argument, nullptr, EXTRACT_OUT},
+      {"extract-include-children", no_argument, nullptr, EXTRACT_CHILDREN}, {"extract-include-parents", no_argument, nullptr, EXTRACT_PARENTS},
+      {"extract-exclude", no_argument, nullptr, EXTRACT_EXCLUDE},
       {nullptr, 0, nullptr, 0}};
   opterr = 0;
   int c;
@@ -205,6 +221,24 @@ Options parse(int argc, char **argv) {
       case COVERAGE_OUT: o.coverage_out = optarg; break;
       case VARIANTS_OUT: o.variants_out = optarg; break;
       case KRAKEN_REPORT: o.kraken_report = optarg; break;
+      case EXTRACT_OUT: o.extract_out = optarg; break;
+      case EXTRACT_CHILDREN: o.extract_children = true; break;
+      case EXTRACT_PARENTS: o.extract_parents = true; break;
+      case EXTRACT_EXCLUDE: o.extract_exclude = true; break;
+      case EXTRACT_TAXID: {   // one id or a comma list; every piece a number other than 0
+        const std::string arg = optarg;
+        size_t at = 0;
+        for (;;) {
+          const size_t comma = arg.find(',', at);
+          const std::string piece = arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+          const uint32_t id = to_u32(piece.c_str(), "extract-taxid");
+          if (id == 0) die("the argument ('" + arg + "') for option '--extract-taxid' is invalid: taxonomy id 0 cannot be chosen (see '--unclassified-out')");
+          o.extract_taxids.push_back(id);
+          if (comma == std::string::npos) break;
+          at = comma + 1;
+        }
+        break;
+      }
       case VARIANTS_MIN_ALT: o.variants_min_alt = to_u32(optarg, "variants-min-alt"); o.variants_min_alt_given = true; break;
       case VARIANTS_MIN_DEPTH: o.variants_min_depth = to_u32(optarg, "variants-min-depth"); o.variants_min_depth_given = true; break;
       case SAM_DEFLATE:
@@ -227,6 +261,13 @@ Options parse(int argc, char **argv) {
   if (o.sam_deflate_given && !o.sam_bgzf && !o.sam_bam && !o.reads_out_bgzf) die("option '--sam-deflate' needs '--sam-bgzf' or '--sam-bam'");
   if (o.sam_unmapped && o.sam.empty()) die("option '--sam-unmapped' needs '--sam-file'");
   if (!o.kraken_report.empty() && o.just_align) die("option '--kraken-report' cannot be combined with '--just-align': the report counts taxonomy ids");
+  if (o.just_align && (!o.extract_taxids.empty() || !o.extract_out.empty()))
+    die(std::string("option '--") + (o.extract_taxids.empty() ? "extract-out" : "extract-taxid") + "' cannot be combined with '--just-align': the reads are chosen by taxonomy id");
+  if (!o.extract_taxids.empty() && o.extract_out.empty()) die("option '--extract-taxid' needs '--extract-out'");
+  if (o.extract_taxids.empty() && !o.extract_out.empty()) die("option '--extract-out' needs '--extract-taxid'");
+  if (o.extract_children && o.extract_taxids.empty()) die("option '--extract-include-children' needs '--extract-taxid'");
+  if (o.extract_parents && o.extract_taxids.empty()) die("option '--extract-include-parents' needs '--extract-taxid'");
+  if (o.extract_exclude && o.extract_taxids.empty()) die("option '--extract-exclude' needs '--extract-taxid'");
   if (o.variants_min_alt_given && o.variants_out.empty()) die("option '--variants-min-alt' needs '--variants-out'");
   if (o.variants_min_depth_given && o.variants_out.empty()) die("option '--variants-min-depth' needs '--variants-out'");
   return o;
@@ -398,6 +439,19 @@ int run(const Options &o, const std::string &command_line) {
     reads_out_names[2 * k] = paired ? name.substr(0, at) + "1" + name.substr(at + 1) : name;
     if (paired) reads_out_names[2 * k + 1] = name.substr(0, at) + "2" + name.substr(at + 1);
   }
+  // --extract-out: the same rule
+  std::string extract_names[2];
+  const bool want_extract = !o.extract_out.empty();
+  if (want_extract) {
+    const size_t at = o.extract_out.find('#');
+    if (paired && at == std::string::npos) {
+      fprintf(stderr, "SLAM: with R1FILE and R2FILE the argument of '--%s' must contain a '#' (replaced by 1 and 2)\n", "extract-out");
+      usage(stderr);
+      exit(1);
+    }
+    extract_names[0] = paired ? o.extract_out.substr(0, at) + "1" + o.extract_out.substr(at + 1) : o.extract_out;
+    if (paired) extract_names[1] = o.extract_out.substr(0, at) + "2" + o.extract_out.substr(at + 1);
+  }
   logl("Performing metagenomic analysis");
   if (o.db.empty()) die("the option '--db' is required but missing");
   // ---- taxDB + database (src/SLAM.h:172-176) ----
@@ -428,8 +482,8 @@ int run(const Options &o, const std::string &command_line) {
   if (kslam_create(&kp, &ctx) != KSLAM_OK) die(std::string("GPU context: ") + (ctx ? kslam_last_error(ctx) : "kslam_create failed"));
   if (o.sam_bgzf && want_sam && kslam_set_sam_bgzf(ctx, 1) != KSLAM_OK) die(std::string("BGZF: ") + kslam_last_error(ctx));
   if (o.sam_bam && want_sam && kslam_set_sam_bam(ctx, 1) != KSLAM_OK) die(std::string("BAM: ") + kslam_last_error(ctx));
-  if (o.reads_out_bgzf && want_reads_out && kslam_set_reads_out_bgzf(ctx, 1) != KSLAM_OK) die(std::string("reads out: ") + kslam_last_error(ctx));
-  if ((want_sam || (want_reads_out && o.reads_out_bgzf)) && kslam_set_bgzf_deflate(ctx, o.sam_deflate) != KSLAM_OK) die(std::string("BGZF: ") + kslam_last_error(ctx));
+  if (o.reads_out_bgzf && (want_reads_out || want_extract) && kslam_set_reads_out_bgzf(ctx, 1) != KSLAM_OK) die(std::string("reads out: ") + kslam_last_error(ctx));
+  if ((want_sam || ((want_reads_out || want_extract) && o.reads_out_bgzf)) && kslam_set_bgzf_deflate(ctx, o.sam_deflate) != KSLAM_OK) die(std::string("BGZF: ") + kslam_last_error(ctx));
   if (o.sam_seq && want_sam && kslam_set_sam_seq(ctx, 1) != KSLAM_OK) die(std::string("SEQ: ") + kslam_last_error(ctx));
   if (o.sam_unmapped && kslam_set_sam_unmapped(ctx, 1) != KSLAM_OK) die(std::string("unmapped rows: ") + kslam_last_error(ctx));
   logl("Getting k-mers from index");
@@ -467,6 +521,23 @@ int run(const Options &o, const std::string &command_line) {
     if (reads_out_fds[k] < 0) die("unable to open " + reads_out_names[k]);
   }
   if (want_reads_out && kslam_stream_set_reads_out(ctx, reads_out_fds) != KSLAM_OK) die(std::string("reads out: ") + kslam_last_error(ctx));
+  // --extract-out: the taxa are chosen on the tree the context holds, so the annotations (they bring the tree) and the pairing
+  // are set here, ahead of the loop, which sets both again for itself and the chosen ids behind them
+  int extract_fds[2] = {-1, -1};
+  if (want_extract) {
+    const uint32_t stages = KSLAM_TAIL_INSERT_SCREEN | KSLAM_TAIL_SCORE_SCREEN | (o.no_pseudo ? 0u : (uint32_t)KSLAM_TAIL_PSEUDO_ASM);
+    const uint32_t mode = (o.extract_children ? KSLAM_TAXREADS_CHILDREN : 0u) | (o.extract_parents ? KSLAM_TAXREADS_PARENTS : 0u) |
+                          (o.extract_exclude ? KSLAM_TAXREADS_EXCLUDE : 0u);
+    if (kslam_set_sam_annotations(ctx, index, taxdb) != KSLAM_OK || kslam_set_pairing(ctx, paired ? 1 : 0, o.score_threshold, o.score_fraction, stages) != KSLAM_OK ||
+        kslam_set_taxon_reads(ctx, o.extract_taxids.data(), o.extract_taxids.size(), mode) != KSLAM_OK)
+      die(std::string("extract: ") + kslam_last_error(ctx));
+    for (int k = 0; k < 2; k++) {
+      if (extract_names[k].empty()) continue;
+      extract_fds[k] = open(extract_names[k].c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+      if (extract_fds[k] < 0) die("unable to open " + extract_names[k]);
+    }
+    if (kslam_stream_set_taxon_reads(ctx, extract_fds) != KSLAM_OK) die(std::string("extract: ") + kslam_last_error(ctx));
+  }
   int coverage_fd = -1;
   if (!o.coverage_out.empty()) {
     coverage_fd = open(o.coverage_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
@@ -527,6 +598,8 @@ int run(const Options &o, const std::string &command_line) {
   if (per_read_fd >= 0) close(per_read_fd);
   for (int fd : reads_out_fds)
     if (fd >= 0 && close(fd) != 0) die("closing a reads-out file failed");
+  for (int fd : extract_fds)
+    if (fd >= 0 && close(fd) != 0) die("closing a file of extracted reads failed");
   if (coverage_fd >= 0 && close(coverage_fd) != 0) die("closing the coverage file failed");
   if (variants_fd >= 0 && close(variants_fd) != 0) die("closing the variants file failed");
   if (kreport_fd >= 0 && close(kreport_fd) != 0) die("closing the Kraken-style report failed");
