@@ -39,7 +39,8 @@
  * The state -- 8 bytes per event, 16 per interval, growing with the batches and not with the database -- belongs to the context
  * the switch was set on and is shared by its lanes; it is emptied at switch-on and by kslam_variants_reset and freed at
  * switch-off, by kslam_set_index and by kslam_destroy.  More than 2^32 - 1 stored events or intervals is outside the envelope
- * (the radix sort's limit): the call that would cross it returns KSLAM_ERR_UNSUPPORTED and leaves the state as it was.
+ * (the radix sort's limit): the call that would cross it returns KSLAM_ERR_UNSUPPORTED and leaves the state as it was.  A run
+ * longer than that still gets its depth along every entry from kslam_depth.h, whose state is compacted and does not grow.
  */
 #ifndef KSLAM_VARIANTS_H_
 #define KSLAM_VARIANTS_H_

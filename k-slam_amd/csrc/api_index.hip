@@ -92,6 +92,7 @@ std::shared_ptr<GenomeIndex> new_index(kslam_ctx *c, uint64_t n_entries) {
   for (auto *l : c->lanes) l->c->index.reset();
   coverage_release(c);   // (include/kslam_coverage.h) the table was laid out for the old index's entries
   variants_release(c);   // (include/kslam_variants.h) the keys hold the old index's base positions
+  depth_release(c);      // (include/kslam_depth.h) likewise, and the spare position per entry besides
   kreport_release(c);    // (include/kslam_kreport.h) the annotations, and the tree with them, belong to the old index's entries
   taxreads_release(c);   // (include/kslam_taxreads.h) likewise
   auto ix = std::make_shared<GenomeIndex>();

@@ -249,6 +249,9 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
     // outside the compute token as well; the batches left to the host go in through kslam_variants_add after the host stage
     if (primary->var.on.load(std::memory_order_acquire) && st == KSLAM_OK && primary->pairing.stages && !pseudo_left && c->have_pairs)
       st = guarded(c, [&] { variants_emit_resident(primary, c); });
+    // (kslam_set_depth) the batch's M runs as interval boundaries into the owner's state, likewise
+    if (primary->dep.on.load(std::memory_order_acquire) && st == KSLAM_OK && primary->pairing.stages && !pseudo_left && c->have_pairs)
+      st = guarded(c, [&] { depth_emit_resident(primary, c); });
     t3 = now();
     // with the SAM records written on the device the host has no use for the rows, the CIGAR pool, the per-row details and
     // the MD text (0.7 GB per batch of configs[1]): they stay where they are, only their counts travel

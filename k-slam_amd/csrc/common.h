@@ -810,5 +810,53 @@ void variants_write_device(const VariantInputs &in, VariantEmitWork &W, uint64_t
 void variants_take_device(VariantTakeWork &T, DevBuf &events, uint64_t n_ev, DevBuf &begins, DevBuf &ends, uint64_t n_iv, bool sorted,
                           const uint64_t *d_goff, const uint8_t *d_gbases, uint64_t n_entries, uint64_t total_bases, uint32_t min_alt,
                           uint32_t min_depth, uint64_t *n_sites_out, uint64_t *n_rows_out, hipStream_t s);
+// passes 1-2 alone, shared with depth.hip: the overlap records a live pair names as a list in `list`; returns its length (waits
+// for the stream).  totals: 4 u64, zeroed here; [0] ends as the list's length
+uint64_t contributing_list_device(const VariantInputs &in, DevBuf &flag, DevBuf &pos, DevBuf &list, DevBuf &scan_tmp, DevBuf &totals, hipStream_t s);
+// sorts n u64 keys of `buf` (scratch: `alt`, at least as large) with as many radix passes as max_key needs; the sorted keys end in `buf`
+void sort_keys(DevBuf &buf, DevBuf &alt, uint64_t n, uint64_t max_key, SortWorkspace &ws, hipStream_t s);
+
+// ------------------------------------------------------------ depth.hip
+// The per-base depth track (include/kslam_depth.h).  Boundaries live in a key space with ONE SPARE position per entry,
+// key = g_off[entry] + entry + pos, so that the boundary after the last base of entry e is not the first base of entry e + 1.
+// Pending: u64 (key << 1) | is_end, two per M run, appended per batch.  Compacted: distinct keys ascending with their net change
+// (i64: begins less ends; a count must hold 2^32 - 1, which a signed 32-bit change does not), none of them 0.
+struct DepthEmitWork {
+  DevBuf flag, pos, list;        // as VariantEmitWork
+  DevBuf cnt, off;               // per listed record: its M runs (u32), its first run's slot (u64)
+  DevBuf scan_tmp, totals;
+  uint64_t n_list = 0, n_iv = 0, n_skipped = 0;   // of the batch counted last
+  hipEvent_t ev[2]{};
+  float ms = 0;
+  DepthEmitWork() = default;
+  DepthEmitWork(const DepthEmitWork &) = delete;
+  DepthEmitWork &operator=(const DepthEmitWork &) = delete;
+  ~DepthEmitWork() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+struct DepthWork {                // compaction and take; used under the state's lock
+  SortWorkspace sortws;
+  DevBuf alt;                    // the sort's second buffer
+  DevBuf head, run, starts;      // u32 per pending key: starts a run of one boundary; the run's number; per run: its first key
+  DevBuf pkey, pnet;             // the pending keys reduced: one record per distinct boundary
+  DevBuf mkey, mnet;             // the merge of the reduced and the compacted list (a boundary at most twice)
+  DevBuf keep, at;               // u32 per merged record / per compacted boundary: kept; its slot
+  DevBuf nkey, nnet;             // the new compacted list (swapped in)
+  DevBuf tile_sum, depth;        // take: i64 per scan tile; u32 per boundary: the depth from it on
+  DevBuf rows, scan_tmp, totals;
+};
+// the list, the counting walk and the scan; fills W.n_list / n_iv / n_skipped (waits for the stream).  in.rbases / in.gbases are not read
+void depth_count_device(const VariantInputs &in, DepthEmitWork &W, hipStream_t s);
+// the writing walk: 2 * W.n_iv pending keys from d_pending on (the caller made room); waits for the stream and fills W.ms
+void depth_write_device(const VariantInputs &in, DepthEmitWork &W, uint64_t *d_pending, hipStream_t s);
+// sort, reduce, merge, drop: n_pend pending keys into the compacted list (ckey / cnet, *n_keys of them).  Throws
+// KSLAM_ERR_UNSUPPORTED before the compacted list is touched when the merge would pass 2^32 - 1 records.  Waits for the stream.
+void depth_compact_device(DepthWork &T, DevBuf &pending, uint64_t n_pend, DevBuf &ckey, DevBuf &cnet, uint64_t *n_keys, uint64_t max_key, hipStream_t s);
+// the rows of the compacted list that reach min_depth into T.rows (device); out[0..3] = rows before the filter, covered bases,
+// the largest depth, rows after the filter.  Waits for the stream.
+void depth_take_device(DepthWork &T, const uint64_t *d_ckey, const int64_t *d_cnet, uint64_t n_keys, const uint64_t *d_goff, uint64_t n_entries,
+                       uint32_t min_depth, uint64_t out[4], hipStream_t s);
 
 }  // namespace kslam

@@ -23,6 +23,7 @@
 #include "../../include/kslam_readsplit.h"
 #include "../../include/kslam_coverage.h"
 #include "../../include/kslam_variants.h"
+#include "../../include/kslam_depth.h"
 #include "../../include/kslam_kreport.h"
 #include "../../include/kslam_taxreads.h"
 #include "../host/workers.hpp"
@@ -172,6 +173,24 @@ struct kslam_ctx {
     std::mutex mu;                // append / take / reset / the switch: one at a time
   } var;
   VariantEmitWork varw;           // this context's own emit passes (a lane's batches; on the primary: kslam_variants_add)
+
+  // ---- the depth track (depth.hip, include/kslam_depth.h) ----
+  struct Depth {                  // on the context the switch was set on; its lanes append to it (lane_main)
+    std::atomic<bool> on{false};
+    uint64_t n_entries = 0, max_key = 0;   // max_key: total bases + entries (one spare position per entry)
+    DevBuf pending;               // u64 (key << 1) | is_end, appended per batch; n_pend of them are in use
+    DevBuf ckey, cnet;            // the compacted list: n_keys distinct boundaries ascending, their net change (i64, never 0)
+    uint64_t n_pend = 0, n_keys = 0, n_records = 0, n_skipped = 0, n_iv = 0;
+    uint64_t compact_at = 0;      // kslam_depth_set_compact_at; 0: the default
+    DepthWork tw;
+    DevBuf up_ov, up_groups, up_pairs, up_pool, up_roff;   // kslam_depth_add's uploads
+    hipEvent_t ev[4]{};           // around a compaction, around a take
+    double compact_ms = 0, take_ms = 0;
+    int stream_fd = -1;           // kslam_stream_set_depth
+    uint32_t stream_min_depth = 1;
+    std::mutex mu;                // append / compact / take / reset / the switch: one at a time
+  } dep;
+  DepthEmitWork depw;             // this context's own emit passes (a lane's batches; on the primary: kslam_depth_add)
 
   // ---- the Kraken-style report's counts (kreport.hip, include/kslam_kreport.h) ----
   struct Kreport {                // on the context the switch was set on; its lanes count into it (lane_main)
@@ -384,6 +403,12 @@ void coverage_mark_resident(kslam_ctx *owner, kslam_ctx *lane);
 void variants_release(kslam_ctx *c);
 // the batch `lane` has just finished (lane->pres over lane->res_ov, lane->res_cig and lane's reads) into owner's state, on lane's stream
 void variants_emit_resident(kslam_ctx *owner, kslam_ctx *lane);
+
+// ---- api_depth.hip
+// frees the depth state of c and switches it off (kslam_set_depth(c, 0), kslam_set_index)
+void depth_release(kslam_ctx *c);
+// the batch `lane` has just finished into owner's state, on lane's stream
+void depth_emit_resident(kslam_ctx *owner, kslam_ctx *lane);
 
 // ---- api_kreport.hip
 // frees the report state of c and switches it off (kslam_set_kreport(c, 0), kslam_set_sam_annotations, kslam_set_index)

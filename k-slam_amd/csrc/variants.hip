@@ -293,6 +293,28 @@ inline unsigned blocks(uint64_t n) { return (unsigned)((n + VAR_BLOCK - 1) / VAR
 
 }  // namespace
 
+uint64_t contributing_list_device(const VariantInputs &in, DevBuf &flag, DevBuf &pos, DevBuf &list, DevBuf &scan_tmp, DevBuf &totals, hipStream_t s) {
+  totals.ensure(4 * sizeof(uint64_t));
+  uint64_t *d_tot = totals.as<uint64_t>();
+  HIPCHK(hipMemsetAsync(d_tot, 0, 4 * sizeof(uint64_t), s));
+  if (!in.n_groups || !in.n_pairs || !in.n_ov) return 0;
+  if (in.n_pairs >= (1ull << 39) || in.n_groups >= (1ull << 39)) throw StatusError{KSLAM_ERR_UNSUPPORTED, "2^39 or more alignment pairs in one batch"};
+  if (in.n_ov >= (1ull << 32)) throw StatusError{KSLAM_ERR_UNSUPPORTED, "2^32 or more overlap records in one batch"};
+  flag.ensure(in.n_ov * sizeof(uint32_t));
+  pos.ensure(in.n_ov * sizeof(uint32_t));
+  scan_tmp.ensure(scan_tmp_bytes(in.n_ov));
+  HIPCHK(hipMemsetAsync(flag.p, 0, in.n_ov * sizeof(uint32_t), s));
+  hipLaunchKernelGGL(k_var_flag, dim3(blocks(in.n_pairs)), dim3(VAR_BLOCK), 0, s, in, flag.as<uint32_t>());
+  exclusive_scan_u32(flag.as<uint32_t>(), pos.as<uint32_t>(), in.n_ov, d_tot, scan_tmp.p, s);
+  uint64_t n_list = 0;
+  read_back(&n_list, d_tot, sizeof n_list, s);
+  if (!n_list) return 0;
+  list.ensure(n_list * sizeof(uint32_t));
+  hipLaunchKernelGGL(k_var_list, dim3(blocks(in.n_ov)), dim3(VAR_BLOCK), 0, s, flag.as<uint32_t>(), pos.as<uint32_t>(), in.n_ov, list.as<uint32_t>());
+  HIPCHK(hipGetLastError());
+  return n_list;
+}
+
 void variants_count_device(const VariantInputs &in, VariantEmitWork &W, hipStream_t s) {
   W.ms = 0;
   W.n_list = W.n_ev = W.n_iv = W.n_skipped = 0;
@@ -300,28 +322,14 @@ void variants_count_device(const VariantInputs &in, VariantEmitWork &W, hipStrea
     for (auto &e : W.ev) HIPCHK(hipEventCreate(&e));
   HIPCHK(hipEventRecord(W.ev[0], s));
   if (!in.n_groups || !in.n_pairs || !in.n_ov) return;
-  if (in.n_pairs >= (1ull << 39) || in.n_groups >= (1ull << 39)) throw StatusError{KSLAM_ERR_UNSUPPORTED, "2^39 or more alignment pairs in one batch"};
-  if (in.n_ov >= (1ull << 32)) throw StatusError{KSLAM_ERR_UNSUPPORTED, "2^32 or more overlap records in one batch"};
-  W.flag.ensure(in.n_ov * sizeof(uint32_t));
-  W.pos.ensure(in.n_ov * sizeof(uint32_t));
-  W.scan_tmp.ensure(scan_tmp_bytes(in.n_ov));
-  W.totals.ensure(4 * sizeof(uint64_t));
+  const uint64_t n_list = contributing_list_device(in, W.flag, W.pos, W.list, W.scan_tmp, W.totals, s);
   uint64_t *d_tot = W.totals.as<uint64_t>();
-  HIPCHK(hipMemsetAsync(d_tot, 0, 4 * sizeof(uint64_t), s));
-  HIPCHK(hipMemsetAsync(W.flag.p, 0, in.n_ov * sizeof(uint32_t), s));
-  hipLaunchKernelGGL(k_var_flag, dim3(blocks(in.n_pairs)), dim3(VAR_BLOCK), 0, s, in, W.flag.as<uint32_t>());
-  exclusive_scan_u32(W.flag.as<uint32_t>(), W.pos.as<uint32_t>(), in.n_ov, d_tot, W.scan_tmp.p, s);
-  uint64_t n_list = 0;
-  read_back(&n_list, d_tot, sizeof n_list, s);
   W.n_list = n_list;
   if (!n_list) return;
-  W.list.ensure(n_list * sizeof(uint32_t));
   W.cnt_ev.ensure(n_list * sizeof(uint32_t));
   W.cnt_iv.ensure(n_list * sizeof(uint32_t));
   W.off_ev.ensure(n_list * sizeof(uint64_t));
   W.off_iv.ensure(n_list * sizeof(uint64_t));
-  hipLaunchKernelGGL(k_var_list, dim3(blocks(in.n_ov)), dim3(VAR_BLOCK), 0, s, W.flag.as<uint32_t>(), W.pos.as<uint32_t>(), in.n_ov,
-                     W.list.as<uint32_t>());
   hipLaunchKernelGGL(k_var_count, dim3(blocks(n_list)), dim3(VAR_BLOCK), 0, s, in, W.list.as<uint32_t>(), n_list, W.cnt_ev.as<uint32_t>(),
                      W.cnt_iv.as<uint32_t>(), reinterpret_cast<unsigned long long *>(d_tot + 3));
   HIPCHK(hipGetLastError());
@@ -344,7 +352,6 @@ void variants_write_device(const VariantInputs &in, VariantEmitWork &W, uint64_t
   HIPCHK(hipEventElapsedTime(&W.ms, W.ev[0], W.ev[1]));
 }
 
-namespace {
 // sorts n keys of `buf` (scratch: `alt`, at least as large); the sorted keys end in `buf`
 void sort_keys(DevBuf &buf, DevBuf &alt, uint64_t n, uint64_t max_key, SortWorkspace &ws, hipStream_t s) {
   if (n < 2) return;
@@ -356,7 +363,6 @@ void sort_keys(DevBuf &buf, DevBuf &alt, uint64_t n, uint64_t max_key, SortWorks
   void *sorted = radix_sort(buf.p, alt.p, n, 2, passes, n_passes, ws, s, nullptr, nullptr, nullptr);
   if (sorted != buf.p) std::swap(buf, alt);
 }
-}  // namespace
 
 void variants_take_device(VariantTakeWork &T, DevBuf &events, uint64_t n_ev, DevBuf &begins, DevBuf &ends, uint64_t n_iv, bool sorted,
                           const uint64_t *d_goff, const uint8_t *d_gbases, uint64_t n_entries, uint64_t total_bases, uint32_t min_alt,

@@ -30,6 +30,7 @@
 #include "../../include/kslam_kreport.h"
 #include "../../include/kslam_taxreads.h"
 #include "../../include/kslam_variants.h"
+#include "../../include/kslam_depth.h"
 #include "workers.hpp"
 
 namespace {
@@ -77,6 +78,9 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
   int var_fd = -1;                    // kslam_stream_set_variants: where the VCF file goes
   uint32_t var_min_alt = 2, var_min_depth = 1;
   bool variants_set = false;
+  int dep_fd = -1;                    // kslam_stream_set_depth: where the bedGraph file goes
+  uint32_t dep_min = 1;
+  bool depth_set = false;
   int kr_fd = -1;                     // kslam_stream_set_kreport: where the Kraken-style report goes
   bool kreport_set = false;
   int tr_fds[2] = {-1, -1};           // kslam_stream_set_taxon_reads: where the selected R1 / R2 records go
@@ -109,6 +113,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     if (ctx) kslam_stream_set_coverage(ctx, -1);          // held for this call alone, like the descriptors below
     if (variants_set) kslam_set_variants(ctx, 0);
     if (ctx) kslam_stream_set_variants(ctx, -1, 2, 1);
+    if (depth_set) kslam_set_depth(ctx, 0);
+    if (ctx) kslam_stream_set_depth(ctx, -1, 1);
     if (kreport_set) kslam_set_kreport(ctx, 0);
     if (ctx) kslam_stream_set_kreport(ctx, -1);
     if (taxreads_set) kslam_set_taxon_reads(ctx, nullptr, 0, 0);
@@ -170,6 +176,13 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       if (kslam_set_variants(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
       variants_set = true;
       if (kslam_variants_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+    }
+    // the depth track (include/kslam_depth.h): the lanes add what they finish; the bedGraph file follows the last batch
+    if (kslam_stream_get_depth(ctx, &dep_fd, &dep_min) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    if (dep_fd >= 0) {
+      if (kslam_set_depth(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
+      depth_set = true;
+      if (kslam_depth_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
     }
     const bool host_split = getenv("KSLAM_HOST_SAM_TEXT") && getenv("KSLAM_HOST_SAM_TEXT")[0] == '1';   // (A/B: the host twin for every batch)
     // the SAM records and the per-read lines written on the GPU (include/kslam_samtext.h); KSLAM_HOST_SAM_TEXT=1 keeps the
@@ -422,6 +435,15 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         });
         if (s != KSLAM_OK) err = g_err;
       }
+      // the depth track likewise; it needs the reads' lengths alone, which came back with the batch
+      if (s == KSLAM_OK && depth_set && P->tail.pseudo_assembly && !(res.pair_stats.stages_done & KSLAM_TAIL_PSEUDO_ASM)) {
+        s = guarded([&] {
+          if (kslam_depth_add(ctx, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, res.reads_bases_off, res.n_reads, res.read_pairs,
+                              res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK)
+            fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+        });
+        if (s != KSLAM_OK) err = g_err;
+      }
       if (s == KSLAM_OK && writer && (res.text_flags & KSLAM_TEXT_SAM)) {
         s = guarded([&] {   // written on the GPU: the page-locked block joins the writer's queue as it is and goes back to the
                             // context's pool once it is in the file
@@ -624,6 +646,15 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       kslam_variant_stats vs;
       if (kslam_variants_take(ctx, var_min_alt, var_min_depth, &rows, &n_rows, &vs) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
       const kslam_status w = kslam_variants_write(index, rows, n_rows, &vs, var_fd);
+      kslam_free_pinned(ctx, rows);
+      if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
+    }
+    if (depth_set) {
+      kslam_depth_row *rows = nullptr;
+      uint64_t n_rows = 0;
+      kslam_depth_stats ds;
+      if (kslam_depth_take(ctx, dep_min, &rows, &n_rows, &ds) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      const kslam_status w = kslam_depth_write(index, rows, n_rows, dep_fd);
       kslam_free_pinned(ctx, rows);
       if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
     }

@@ -57,13 +57,15 @@ class StreamStats(C.Structure):
 def classify_stream_native(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_batch, params, taxdb=None, report=None,
                            sam_fd=-1, per_read_fd=-1, sam_header=None, max_pairs_total=0, depth=0, passes=1, host_threads=0, pool_threads=0,
                            reads_out_fds=None, coverage_fd=-1, variants_fd=None, variants_min_alt=2, variants_min_depth=1, kreport_fd=-1,
-                           taxon_reads_fds=None):
+                           taxon_reads_fds=None, depth_fd=None, depth_min=1):
     """kslam_stream_classify: the same loop as classify_stream below, inside the library (no Python between the batches).
     Single-end data: params.paired = 0, r2_ptr = None, len2 = 0.
     reads_out_fds: four descriptors for the classified R1 / R2 and unclassified R1 / R2 records (kslam_amd.readsplit; -1 = not wanted).
     coverage_fd: an open descriptor for the per-entry coverage report (kslam_amd.coverage; -1 = none).
     variants_fd: an open descriptor for the VCF file of the SNV table (kslam_amd.variants; None = none) with its two thresholds;
     the context needs report_cigar.
+    depth_fd: an open descriptor for the bedGraph file of the depth track (kslam_amd.depth; None = none) with its threshold
+    depth_min; the context needs report_cigar.  (`depth` is the pipeline's depth, not this.)
     kreport_fd: an open descriptor for the Kraken-style report (kslam_amd.kreport; -1 = none); needs a taxdb.
     taxon_reads_fds: two descriptors for the selected R1 / R2 records of the taxa chosen with kslam_amd.taxreads.set_taxon_reads
     before this call (-1 = not wanted; None = none); needs a taxdb.
@@ -84,6 +86,9 @@ def classify_stream_native(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_bat
     if variants_fd is not None and variants_fd >= 0:
         from . import variants as VR
         VR.stream_set_variants(ctx, variants_fd, variants_min_alt, variants_min_depth)
+    if depth_fd is not None and depth_fd >= 0:
+        from . import depth as DP
+        DP.stream_set_depth(ctx, depth_fd, depth_min)
     if kreport_fd is not None and kreport_fd >= 0:
         from . import kreport as KR
         KR.stream_set_kreport(ctx, kreport_fd)

@@ -40,6 +40,7 @@
 #include "../include/kslam_samtext.h"
 #include "../include/kslam_taxreads.h"
 #include "../include/kslam_variants.h"
+#include "../include/kslam_depth.h"
 #include "../include/kslam_stream.h"
 
 namespace {
@@ -75,6 +76,9 @@ struct Options {
   std::string db, out, sam, classified_out, unclassified_out, coverage_out, variants_out, kraken_report;
   uint32_t variants_min_alt = 2, variants_min_depth = 1;
   bool variants_min_alt_given = false, variants_min_depth_given = false;
+  std::string depth_out;                   // --depth-out (include/kslam_depth.h)
+  uint32_t depth_min = 1;
+  bool depth_min_given = false;
   bool reads_out_bgzf = false;
   std::string extract_out;                 // --extract-out (include/kslam_taxreads.h)
   std::vector<uint32_t> extract_taxids;    // --extract-taxid, repeatable and comma lists
@@ -147,6 +151,9 @@ void usage(FILE *o) {
         "                                        VCF 4.2 (sites only: DP, AO, SAF, SAR, AF); works with --just-align, needs no --sam-file\n"
         "  --variants-min-alt arg (=2)           report a site only when at least arg reads carry the alternate base\n"
         "  --variants-min-depth arg (=1)         report a site only when at least arg reads cover it\n"
+        "  --depth-out arg                       write the depth along every entry to this file as bedGraph (locus, start, end, depth;\n"
+        "                                        0-based, half-open, as bedtools genomecov -bg); works with --just-align, needs no --sam-file\n"
+        "  --depth-min arg (=1)                  write only the runs whose depth is at least arg\n"
         "\n", o);
 }
 
@@ -154,7 +161,7 @@ Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
          PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT,
-         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
+         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, DEPTH_OUT, DEPTH_MIN, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -180,6 +187,7 @@ Options parse(int argc, char **argv) {
       // not in the reference: include/kslam_variants.h
       {"variants-out", required_argument, nullptr, VARIANTS_OUT}, {"variants-min-alt", required_argument, nullptr, VARIANTS_MIN_ALT},
       {"variants-min-depth", required_argument, nullptr, VARIANTS_MIN_DEPTH},
+      {"depth-out", required_argument, nullptr, DEPTH_OUT}, {"depth-min", required_argument, nullptr, DEPTH_MIN},   // not in the reference: include/kslam_depth.h
       {"kraken-report", required_argument, nullptr, KRAKEN_REPORT},   // not in the reference: include/kslam_kreport.h (Kraken 2's --report)
       // not in the reference: include/kslam_taxreads.h (KrakenTools' extract_kraken_reads.py)
       {"extract-taxid", required_argument, nullptr, EXTRACT_TAXID}, {"extract-out", required_argument, nullptr, EXTRACT_OUT},
@@ -220,6 +228,8 @@ Options parse(int argc, char **argv) {
       case READS_OUT_BGZF: o.reads_out_bgzf = true; break;
       case COVERAGE_OUT: o.coverage_out = optarg; break;
       case VARIANTS_OUT: o.variants_out = optarg; break;
+      case DEPTH_OUT: o.depth_out = optarg; break;
+      case DEPTH_MIN: o.depth_min = to_u32(optarg, "depth-min"); o.depth_min_given = true; break;
       case KRAKEN_REPORT: o.kraken_report = optarg; break;
       case EXTRACT_OUT: o.extract_out = optarg; break;
       case EXTRACT_CHILDREN: o.extract_children = true; break;
@@ -270,6 +280,7 @@ Options parse(int argc, char **argv) {
   if (o.extract_exclude && o.extract_taxids.empty()) die("option '--extract-exclude' needs '--extract-taxid'");
   if (o.variants_min_alt_given && o.variants_out.empty()) die("option '--variants-min-alt' needs '--variants-out'");
   if (o.variants_min_depth_given && o.variants_out.empty()) die("option '--variants-min-depth' needs '--variants-out'");
+  if (o.depth_min_given && o.depth_out.empty()) die("option '--depth-min' needs '--depth-out'");
   return o;
 }
 
@@ -476,7 +487,7 @@ int run(const Options &o, const std::string &command_line) {
   kp.gap_extend = o.gap_extend;
   kp.score_threshold = o.score_threshold;
   // reportCigar = a SAM file was asked for (src/SLAM.h:169); the variants walk the CIGARs too (the SAM text follows sp.tail.report_cigar)
-  kp.report_cigar = (want_sam || !o.variants_out.empty()) ? 1 : 0;
+  kp.report_cigar = (want_sam || !o.variants_out.empty() || !o.depth_out.empty()) ? 1 : 0;
   kp.device = o.device;
   kslam_ctx *ctx = nullptr;
   if (kslam_create(&kp, &ctx) != KSLAM_OK) die(std::string("GPU context: ") + (ctx ? kslam_last_error(ctx) : "kslam_create failed"));
@@ -556,6 +567,12 @@ int run(const Options &o, const std::string &command_line) {
     if (variants_fd < 0) die("unable to open " + o.variants_out);
     if (kslam_stream_set_variants(ctx, variants_fd, o.variants_min_alt, o.variants_min_depth) != KSLAM_OK) die(std::string("variants: ") + kslam_last_error(ctx));
   }
+  int depth_fd = -1;
+  if (!o.depth_out.empty()) {
+    depth_fd = open(o.depth_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (depth_fd < 0) die("unable to open " + o.depth_out);
+    if (kslam_stream_set_depth(ctx, depth_fd, o.depth_min) != KSLAM_OK) die(std::string("depth: ") + kslam_last_error(ctx));
+  }
   kslam_stream_params sp;
   memset(&sp, 0, sizeof sp);
   sp.pairs_per_batch = o.num_reads_at_once;
@@ -602,6 +619,7 @@ int run(const Options &o, const std::string &command_line) {
     if (fd >= 0 && close(fd) != 0) die("closing a file of extracted reads failed");
   if (coverage_fd >= 0 && close(coverage_fd) != 0) die("closing the coverage file failed");
   if (variants_fd >= 0 && close(variants_fd) != 0) die("closing the variants file failed");
+  if (depth_fd >= 0 && close(depth_fd) != 0) die("closing the depth file failed");
   if (kreport_fd >= 0 && close(kreport_fd) != 0) die("closing the Kraken-style report failed");
   logl(cat("Found ", st.n_overlaps, " k-mer overlaps"));
   logl(cat("", st.n_read_pairs_aligned, " entries have k-mer overlaps"));
