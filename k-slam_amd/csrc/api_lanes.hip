@@ -226,6 +226,11 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
       }
     }
     sam_stage_free(c, sam);
+    // (kslam_set_read_qc) the batch's reads into the owner's per-cycle tables, from the bases and quality columns this lane cut
+    // out of the text it uploaded: a streaming pass on this lane's stream, outside the compute token like the split below, and
+    // it does not wait.  It asks for no alignment result, so every batch of the text route is counted, whatever became of it.
+    if (st == KSLAM_OK && job->fastq_text && primary->rq.on.load(std::memory_order_acquire))
+      st = guarded(c, [&] { readqc_count_resident(primary, c, job->single); });
     // (kslam_set_reads_out) the records split by outcome, cut out of the text this lane uploaded.  Outside the compute token as
     // well: a streaming copy next to the other lane's alignment kernels.  A batch whose pseudo-assembly is left to the host
     // has no final read pairs yet: the host twin splits it.

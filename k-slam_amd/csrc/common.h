@@ -758,6 +758,36 @@ void kreport_count_device(const uint32_t *d_ids, uint64_t n, const KreportTable 
 void kreport_take_device(const KreportTable &T, const uint32_t *d_up, const uint32_t *d_depth, const uint32_t *d_node_tax, const uint64_t *d_items,
                          uint64_t n_items, KreportTakeWork &W, uint64_t *n_known, uint64_t *n_unknown, hipEvent_t ev[2], hipStream_t s);
 
+// -------------------------------------------------------------- readqc.hip
+// The read QC report's tables (include/kslam_readqc.h).  The state -- two streams of 64-bit words in the header's layout --
+// belongs to the context the switch was set on (context.h: kslam_ctx::ReadQc); its lanes count into it from their own streams
+// (every update a device-scope atomic), each with a ReadQcWork of its own.
+struct ReadQcTable {              // what the count pass sees
+  unsigned long long *words;     // [2 * n_words]: stream 0's words, then stream 1's
+  uint64_t n_words;              // KSLAM_READ_QC_WORDS(C)
+  uint32_t C;                    // cycle rows without the pooled one
+};
+struct ReadQcWork {
+  hipEvent_t ev[2]{};            // around the count launches
+  float ms = 0;                  // their device time, last batch counted with `timed`
+  uint64_t bytes = 0;            // bases + quality bytes that batch held
+  ReadQcWork() = default;
+  ReadQcWork(const ReadQcWork &) = delete;
+  ReadQcWork &operator=(const ReadQcWork &) = delete;
+  ~ReadQcWork() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+constexpr uint64_t RQ_READS = 256;   // the fewest reads a workgroup of the count pass takes (more when the grid is full)
+// n reads (read i = d_bases / d_quality[d_off[i] .. d_off[i + 1])) into the table; paired: the first n / 2 are stream 0, the
+// rest stream 1.  max_len: no read is longer (it sizes the grid's tiles).  timed: events around the launches, and the call
+// waits for the stream and reads them; else it does not wait.
+void readqc_count_device(const uint8_t *d_bases, const uint8_t *d_quality, const uint64_t *d_off, uint64_t n, bool paired, uint64_t max_len,
+                         const ReadQcTable &T, ReadQcWork &W, bool timed, hipStream_t s);
+// a zeroed table: every word 0, the two min_len words all ones (the take turns an untouched one into 0)
+void readqc_zero_device(const ReadQcTable &T, hipStream_t s);
+
 // ------------------------------------------------------------ variants.hip
 // The SNV table (include/kslam_variants.h).  The state -- three arrays of 8-byte keys -- belongs to the context the switch was
 // set on (context.h: kslam_ctx::Variants); each lane counts its batch with a VariantEmitWork of its own and appends under the

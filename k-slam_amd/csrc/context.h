@@ -25,6 +25,7 @@
 #include "../../include/kslam_variants.h"
 #include "../../include/kslam_depth.h"
 #include "../../include/kslam_kreport.h"
+#include "../../include/kslam_readqc.h"
 #include "../../include/kslam_taxreads.h"
 #include "../host/workers.hpp"
 #include "../host/inflate.hpp"
@@ -207,6 +208,20 @@ struct kslam_ctx {
     std::mutex mu;                // add / take / reset / the lanes' appends / the switch: one at a time
   } kr;
   KreportCountWork krw;           // this context's own count passes (a lane's batches; on the primary: kslam_kreport_add)
+
+  // ---- the read QC report's tables (readqc.hip, include/kslam_readqc.h) ----
+  struct ReadQc {                 // on the context the switch was set on; its lanes count into it (lane_main)
+    std::atomic<bool> on{false};
+    uint32_t C = 0;               // cycle rows, resolved
+    uint64_t n_words = 0;         // a stream's words
+    DevBuf words;                 // u64 [2 * n_words]
+    bool paired = false;          // a batch counted since the last reset was paired
+    DevBuf up_bases, up_qual, up_off;   // kslam_read_qc_add's uploads
+    int stream_fd = -1;           // kslam_stream_set_read_qc
+    uint32_t stream_cycles = 0;
+    std::mutex mu;                // add / take / reset / the lanes' launches / the switch: one at a time
+  } rq;
+  ReadQcWork rqw;                 // this context's own count passes (a lane's batches; on the primary: kslam_read_qc_add)
 
   // ---- the reads of chosen taxa (taxreads.hip, include/kslam_taxreads.h) ----
   struct TaxReads {               // on the context kslam_set_taxon_reads was called on; its lanes read it (lane_main)
@@ -417,6 +432,13 @@ void kreport_release(kslam_ctx *c);
 void kreport_count_resident(kslam_ctx *owner, kslam_ctx *lane, uint64_t n);
 // the id -> node table of c's device tree (c->annot), uploaded into the two buffers; waits for c's stream
 void id_node_table(kslam_ctx *c, DevBuf &d_keys, DevBuf &d_nodes);
+
+// ---- api_readqc.hip
+// frees the read QC state of c and switches it off (kslam_set_read_qc(c, 0, 0))
+void readqc_release(kslam_ctx *c);
+// the batch resident on `lane` (lane->r_bases, r_qual, r_off: the columns cut out of the text it uploaded) into owner's tables,
+// on lane's stream; does not wait
+void readqc_count_resident(kslam_ctx *owner, kslam_ctx *lane, bool single);
 
 // ---- api_taxreads.hip
 // frees the selection of c and switches it off (kslam_set_taxon_reads(c, NULL, 0, 0), kslam_set_sam_annotations, kslam_set_index)

@@ -28,6 +28,7 @@
 #include "../../include/kslam_readsplit.h"
 #include "../../include/kslam_coverage.h"
 #include "../../include/kslam_kreport.h"
+#include "../../include/kslam_readqc.h"
 #include "../../include/kslam_taxreads.h"
 #include "../../include/kslam_variants.h"
 #include "../../include/kslam_depth.h"
@@ -83,6 +84,9 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
   bool depth_set = false;
   int kr_fd = -1;                     // kslam_stream_set_kreport: where the Kraken-style report goes
   bool kreport_set = false;
+  int qc_fd = -1;                     // kslam_stream_set_read_qc: where the read QC report goes
+  uint32_t qc_cycles = 0;
+  bool read_qc_set = false;
   int tr_fds[2] = {-1, -1};           // kslam_stream_set_taxon_reads: where the selected R1 / R2 records go
   bool taxreads_on = false, taxreads_set = false;
   std::vector<uint32_t> tr_ids;       // the chosen ids and the mode, as kslam_set_taxon_reads was given them before this call
@@ -117,6 +121,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     if (ctx) kslam_stream_set_depth(ctx, -1, 1);
     if (kreport_set) kslam_set_kreport(ctx, 0);
     if (ctx) kslam_stream_set_kreport(ctx, -1);
+    if (read_qc_set) kslam_set_read_qc(ctx, 0, 0);
+    if (ctx) kslam_stream_set_read_qc(ctx, -1, 0);
     if (taxreads_set) kslam_set_taxon_reads(ctx, nullptr, 0, 0);
     if (ctx) kslam_stream_set_taxon_reads(ctx, nullptr);
     if (ctx) kslam_stream_set_reads_out(ctx, nullptr);   // the descriptors held for this call alone
@@ -183,6 +189,14 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       if (kslam_set_depth(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
       depth_set = true;
       if (kslam_depth_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+    }
+    // the read QC report (include/kslam_readqc.h): the lanes count the columns of every batch they take in; the file follows the
+    // last batch.  It needs neither the tree nor the pairing.
+    if (kslam_stream_get_read_qc(ctx, &qc_fd, &qc_cycles) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    if (qc_fd >= 0) {
+      if (kslam_set_read_qc(ctx, 1, qc_cycles) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
+      read_qc_set = true;
+      if (kslam_read_qc_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
     }
     const bool host_split = getenv("KSLAM_HOST_SAM_TEXT") && getenv("KSLAM_HOST_SAM_TEXT")[0] == '1';   // (A/B: the host twin for every batch)
     // the SAM records and the per-read lines written on the GPU (include/kslam_samtext.h); KSLAM_HOST_SAM_TEXT=1 keeps the
@@ -647,6 +661,14 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       if (kslam_variants_take(ctx, var_min_alt, var_min_depth, &rows, &n_rows, &vs) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
       const kslam_status w = kslam_variants_write(index, rows, n_rows, &vs, var_fd);
       kslam_free_pinned(ctx, rows);
+      if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
+    }
+    if (read_qc_set) {
+      kslam_read_qc_tables qt;
+      if (kslam_read_qc_take(ctx, &qt) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      qt.paired = paired ? 1 : 0;   // (a run that ends before its first batch is still the kind of run it was asked to be)
+      const kslam_status w = kslam_read_qc_write(&qt, qc_fd);
+      kslam_read_qc_release(ctx, &qt);
       if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
     }
     if (depth_set) {

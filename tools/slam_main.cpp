@@ -37,6 +37,7 @@
 #include "../include/kslam_readsplit.h"
 #include "../include/kslam_coverage.h"
 #include "../include/kslam_kreport.h"
+#include "../include/kslam_readqc.h"
 #include "../include/kslam_samtext.h"
 #include "../include/kslam_taxreads.h"
 #include "../include/kslam_variants.h"
@@ -79,6 +80,9 @@ struct Options {
   std::string depth_out;                   // --depth-out (include/kslam_depth.h)
   uint32_t depth_min = 1;
   bool depth_min_given = false;
+  std::string qc_out;                      // --qc-out (include/kslam_readqc.h)
+  uint32_t qc_max_cycles = 0;
+  bool qc_max_cycles_given = false;
   bool reads_out_bgzf = false;
   std::string extract_out;                 // --extract-out (include/kslam_taxreads.h)
   std::vector<uint32_t> extract_taxids;    // --extract-taxid, repeatable and comma lists
@@ -154,6 +158,10 @@ void usage(FILE *o) {
         "  --depth-out arg                       write the depth along every entry to this file as bedGraph (locus, start, end, depth;\n"
         "                                        0-based, half-open, as bedtools genomecov -bg); works with --just-align, needs no --sam-file\n"
         "  --depth-min arg (=1)                  write only the runs whose depth is at least arg\n"
+        "  --qc-out arg                          write a QC report on the reads taken in to this file as JSON: reads, bases, lengths, base\n"
+        "                                        content and quality per cycle, mean quality per read, GC content, Q20 / Q30 rates;\n"
+        "                                        works with --just-align, needs no --sam-file\n"
+        "  --qc-max-cycles arg (=512)            per-cycle rows of --qc-out, 1 to 65536; later cycles are pooled in one more row\n"
         "\n", o);
 }
 
@@ -161,7 +169,7 @@ Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
          PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT,
-         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, DEPTH_OUT, DEPTH_MIN, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
+         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, DEPTH_OUT, DEPTH_MIN, QC_OUT, QC_MAX_CYCLES, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -188,6 +196,7 @@ Options parse(int argc, char **argv) {
       {"variants-out", required_argument, nullptr, VARIANTS_OUT}, {"variants-min-alt", required_argument, nullptr, VARIANTS_MIN_ALT},
       {"variants-min-depth", required_argument, nullptr, VARIANTS_MIN_DEPTH},
       {"depth-out", required_argument, nullptr, DEPTH_OUT}, {"depth-min", required_argument, nullptr, DEPTH_MIN},   // not in the reference: include/kslam_depth.h
+      {"qc-out", required_argument, nullptr, QC_OUT}, {"qc-max-cycles", required_argument, nullptr, QC_MAX_CYCLES},   // not in the reference: include/kslam_readqc.h
       {"kraken-report", required_argument, nullptr, KRAKEN_REPORT},   // not in the reference: include/kslam_kreport.h (Kraken 2's --report)
       // not in the reference: include/kslam_taxreads.h (KrakenTools' extract_kraken_reads.py)
       {"extract-taxid", required_argument, nullptr, EXTRACT_TAXID}, {"extract-out", required_argument, nullptr, EXTRACT_OUT},
@@ -231,6 +240,13 @@ Options parse(int argc, char **argv) {
       case DEPTH_OUT: o.depth_out = optarg; break;
       case DEPTH_MIN: o.depth_min = to_u32(optarg, "depth-min"); o.depth_min_given = true; break;
       case KRAKEN_REPORT: o.kraken_report = optarg; break;
+      case QC_OUT: o.qc_out = optarg; break;
+      case QC_MAX_CYCLES:
+        o.qc_max_cycles = to_u32(optarg, "qc-max-cycles");
+        if (o.qc_max_cycles < 1 || o.qc_max_cycles > KSLAM_READ_QC_MAX_CYCLES)
+          die(std::string("the argument ('") + optarg + "') for option '--qc-max-cycles' is invalid: 1 to 65536");
+        o.qc_max_cycles_given = true;
+        break;
       case EXTRACT_OUT: o.extract_out = optarg; break;
       case EXTRACT_CHILDREN: o.extract_children = true; break;
       case EXTRACT_PARENTS: o.extract_parents = true; break;
@@ -281,6 +297,7 @@ Options parse(int argc, char **argv) {
   if (o.variants_min_alt_given && o.variants_out.empty()) die("option '--variants-min-alt' needs '--variants-out'");
   if (o.variants_min_depth_given && o.variants_out.empty()) die("option '--variants-min-depth' needs '--variants-out'");
   if (o.depth_min_given && o.depth_out.empty()) die("option '--depth-min' needs '--depth-out'");
+  if (o.qc_max_cycles_given && o.qc_out.empty()) die("option '--qc-max-cycles' needs '--qc-out'");
   return o;
 }
 
@@ -573,6 +590,12 @@ int run(const Options &o, const std::string &command_line) {
     if (depth_fd < 0) die("unable to open " + o.depth_out);
     if (kslam_stream_set_depth(ctx, depth_fd, o.depth_min) != KSLAM_OK) die(std::string("depth: ") + kslam_last_error(ctx));
   }
+  int qc_fd = -1;
+  if (!o.qc_out.empty()) {
+    qc_fd = open(o.qc_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (qc_fd < 0) die("unable to open " + o.qc_out);
+    if (kslam_stream_set_read_qc(ctx, qc_fd, o.qc_max_cycles) != KSLAM_OK) die(std::string("read QC: ") + kslam_last_error(ctx));
+  }
   kslam_stream_params sp;
   memset(&sp, 0, sizeof sp);
   sp.pairs_per_batch = o.num_reads_at_once;
@@ -621,6 +644,7 @@ int run(const Options &o, const std::string &command_line) {
   if (variants_fd >= 0 && close(variants_fd) != 0) die("closing the variants file failed");
   if (depth_fd >= 0 && close(depth_fd) != 0) die("closing the depth file failed");
   if (kreport_fd >= 0 && close(kreport_fd) != 0) die("closing the Kraken-style report failed");
+  if (qc_fd >= 0 && close(qc_fd) != 0) die("closing the read QC report failed");
   logl(cat("Found ", st.n_overlaps, " k-mer overlaps"));
   logl(cat("", st.n_read_pairs_aligned, " entries have k-mer overlaps"));
   if (paired && st.n_batches) logl(cat("Screening all alignment pairs with insert size >= ", st.first_max_insert_size, ""));
