@@ -1032,6 +1032,7 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
                          W.list.as<uint32_t>(), (uint32_t)n_big, reinterpret_cast<uint32_t *>(d_tot + 1));
       uint64_t mb = 0;
       read_back(&mb, d_tot + 1, sizeof mb, s);
+      if (debug) fprintf(stderr, "[kslam] cigar big rerun: %llu candidates at band %llu\n", (unsigned long long)n_big, (unsigned long long)mb);
       CigJob J = Jc;
       J.items = ListSlice{W.list.as<uint32_t>(), 0, (uint32_t)n_big, 0, nullptr};
       J.big = 1;

@@ -94,6 +94,8 @@ def lib():
                                          C.c_uint16, i32, vp, i32, C.POINTER(SswResult), C.c_int]
         L.orc_banded_sw.restype = i32
         L.orc_banded_sw.argtypes = [vp, vp, i32, i32, i32, u32, u32, i32, vp, i32, vp, i32, vp]
+        L.orc_banded_sw_band.restype = i32
+        L.orc_banded_sw_band.argtypes = [vp, vp, i32, i32, i32, u32, u32, i32, vp, i32, vp, i32, vp, vp]
         L.orc_align.argtypes = [C.c_char_p, i32, C.c_char_p, i32, C.POINTER(Params),
                                 vp, i32, C.POINTER(SswResult), C.c_int]
         L.orc_sw_on_overlap.argtypes = [vp, C.c_char_p, u64, C.c_char_p, u64,
@@ -188,6 +190,27 @@ def ssw_align(read_codes, ref_codes, mat, gap_open, gap_extend, flag=0x0f,
                          gap_extend, flag, filters, filterd, cig.ctypes.data, cap, C.byref(res),
                          int(plain))
     return res, cig[:max(res.cigar_len, 0)].copy()
+
+
+def banded_sw(read_span, ref_span, score, mat, gap_open, gap_extend, band_width):
+    """banded_sw (reference src/ssw.c:594-792) on the translated spans of an alignment that scores `score`, starting at
+    `band_width` and doubling until an attempt reaches the score.
+
+    Returns (cigar[uint32] in alignment order, status, band): status 0, or 1 where the reference would print "Trace
+    back error"; band is the width of the attempt that reached the score.  (None, -1, 0) where the reference's
+    direction buffer check gives up (:631-642)."""
+    L = lib()
+    rd = np.ascontiguousarray(read_span, dtype=np.int8)
+    rf = np.ascontiguousarray(ref_span, dtype=np.int8)
+    cap = len(rd) + len(rf) + 8
+    cig = np.zeros(cap, dtype=np.uint32)
+    st, band = C.c_int32(0), C.c_int32(0)
+    n = L.orc_banded_sw_band(rf.ctypes.data, rd.ctypes.data, len(rf), len(rd), int(score), int(gap_open),
+                             int(gap_extend), int(band_width), mat.ctypes.data, 5, cig.ctypes.data, cap,
+                             C.byref(st), C.byref(band))
+    if n == 2 ** 31 - 1:
+        return None, -1, 0
+    return cig[:n].copy(), int(st.value), int(band.value)
 
 
 def align(query, ref, params=None, plain=False):

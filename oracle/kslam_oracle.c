@@ -638,11 +638,11 @@ static inline int32_t band_d(int32_t w, int32_t i, int32_t j, int32_t p) {
   int32_t x = i - w; x = x > 0 ? x : 0; x = j - x; return x * 3 + p;
 }
 
-int32_t orc_banded_sw(const int8_t *ref, const int8_t *read, int32_t refLen,
-                      int32_t readLen, int32_t score, uint32_t gapO,
-                      uint32_t gapE, int32_t band_width, const int8_t *mat,
-                      int32_t n, uint32_t *cigar_out, int32_t cigar_cap,
-                      int32_t *status) {
+static int32_t banded_sw_impl(const int8_t *ref, const int8_t *read, int32_t refLen,
+                              int32_t readLen, int32_t score, uint32_t gapO,
+                              uint32_t gapE, int32_t band_width, const int8_t *mat,
+                              int32_t n, uint32_t *cigar_out, int32_t cigar_cap,
+                              int32_t *status, int32_t *band_out) {
   int32_t max = 0, width, width_d, *h_b = NULL, *e_b = NULL, *h_c = NULL;
   int8_t *direction = NULL;
   int32_t wgO = (int32_t)gapO, wgE = (int32_t)gapE;
@@ -703,6 +703,7 @@ int32_t orc_banded_sw(const int8_t *ref, const int8_t *read, int32_t refLen,
   } while (max < score);                                  /* :694-695 */
   band_width /= 2;
   width_d = band_width * 2 + 1;
+  if (band_out) *band_out = band_width;   /* the attempt that reached the score */
 
   /* traceback, :698-771; ops collected in reverse then flipped (:773-784) */
   int32_t i = readLen - 1, j = refLen - 1, cnt = 0, l = 0, op = 0, cur = 0, plane = 2;
@@ -742,6 +743,26 @@ int32_t orc_banded_sw(const int8_t *ref, const int8_t *read, int32_t refLen,
   }
   free(c); free(direction); free(h_c); free(e_b); free(h_b);
   return len;
+}
+
+int32_t orc_banded_sw(const int8_t *ref, const int8_t *read, int32_t refLen,
+                      int32_t readLen, int32_t score, uint32_t gapO,
+                      uint32_t gapE, int32_t band_width, const int8_t *mat,
+                      int32_t n, uint32_t *cigar_out, int32_t cigar_cap,
+                      int32_t *status) {
+  return banded_sw_impl(ref, read, refLen, readLen, score, gapO, gapE, band_width, mat, n,
+                        cigar_out, cigar_cap, status, NULL);
+}
+
+/* the same, and *band_out = the band width of the attempt that reached the score (the initial
+ * one doubled zero or more times, :693-694); left alone on the INT32_MAX path */
+int32_t orc_banded_sw_band(const int8_t *ref, const int8_t *read, int32_t refLen,
+                           int32_t readLen, int32_t score, uint32_t gapO,
+                           uint32_t gapE, int32_t band_width, const int8_t *mat,
+                           int32_t n, uint32_t *cigar_out, int32_t cigar_cap,
+                           int32_t *status, int32_t *band_out) {
+  return banded_sw_impl(ref, read, refLen, readLen, score, gapO, gapE, band_width, mat, n,
+                        cigar_out, cigar_cap, status, band_out);
 }
 
 /* ------------------------------------------------------------------------

@@ -145,6 +145,12 @@ int32_t orc_banded_sw(const int8_t *ref, const int8_t *read, int32_t ref_len,
                       uint32_t gap_extend, int32_t band_width,
                       const int8_t *mat, int32_t n, uint32_t *cigar_out,
                       int32_t cigar_cap, int32_t *status);
+/* orc_banded_sw, and *band_out = the band width of the attempt that reached the score */
+int32_t orc_banded_sw_band(const int8_t *ref, const int8_t *read, int32_t ref_len,
+                           int32_t read_len, int32_t score, uint32_t gap_open,
+                           uint32_t gap_extend, int32_t band_width,
+                           const int8_t *mat, int32_t n, uint32_t *cigar_out,
+                           int32_t cigar_cap, int32_t *status, int32_t *band_out);
 /* Aligner::Align on ASCII, src/ssw_cpp.cpp:234-283 */
 void orc_align(const char *query, int32_t query_len, const char *ref,
                int32_t ref_len, const orc_params *p, uint32_t *cigar_out,

@@ -51,6 +51,54 @@ def test_ssw_golden_vectors(oracle):
             assert np.array_equal(cig, cigs[i]), (i, plain)
 
 
+def _banded_from_ends(oracle, rd, rf, mat, go, ge, ends):
+    """banded_sw through the band-reporting export, called the way ssw_align calls it (ssw.c:930-935)"""
+    score, rb, re_, qb, qe = ends
+    rfl, rdl = re_ - rb + 1, qe - qb + 1
+    return oracle.banded_sw(rd[qb:qe + 1], rf[rb:re_ + 1], score, mat, go, ge, abs(rfl - rdl) + 1), rfl, rdl
+
+
+def test_banded_sw_export_equals_ssw_align_on_the_golden_vectors(oracle):
+    """The export that also reports the band banded_sw stopped at gives ssw_align's CIGAR on the stored vectors, and the
+    band it reports is the initial one doubled zero or more times."""
+    z = np.load(os.path.join(GOLD, "ssw_vectors.npz"))
+    reads, refs = _split(z["reads"], z["read_len"]), _split(z["refs"], z["ref_len"])
+    cigs = _split(z["cigars"], z["cigar_len"])
+    n = 0
+    for i in range(len(reads)):
+        m, x, go, ge = [int(v) for v in z["params"][i]]
+        mat = oracle.build_matrix(m, x)
+        res, cig = oracle.ssw_align(reads[i], refs[i], mat, go, ge)
+        if res.cigar_len <= 0:
+            continue
+        ends = (res.score1, res.ref_begin1, res.ref_end1, res.read_begin1, res.read_end1)
+        (got, st, band), rfl, rdl = _banded_from_ends(oracle, reads[i], refs[i], mat, go, ge, ends)
+        assert st == res.status == 0, i
+        assert np.array_equal(got, cig) and np.array_equal(got, cigs[i]), i
+        bw0 = abs(rfl - rdl) + 1
+        assert band >= bw0 and band % bw0 == 0 and (band // bw0) & (band // bw0 - 1) == 0, (i, bw0, band)
+        n += 1
+    assert n >= len(reads) // 2
+
+
+def test_banded_sw_export_against_real_ssw_when_present(oracle):
+    if not oracle.have_ref_ssw():
+        pytest.skip("oracle/_ref/libssw_ref.so not built (no /root/reference)")
+    rng = np.random.default_rng(77)
+    doubled = 0
+    for params in ((2, 3, 5, 2), (3, 2, 4, 1), (10, 8, 6, 3)):
+        mat = oracle.build_matrix(params[0], params[1])
+        for i in range(300):
+            rd, ref = _random_pair(rng)
+            r0, c0 = oracle.ref_ssw_align(rd, ref, mat, params[2], params[3])
+            if len(c0) == 0:
+                continue
+            (got, st, band), rfl, rdl = _banded_from_ends(oracle, rd, ref, mat, params[2], params[3], r0)
+            assert st == 0 and np.array_equal(got, c0), (params, i)
+            doubled += band > abs(rfl - rdl) + 1
+    assert doubled >= 10, doubled
+
+
 def test_kmer_golden_vectors(oracle):
     z = np.load(os.path.join(GOLD, "kmer_vectors.npz"))
     seqs = [s.tobytes() for s in _split(z["seqs"], z["seq_len"])]
