@@ -17,6 +17,13 @@
 // count exchange every shard knows where its R1 rows, R2 rows and CIGAR words go in the batch-global
 // arrays, re-bases its own records (k_export_rows, on its own GPU, all shards in parallel) and the
 // transfers land in their final place -- the collecting device runs no kernel at all.
+//
+// Relied on, not checked: the rows of a shard are sorted by local read id, its pool is in row order and holds nothing
+// but the rows' ops, cigar_off grows with the row number and is 0 where cigar_len == 0.  Every result a context aligned
+// (cigar.hip k_finalize), merged or received through the export is laid out like that; kslam_adopt_results_device does
+// not check it, so a hand-made table with the pool in another order (dist.reassemble's output is one) must go through
+// merge_shards before its context is asked for counts or an export: k_shard_first_cigar would report a wrong
+// n_cigar_r1 for it and nothing would fault.
 #include <cstddef>
 
 #include "common.h"
