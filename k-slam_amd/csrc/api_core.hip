@@ -246,6 +246,7 @@ void kslam_destroy(kslam_ctx *c) {
     for (auto &ev : c->dep.ev) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->kr.ev_take) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->tr.ev_mask) if (ev) (void)hipEventDestroy(ev);
+    for (auto &ev : c->gen.ev_take) if (ev) (void)hipEventDestroy(ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
   }
   delete c;   // every DevBuf frees itself, the index with the last context that holds it

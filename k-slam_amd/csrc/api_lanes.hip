@@ -257,6 +257,9 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
     // (kslam_set_depth) the batch's M runs as interval boundaries into the owner's state, likewise
     if (primary->dep.on.load(std::memory_order_acquire) && st == KSLAM_OK && primary->pairing.stages && !pseudo_left && c->have_pairs)
       st = guarded(c, [&] { depth_emit_resident(primary, c); });
+    // (kslam_set_genes) the batch's final alignment pairs into the owner's per-gene counters, likewise
+    if (primary->gen.on.load(std::memory_order_acquire) && st == KSLAM_OK && primary->pairing.stages && !pseudo_left && c->have_pairs)
+      st = guarded(c, [&] { genes_count_resident(primary, c); });
     t3 = now();
     // with the SAM records written on the device the host has no use for the rows, the CIGAR pool, the per-row details and
     // the MD text (0.7 GB per batch of configs[1]): they stay where they are, only their counts travel

@@ -442,6 +442,7 @@ kslam_status kslam_set_sam_annotations(kslam_ctx *c, const kslam_index_view *iv,
       throw StatusError{KSLAM_ERR_ARG, "index view has n_genes > 0 but no gene columns"};
     kreport_release(c);   // (include/kslam_kreport.h) the counters were laid out for the old tree's nodes
     taxreads_release(c);  // (include/kslam_taxreads.h) the mask was laid out for them too
+    genes_release(c);     // (include/kslam_genes.h) the lookup index was built from the old gene columns
     for (auto &b : c->annot_bufs) b.release();
     c->annot_bufs.clear();
     c->annot_bufs.reserve(24);

@@ -758,6 +758,54 @@ void kreport_count_device(const uint32_t *d_ids, uint64_t n, const KreportTable 
 void kreport_take_device(const KreportTable &T, const uint32_t *d_up, const uint32_t *d_depth, const uint32_t *d_node_tax, const uint64_t *d_items,
                          uint64_t n_items, KreportTakeWork &W, uint64_t *n_known, uint64_t *n_unknown, hipEvent_t ev[2], hipStream_t s);
 
+// --------------------------------------------------------------- genes.hip
+// The per-gene abundance table (include/kslam_genes.h).  The state -- the lookup index, four 64-bit counters per gene and four
+// statistics counters -- belongs to the context the switch was set on (context.h: kslam_ctx::Genes); its lanes count into it
+// from their own streams (every update a device-scope atomic), each with a GenesCountWork of its own.
+struct GeneTable {                // what the kernels see
+  uint64_t n_entries, n_genes;
+  const uint64_t *gene_first;    // [n_entries + 1], ascending from 0 to n_genes (checked at switch-on)
+  const int32_t *gene_start, *gene_stop;   // [n_genes] the annotation columns, in gene-index order
+  // the lookup index: per entry, its genes ordered by (start, gene index); position p lies in the entry's own slice
+  // [gene_first[e], gene_first[e + 1])
+  const uint32_t *order;         // [n_genes] the gene at position p
+  const int32_t *sstart, *sstop; // [n_genes] its start and stop
+  const int32_t *runmax;         // [n_genes] the largest stop among the entry's positions <= p
+  unsigned long long *rows;      // 4 per gene: unused, alignments, unique_read_pairs, overlap_bases
+  unsigned long long *stats;     // n_alignments, n_in_gene, n_no_gene, n_skipped
+};
+struct GenesCountWork {
+  DevBuf gene;                   // u32 per alignment-pair record: its gene, GENE_NONE or GENE_SKIPPED (live records only)
+  DevBuf gflag;                  // u32 per read pair: a live record's gene differs from the first record's, or is no gene
+  hipEvent_t ev[2]{};            // around the count launches
+  float ms = 0;                  // their device time, last batch
+  GenesCountWork() = default;
+  GenesCountWork(const GenesCountWork &) = delete;
+  GenesCountWork &operator=(const GenesCountWork &) = delete;
+  ~GenesCountWork() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+struct GenesTakeWork {
+  DevBuf flag, pos, rows, scan_tmp, totals;   // u32 per gene: alignments > 0, its place among the rows; the compacted rows
+};
+constexpr int GENES_BLOCK = 256;      // threads per workgroup of the count pass (one alignment-pair record each)
+// the lookup index of n_genes genes from the three annotation columns into the four arrays (each n_genes long); *ms: the device
+// time of the launches.  Waits for the stream.
+void genes_build_device(uint64_t n_entries, uint64_t n_genes, const uint64_t *d_gene_first, const int32_t *d_gene_start, const int32_t *d_gene_stop,
+                        uint32_t *d_order, int32_t *d_sstart, int32_t *d_sstop, int32_t *d_runmax, float *ms, hipStream_t s);
+// one batch into the table; linear: the walk over all genes of the entry instead of the indexed lookup (the same result).
+// Waits for the stream (the events are read).
+void genes_count_device(const kslam_read_pair *d_groups, uint64_t n_groups, const kslam_paired_overlap *d_pairs, uint64_t n_pairs,
+                        const GeneTable &T, GenesCountWork &W, bool linear, hipStream_t s);
+// the rows with alignments > 0 (kslam_gene_row) into W.rows in gene order; ev: two events around the launches.  Waits for the
+// stream for *n_rows, not for the row kernel.
+void genes_take_device(const GeneTable &T, GenesTakeWork &W, uint64_t *n_rows, hipEvent_t ev[2], hipStream_t s);
+// n triples through the count pass's device function: d_gene_out / d_shared_out as kslam_genes_lookup describes them
+void genes_lookup_device(const uint32_t *d_entries, const int32_t *d_starts, const int32_t *d_stops, uint64_t n, const GeneTable &T, bool linear,
+                         int64_t *d_gene_out, int64_t *d_shared_out, hipStream_t s);
+
 // -------------------------------------------------------------- readqc.hip
 // The read QC report's tables (include/kslam_readqc.h).  The state -- two streams of 64-bit words in the header's layout --
 // belongs to the context the switch was set on (context.h: kslam_ctx::ReadQc); its lanes count into it from their own streams

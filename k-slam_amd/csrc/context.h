@@ -27,6 +27,7 @@
 #include "../../include/kslam_kreport.h"
 #include "../../include/kslam_readqc.h"
 #include "../../include/kslam_taxreads.h"
+#include "../../include/kslam_genes.h"
 #include "../host/workers.hpp"
 #include "../host/inflate.hpp"
 #include <algorithm>
@@ -208,6 +209,22 @@ struct kslam_ctx {
     std::mutex mu;                // add / take / reset / the lanes' appends / the switch: one at a time
   } kr;
   KreportCountWork krw;           // this context's own count passes (a lane's batches; on the primary: kslam_kreport_add)
+
+  // ---- the per-gene abundance table (genes.hip, include/kslam_genes.h) ----
+  struct Genes {                  // on the context the switch was set on; its lanes count into it (lane_main)
+    std::atomic<bool> on{false};
+    uint64_t n_entries = 0, n_genes = 0;   // of the annotations the state was laid out for
+    DevBuf order, sstart, sstop, runmax;   // the lookup index: 16 bytes per gene
+    DevBuf rows, stats;           // u64 [4 * n_genes], u64 [4]
+    DevBuf up_groups, up_pairs;   // kslam_genes_add's uploads
+    DevBuf lk_in, lk_out;         // kslam_genes_lookup's triples and answers
+    GenesTakeWork tw;
+    hipEvent_t ev_take[2]{};
+    double build_ms = 0, take_ms = 0;
+    int stream_fd = -1;           // kslam_stream_set_genes
+    std::mutex mu;                // add / take / reset / lookup / the switch: one at a time
+  } gen;
+  GenesCountWork genw;            // this context's own count passes (a lane's batches; on the primary: kslam_genes_add)
 
   // ---- the read QC report's tables (readqc.hip, include/kslam_readqc.h) ----
   struct ReadQc {                 // on the context the switch was set on; its lanes count into it (lane_main)
@@ -432,6 +449,12 @@ void kreport_release(kslam_ctx *c);
 void kreport_count_resident(kslam_ctx *owner, kslam_ctx *lane, uint64_t n);
 // the id -> node table of c's device tree (c->annot), uploaded into the two buffers; waits for c's stream
 void id_node_table(kslam_ctx *c, DevBuf &d_keys, DevBuf &d_nodes);
+
+// ---- api_genes.hip
+// frees the gene table of c and switches it off (kslam_set_genes(c, 0), kslam_set_sam_annotations, kslam_set_index)
+void genes_release(kslam_ctx *c);
+// the batch `lane` has just finished (lane->pres) into owner's table, on lane's stream
+void genes_count_resident(kslam_ctx *owner, kslam_ctx *lane);
 
 // ---- api_readqc.hip
 // frees the read QC state of c and switches it off (kslam_set_read_qc(c, 0, 0))

@@ -18,6 +18,7 @@
 // Bounds: a mate is marked only after entry < n_entries, 0 <= ref_begin <= ref_end < the entry's length held, so every word
 // index lies inside the entry's words; a counter row is touched only for an entry < n_entries.
 #include "common.h"
+#include "wave_add.h"
 #include "../../include/kslam_coverage.h"
 
 namespace kslam {
@@ -30,38 +31,9 @@ constexpr int COV_COUNT_PER_THREAD = 8;
 constexpr uint64_t COV_COUNT_TILE = (uint64_t)COV_COUNT_BLOCK * COV_COUNT_PER_THREAD;
 enum { F_ALIGNMENTS = 0, F_UNIQUE = 1, F_ALIGNED = 2, F_COVERED = 3 };
 
-__device__ inline uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, o), hi = __shfl_xor((uint32_t)(v >> 32), o);
-    v += ((uint64_t)hi << 32) | lo;
-  }
-  return v;
-}
-
 __device__ inline uint64_t shfl64(uint64_t v, int lane) {
   const uint32_t lo = __shfl((uint32_t)v, lane), hi = __shfl((uint32_t)(v >> 32), lane);
   return ((uint64_t)hi << 32) | lo;
-}
-
-// rows[key][f_one] += the number of lanes with `one`, rows[key][f_sum] += their `sum`s, for the lanes with `has`: lanes that
-// share a key go to memory as one add each.  Called by every lane of the wavefront (has = false for those with nothing).
-__device__ inline void wave_add(bool has, uint32_t key, bool one, uint64_t sum, unsigned long long *rows, int f_one, int f_sum) {
-  uint64_t pending = __ballot(has);
-  const int lane = threadIdx.x & 63;
-  while (pending) {
-    const int leader = __ffsll((long long)pending) - 1;
-    const uint32_t k0 = __shfl(key, leader);
-    const bool same = has && key == k0;
-    const uint64_t m = __ballot(same);
-    const uint64_t ones = __popcll(__ballot(same && one));
-    const uint64_t total = (m & (m - 1)) ? wave_sum(same ? sum : 0ull) : sum;   // (one lane: its own sum)
-    if (lane == leader) {
-      if (ones) atomicAdd(rows + 4ull * k0 + f_one, (unsigned long long)ones);
-      if (total) atomicAdd(rows + 4ull * k0 + f_sum, (unsigned long long)total);
-    }
-    pending &= ~m;
-  }
 }
 
 // word w of an interval of nw words that begins at bit sb of its first word and ends at bit eb of its last

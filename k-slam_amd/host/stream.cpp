@@ -27,6 +27,7 @@
 #include "../../include/kslam_samunmapped.h"
 #include "../../include/kslam_readsplit.h"
 #include "../../include/kslam_coverage.h"
+#include "../../include/kslam_genes.h"
 #include "../../include/kslam_kreport.h"
 #include "../../include/kslam_readqc.h"
 #include "../../include/kslam_taxreads.h"
@@ -76,7 +77,9 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
   int ro_bgzf = 0;
   int cov_fd = -1;                    // kslam_stream_set_coverage: where the coverage report goes
   bool coverage_set = false;
-  int var_fd = -1;                    // kslam_stream_set_variants: where the VCF file goes
+  int gen_fd = -1;                    // kslam_stream_set_genes: where the per-gene table goes
+  bool genes_set = false;
+  int var_fd = -1;                   // kslam_stream_set_variants: where the VCF file goes
   uint32_t var_min_alt = 2, var_min_depth = 1;
   bool variants_set = false;
   int dep_fd = -1;                    // kslam_stream_set_depth: where the bedGraph file goes
@@ -115,6 +118,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     if (reads_out_set) kslam_set_reads_out(ctx, 0);
     if (coverage_set) kslam_set_coverage(ctx, 0);
     if (ctx) kslam_stream_set_coverage(ctx, -1);          // held for this call alone, like the descriptors below
+    if (genes_set) kslam_set_genes(ctx, 0);
+    if (ctx) kslam_stream_set_genes(ctx, -1);
     if (variants_set) kslam_set_variants(ctx, 0);
     if (ctx) kslam_stream_set_variants(ctx, -1, 2, 1);
     if (depth_set) kslam_set_depth(ctx, 0);
@@ -214,8 +219,16 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     if (kr_fd >= 0) {
       if (!taxdb) fail(KSLAM_ERR_STATE, "the Kraken-style report needs a taxonomy tree (not available with --just-align)");
     }
-    if ((kr_fd >= 0 || taxreads_on) && !device_text && kslam_set_sam_annotations(ctx, index, taxdb) != KSLAM_OK)
+    if (kslam_stream_get_genes(ctx, &gen_fd) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    if ((kr_fd >= 0 || taxreads_on || gen_fd >= 0) && !device_text && kslam_set_sam_annotations(ctx, index, taxdb) != KSLAM_OK)
       fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+    // the per-gene abundance table (include/kslam_genes.h): the lanes count what they finish; the file follows the last batch.
+    // Behind the annotations: they bring the gene columns, and setting them drops the table.
+    if (gen_fd >= 0) {
+      if (kslam_set_genes(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
+      genes_set = true;
+      if (kslam_genes_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+    }
     if (kr_fd >= 0) {
       if (kslam_set_kreport(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
       kreport_set = true;
@@ -427,6 +440,13 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         s = guarded([&] {
           if (kslam_coverage_add(ctx, res.overlaps, res.n_overlaps, res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK)
             fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+        });
+        if (s != KSLAM_OK) err = g_err;
+      }
+      // the per-gene table likewise
+      if (s == KSLAM_OK && genes_set && P->tail.pseudo_assembly && !(res.pair_stats.stages_done & KSLAM_TAIL_PSEUDO_ASM)) {
+        s = guarded([&] {
+          if (kslam_genes_add(ctx, res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
         });
         if (s != KSLAM_OK) err = g_err;
       }
@@ -642,6 +662,15 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       uint64_t n_rows = 0, n_skipped = 0;
       if (kslam_coverage_take(ctx, &rows, &n_rows, &n_skipped) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
       const kslam_status w = kslam_coverage_write(index, rows, n_rows, cov_fd);
+      kslam_free_pinned(ctx, rows);
+      if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
+    }
+    if (genes_set) {
+      kslam_gene_row *rows = nullptr;
+      uint64_t n_rows = 0;
+      kslam_gene_stats gs;
+      if (kslam_genes_take(ctx, &rows, &n_rows, &gs) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      const kslam_status w = kslam_genes_write(index, rows, n_rows, gen_fd);
       kslam_free_pinned(ctx, rows);
       if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
     }

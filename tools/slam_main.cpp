@@ -42,6 +42,7 @@
 #include "../include/kslam_taxreads.h"
 #include "../include/kslam_variants.h"
 #include "../include/kslam_depth.h"
+#include "../include/kslam_genes.h"
 #include "../include/kslam_stream.h"
 
 namespace {
@@ -78,6 +79,7 @@ struct Options {
   uint32_t variants_min_alt = 2, variants_min_depth = 1;
   bool variants_min_alt_given = false, variants_min_depth_given = false;
   std::string depth_out;                   // --depth-out (include/kslam_depth.h)
+  std::string genes_out;                   // --genes-out (include/kslam_genes.h)
   uint32_t depth_min = 1;
   bool depth_min_given = false;
   std::string qc_out;                      // --qc-out (include/kslam_readqc.h)
@@ -158,6 +160,8 @@ void usage(FILE *o) {
         "  --depth-out arg                       write the depth along every entry to this file as bedGraph (locus, start, end, depth;\n"
         "                                        0-based, half-open, as bedtools genomecov -bg); works with --just-align, needs no --sam-file\n"
         "  --depth-min arg (=1)                  write only the runs whose depth is at least arg\n"
+        "  --genes-out arg                       write a per-gene abundance table to this file: alignments, unique read pairs,\n"
+        "                                        overlapping bases, RPK and TPM per annotated gene (works with --just-align)\n"
         "  --qc-out arg                          write a QC report on the reads taken in to this file as JSON: reads, bases, lengths, base\n"
         "                                        content and quality per cycle, mean quality per read, GC content, Q20 / Q30 rates;\n"
         "                                        works with --just-align, needs no --sam-file\n"
@@ -169,7 +173,7 @@ Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
          PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT,
-         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, DEPTH_OUT, DEPTH_MIN, QC_OUT, QC_MAX_CYCLES, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
+         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, DEPTH_OUT, DEPTH_MIN, GENES_OUT, QC_OUT, QC_MAX_CYCLES, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -196,6 +200,7 @@ Options parse(int argc, char **argv) {
       {"variants-out", required_argument, nullptr, VARIANTS_OUT}, {"variants-min-alt", required_argument, nullptr, VARIANTS_MIN_ALT},
       {"variants-min-depth", required_argument, nullptr, VARIANTS_MIN_DEPTH},
       {"depth-out", required_argument, nullptr, DEPTH_OUT}, {"depth-min", required_argument, nullptr, DEPTH_MIN},   // not in the reference: include/kslam_depth.h
+      {"genes-out", required_argument, nullptr, GENES_OUT},   // not in the reference: include/kslam_genes.h
       {"qc-out", required_argument, nullptr, QC_OUT}, {"qc-max-cycles", required_argument, nullptr, QC_MAX_CYCLES},   // not in the reference: include/kslam_readqc.h
       {"kraken-report", required_argument, nullptr, KRAKEN_REPORT},   // not in the reference: include/kslam_kreport.h (Kraken 2's --report)
       // not in the reference: include/kslam_taxreads.h (KrakenTools' extract_kraken_reads.py)
@@ -238,6 +243,7 @@ Options parse(int argc, char **argv) {
       case COVERAGE_OUT: o.coverage_out = optarg; break;
       case VARIANTS_OUT: o.variants_out = optarg; break;
       case DEPTH_OUT: o.depth_out = optarg; break;
+      case GENES_OUT: o.genes_out = optarg; break;
       case DEPTH_MIN: o.depth_min = to_u32(optarg, "depth-min"); o.depth_min_given = true; break;
       case KRAKEN_REPORT: o.kraken_report = optarg; break;
       case QC_OUT: o.qc_out = optarg; break;
@@ -590,6 +596,12 @@ int run(const Options &o, const std::string &command_line) {
     if (depth_fd < 0) die("unable to open " + o.depth_out);
     if (kslam_stream_set_depth(ctx, depth_fd, o.depth_min) != KSLAM_OK) die(std::string("depth: ") + kslam_last_error(ctx));
   }
+  int genes_fd = -1;
+  if (!o.genes_out.empty()) {
+    genes_fd = open(o.genes_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (genes_fd < 0) die("unable to open " + o.genes_out);
+    if (kslam_stream_set_genes(ctx, genes_fd) != KSLAM_OK) die(std::string("genes: ") + kslam_last_error(ctx));
+  }
   int qc_fd = -1;
   if (!o.qc_out.empty()) {
     qc_fd = open(o.qc_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
@@ -643,6 +655,7 @@ int run(const Options &o, const std::string &command_line) {
   if (coverage_fd >= 0 && close(coverage_fd) != 0) die("closing the coverage file failed");
   if (variants_fd >= 0 && close(variants_fd) != 0) die("closing the variants file failed");
   if (depth_fd >= 0 && close(depth_fd) != 0) die("closing the depth file failed");
+  if (genes_fd >= 0 && close(genes_fd) != 0) die("closing the gene table failed");
   if (kreport_fd >= 0 && close(kreport_fd) != 0) die("closing the Kraken-style report failed");
   if (qc_fd >= 0 && close(qc_fd) != 0) die("closing the read QC report failed");
   logl(cat("Found ", st.n_overlaps, " k-mer overlaps"));
