@@ -645,6 +645,33 @@ kslam_status kslam_debug_overlap_unique(kslam_ctx *ctx, const uint64_t *keys, ui
                                         uint32_t read_id_base, int route, uint64_t *keys_after, uint64_t *ordered,
                                         uint32_t *flags, uint32_t *big, uint64_t *n_rows, kslam_overlap *rows);
 
+/* ---- test hook for the one-time index build (csrc/api_index.hip: build_index; tests/test_gpu_index_build.py) ----
+ * Copies what kslam_set_index / kslam_set_index_device left on the device to the host, table by table.  Read-only: it waits
+ * for the context's stream and changes nothing of the context, the index or the sort workspace.
+ * The first six fields are written by every call that gets as far as the index.  The tables are copied when a buffer pointer
+ * is set; with all six pointers NULL the call only reports the sizes (the first of two calls).  Otherwise every table that
+ * has elements needs its pointer and a capacity, in elements, of at least its size:
+ *   offsets   n_entries + 1          the entries' start offsets in the concatenated bases (the first is 0)
+ *   codes     n_bases                one byte per base: bits 0-2 the SSW code, bit 3 "inPlaceReverseComplement complements it"
+ *   keys      n_genome_kmers         the sorted k-mers
+ *   meta      n_genome_kmers         {meta, offset} of the same records, two 32-bit words each (cap_records counts records)
+ *   bucket    2^bucket_bits + 1      lower bounds of the keys by their top bucket_bits bits
+ *   filter    n_filter_bytes         the membership filter, 2^filter_bits bits (nothing when filter_bits is 0)
+ * KSLAM_ERR_ARG for a null ctx or x, a missing pointer or a capacity that is too small: then no table is written at all.
+ * KSLAM_ERR_STATE without an index. */
+typedef struct {
+  uint64_t n_entries, n_genome_kmers, n_bases, n_filter_bytes; /* out */
+  uint32_t bucket_bits, filter_bits;                           /* out */
+  uint64_t *offsets;                                           /* in: host buffers ... */
+  uint8_t *codes;
+  uint64_t *keys;
+  uint32_t *meta;
+  uint32_t *bucket;
+  uint8_t *filter;
+  uint64_t cap_offsets, cap_codes, cap_records, cap_bucket, cap_filter; /* ... and their capacities in elements */
+} kslam_index_export;
+kslam_status kslam_debug_index_export(kslam_ctx *ctx, kslam_index_export *x);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,7 +49,7 @@ EXPORTS = ["kslam_abi_version", "kslam_index_build_stats", "kslam_version", "ksl
            "kslam_load_reads", "kslam_load_reads_device", "kslam_align_resident",
            "kslam_fetch_results", "kslam_take_results", "kslam_copy_results_device", "kslam_get_timings",
            "kslam_extract_kmers", "kslam_sort_kmers", "kslam_find_overlaps", "kslam_free",
-           "kslam_selftest_sort", "kslam_debug_radix_sort", "kslam_debug_scan", "kslam_debug_partition_bins", "kslam_debug_bgzf_code_lengths", "kslam_debug_join", "kslam_debug_overlap_unique",
+           "kslam_selftest_sort", "kslam_debug_radix_sort", "kslam_debug_scan", "kslam_debug_partition_bins", "kslam_debug_bgzf_code_lengths", "kslam_debug_join", "kslam_debug_overlap_unique", "kslam_debug_index_export",
            "kslam_merge_shards_device", "kslam_shard_counts_device",
            "kslam_export_shard_device", "kslam_multi_create", "kslam_multi_destroy",
            "kslam_multi_last_error", "kslam_multi_set_index", "kslam_multi_align_batch", "kslam_multi_free_batch"]
@@ -107,6 +107,16 @@ class IndexStats(C.Structure):
 class OverlapLayout(C.Structure):
     """kslam_overlap_layout: read | entry | rel + rel_bias | revComp, the packed overlap key of csrc/join.hip"""
     _fields_ = [("bits_read", C.c_uint32), ("bits_entry", C.c_uint32), ("bits_rel", C.c_uint32), ("rel_bias", C.c_uint32)]
+
+
+class IndexExport(C.Structure):
+    """kslam_index_export: the sizes of the built index (out), then host buffers and their capacities in elements (in)"""
+    _fields_ = [("n_entries", C.c_uint64), ("n_genome_kmers", C.c_uint64), ("n_bases", C.c_uint64), ("n_filter_bytes", C.c_uint64),
+                ("bucket_bits", C.c_uint32), ("filter_bits", C.c_uint32),
+                ("offsets", C.c_void_p), ("codes", C.c_void_p), ("keys", C.c_void_p), ("meta", C.c_void_p), ("bucket", C.c_void_p),
+                ("filter", C.c_void_p),
+                ("cap_offsets", C.c_uint64), ("cap_codes", C.c_uint64), ("cap_records", C.c_uint64), ("cap_bucket", C.c_uint64),
+                ("cap_filter", C.c_uint64)]
 
 
 DEBUG_SENTINEL_BYTE = 0xEE        # kslam.h: KSLAM_DEBUG_SENTINEL_BYTE
@@ -206,6 +216,7 @@ def lib():
         L.kslam_debug_join.argtypes = [vp, vp, u64, u32, vp, u64, u32, vp, u64, C.POINTER(OverlapLayout), C.c_int, u64, C.POINTER(u64), vp, vp]
         L.kslam_debug_overlap_unique.argtypes = [vp, vp, u64, C.POINTER(OverlapLayout), u32, C.c_int, vp, vp, vp, C.POINTER(u32),
                                                  C.POINTER(u64), vp]
+        L.kslam_debug_index_export.argtypes = [vp, C.POINTER(IndexExport)]
         L.kslam_merge_shards_device.argtypes = [vp, u32, vp, u64, vp, vp, vp, vp]
         L.kslam_shard_counts_device.argtypes = [vp, u64, vp]
         L.kslam_export_shard_device.argtypes = [vp, u64, u64, u64, u64, u64, vp, vp, vp, vp]
@@ -720,6 +731,33 @@ class Context:
                                                      C.byref(m), rows.ctypes.data))
         return {"keys_after": after[:n], "ordered": ordered[:n], "flags": flags[:n], "big": int(big.value),
                 "rows": rows[:int(m.value)]}
+
+    def debug_index_export(self, guard=64):
+        """kslam_debug_index_export, both calls: the sizes, then the tables -> dict(n_entries, n_genome_kmers, n_bases,
+        bucket_bits, filter_bits, offsets u64 [n + 1], codes u8 [n_bases], keys u64 [m], meta u32 [m], offset u32 [m],
+        bucket u32 [2^bucket_bits + 1], filter u32 [2^filter_bits / 32]).  Each host buffer carries `guard` sentinel bytes
+        past its capacity, which the call must leave alone."""
+        x = IndexExport()
+        self._chk(self._L.kslam_debug_index_export(self._h, C.byref(x)))
+        n, m = int(x.n_entries), int(x.n_genome_kmers)
+        need = {"offsets": (n + 1) * 8, "codes": int(x.n_bases), "keys": m * 8, "meta": m * 8,
+                "bucket": ((1 << int(x.bucket_bits)) + 1) * 4, "filter": int(x.n_filter_bytes)}
+        assert need["filter"] == ((1 << int(x.filter_bits)) >> 3 if x.filter_bits else 0)
+        buf = {k: np.full(v + guard, DEBUG_SENTINEL_BYTE, dtype=np.uint8) for k, v in need.items()}
+        for k in need:
+            setattr(x, k, buf[k].ctypes.data)
+        x.cap_offsets, x.cap_codes, x.cap_records = n + 1, int(x.n_bases), m
+        x.cap_bucket, x.cap_filter = (1 << int(x.bucket_bits)) + 1, int(x.n_filter_bytes)
+        self._chk(self._L.kslam_debug_index_export(self._h, C.byref(x)))
+        for k, v in need.items():
+            assert (buf[k][v:] == DEBUG_SENTINEL_BYTE).all(), "kslam_debug_index_export wrote past its %s buffer" % k
+        mo = buf["meta"][:need["meta"]].view(np.uint32).reshape(-1, 2)
+        return {"n_entries": n, "n_genome_kmers": m, "n_bases": int(x.n_bases), "bucket_bits": int(x.bucket_bits),
+                "filter_bits": int(x.filter_bits), "offsets": buf["offsets"][:need["offsets"]].view(np.uint64).copy(),
+                "codes": buf["codes"][:need["codes"]].copy(), "keys": buf["keys"][:need["keys"]].view(np.uint64).copy(),
+                "meta": mo[:, 0].copy(), "offset": mo[:, 1].copy(),
+                "bucket": buf["bucket"][:need["bucket"]].view(np.uint32).copy(),
+                "filter": buf["filter"][:need["filter"]].view(np.uint32).copy()}
 
     def find_overlaps(self):
         out = C.c_void_p()

@@ -649,4 +649,35 @@ kslam_status kslam_debug_overlap_unique(kslam_ctx *c, const uint64_t *keys, uint
   });
 }
 
+// ---- test hook for build_index (tests/test_gpu_index_build.py): the built index copied to the host, table by table.  Read-only:
+// nothing of the context, the index or the sort workspace changes.  Sizes and capacities are settled before the first copy.
+kslam_status kslam_debug_index_export(kslam_ctx *c, kslam_index_export *x) {
+  if (!c || !x) return KSLAM_ERR_ARG;
+  return guarded(c, [&] {
+    const GenomeIndex &ix = c->need_index();
+    HIPCHK(stream_wait(c->stream));
+    const uint64_t n = ix.n_entries, m = ix.n_gk, total = ix.h_goff[n];
+    const uint64_t nb = (1ull << ix.bucket_bits) + 1, fbytes = ix.filter_bits ? filter_bytes(ix.filter_bits) : 0;
+    x->n_entries = n; x->n_genome_kmers = m; x->n_bases = total; x->n_filter_bytes = fbytes;
+    x->bucket_bits = ix.bucket_bits; x->filter_bits = ix.filter_bits;
+    if (!x->offsets && !x->codes && !x->keys && !x->meta && !x->bucket && !x->filter) return;   // the sizes alone
+    auto room = [](const void *p, uint64_t cap, uint64_t need) { return need == 0 || (p && cap >= need); };
+    if (!room(x->offsets, x->cap_offsets, n + 1) || !room(x->codes, x->cap_codes, total) || !room(x->keys, x->cap_records, m) ||
+        !room(x->meta, x->cap_records, m) || !room(x->bucket, x->cap_bucket, nb) || !room(x->filter, x->cap_filter, fbytes))
+      throw StatusError{KSLAM_ERR_ARG, "index export: a buffer is missing or smaller than its table"};
+    hipStream_t s = c->stream;
+    auto copy = [&](void *dst, const DevBuf &src, uint64_t bytes) {
+      if (bytes > src.cap) throw StatusError{KSLAM_ERR_INTERNAL, "index export: a table larger than its allocation"};
+      if (bytes) HIPCHK(hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, s));
+    };
+    copy(x->offsets, ix.g_off, (n + 1) * sizeof(uint64_t));
+    copy(x->codes, ix.g_codes, total);
+    copy(x->keys, ix.gk_key, m * sizeof(uint64_t));
+    copy(x->meta, ix.gk_meta, m * sizeof(uint2));
+    copy(x->bucket, ix.g_bucket, nb * sizeof(uint32_t));
+    copy(x->filter, ix.g_filter, fbytes);
+    HIPCHK(stream_wait(s));
+  });
+}
+
 }  // extern "C"
