@@ -96,6 +96,7 @@ std::shared_ptr<GenomeIndex> new_index(kslam_ctx *c, uint64_t n_entries) {
   kreport_release(c);    // (include/kslam_kreport.h) the annotations, and the tree with them, belong to the old index's entries
   taxreads_release(c);   // (include/kslam_taxreads.h) likewise
   genes_release(c);      // (include/kslam_genes.h) likewise: the gene columns belong to the old index's entries
+  alignqc_release(c);    // (include/kslam_alignqc.h) its counts are of alignments to the old index's entries
   auto ix = std::make_shared<GenomeIndex>();
   ix->n_entries = n_entries;
   ix->h_goff.assign(n_entries + 1, 0);

@@ -260,6 +260,10 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
     // (kslam_set_genes) the batch's final alignment pairs into the owner's per-gene counters, likewise
     if (primary->gen.on.load(std::memory_order_acquire) && st == KSLAM_OK && primary->pairing.stages && !pseudo_left && c->have_pairs)
       st = guarded(c, [&] { genes_count_resident(primary, c); });
+    // (kslam_set_align_qc) the batch's contributing records and live pairs into the owner's per-cycle tables, likewise; the batches
+    // left to the host go in through kslam_align_qc_add after the host stage
+    if (primary->aq.on.load(std::memory_order_acquire) && st == KSLAM_OK && primary->pairing.stages && !pseudo_left && c->have_pairs)
+      st = guarded(c, [&] { alignqc_count_resident(primary, c, job->single); });
     t3 = now();
     // with the SAM records written on the device the host has no use for the rows, the CIGAR pool, the per-row details and
     // the MD text (0.7 GB per batch of configs[1]): they stay where they are, only their counts travel

@@ -894,6 +894,34 @@ uint64_t contributing_list_device(const VariantInputs &in, DevBuf &flag, DevBuf 
 // sorts n u64 keys of `buf` (scratch: `alt`, at least as large) with as many radix passes as max_key needs; the sorted keys end in `buf`
 void sort_keys(DevBuf &buf, DevBuf &alt, uint64_t n, uint64_t max_key, SortWorkspace &ws, hipStream_t s);
 
+// ------------------------------------------------------------ alignqc.hip
+// The alignment QC report (include/kslam_alignqc.h).  The state -- one block of 64-bit counters -- belongs to the context the
+// switch was set on (context.h: kslam_ctx::AlignQc); each lane counts its batch with an AlignQcWork of its own.
+struct AlignQcTable {             // what the passes see
+  unsigned long long *words;     // [KSLAM_ALIGN_QC_WORDS(C)]: the report's words, stream 0's, stream 1's
+  uint32_t C;                    // cycle rows without the pooled one
+};
+struct AlignQcWork {
+  DevBuf flag, pos, list;        // as VariantEmitWork
+  DevBuf scan_tmp, totals;
+  hipEvent_t ev[2]{};            // around the count pass
+  float ms = 0;                  // its device time, last batch counted with `timed`
+  AlignQcWork() = default;
+  AlignQcWork(const AlignQcWork &) = delete;
+  AlignQcWork &operator=(const AlignQcWork &) = delete;
+  ~AlignQcWork() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+// one batch into the table: the pair pass, the contributing list (variants.hip's) and the count pass.  d_quality: the quality
+// column laid out as in.rbases, or null; paired: reads below in.n_reads / 2 are stream 0, the others stream 1; max_len: no read
+// is longer (it sizes the grid's tiles).  timed: events around the count pass, and the call reads them after waiting for the
+// stream; it waits for the stream in any case (the list's length is read back).  thread_per_record: the baseline instantiation.
+void alignqc_count_device(const VariantInputs &in, const uint8_t *d_quality, bool paired, uint64_t max_len, const AlignQcTable &T, AlignQcWork &W,
+                          bool timed, bool thread_per_record, hipStream_t s);
+void alignqc_zero_device(const AlignQcTable &T, hipStream_t s);
+
 // ------------------------------------------------------------ depth.hip
 // The per-base depth track (include/kslam_depth.h).  Boundaries live in a key space with ONE SPARE position per entry,
 // key = g_off[entry] + entry + pos, so that the boundary after the last base of entry e is not the first base of entry e + 1.

@@ -28,6 +28,7 @@
 #include "../../include/kslam_readqc.h"
 #include "../../include/kslam_taxreads.h"
 #include "../../include/kslam_genes.h"
+#include "../../include/kslam_alignqc.h"
 #include "../host/workers.hpp"
 #include "../host/inflate.hpp"
 #include <algorithm>
@@ -239,6 +240,20 @@ struct kslam_ctx {
     std::mutex mu;                // add / take / reset / the lanes' launches / the switch: one at a time
   } rq;
   ReadQcWork rqw;                 // this context's own count passes (a lane's batches; on the primary: kslam_read_qc_add)
+
+  // ---- the alignment QC report's tables (alignqc.hip, include/kslam_alignqc.h) ----
+  struct AlignQc {                // on the context the switch was set on; its lanes count into it (lane_main)
+    std::atomic<bool> on{false};
+    uint32_t C = 0;               // cycle rows, resolved
+    uint64_t n_entries = 0;       // of the index the switch was set for
+    DevBuf words;                 // u64 [KSLAM_ALIGN_QC_WORDS(C)]
+    bool paired = false;          // a batch counted since the last reset was paired
+    DevBuf up_ov, up_groups, up_pairs, up_pool, up_rbases, up_rqual, up_roff;   // kslam_align_qc_add's uploads
+    int stream_fd = -1;           // kslam_stream_set_align_qc
+    uint32_t stream_cycles = 0;
+    std::mutex mu;                // add / take / reset / the lanes' launches / the switch: one at a time
+  } aq;
+  AlignQcWork aqw;                // this context's own count passes (a lane's batches; on the primary: kslam_align_qc_add)
 
   // ---- the reads of chosen taxa (taxreads.hip, include/kslam_taxreads.h) ----
   struct TaxReads {               // on the context kslam_set_taxon_reads was called on; its lanes read it (lane_main)
@@ -462,6 +477,13 @@ void readqc_release(kslam_ctx *c);
 // the batch resident on `lane` (lane->r_bases, r_qual, r_off: the columns cut out of the text it uploaded) into owner's tables,
 // on lane's stream; does not wait
 void readqc_count_resident(kslam_ctx *owner, kslam_ctx *lane, bool single);
+
+// ---- api_alignqc.hip
+// frees the alignment QC state of c and switches it off (kslam_set_align_qc(c, 0, 0), kslam_set_index)
+void alignqc_release(kslam_ctx *c);
+// the batch `lane` has just finished (lane->pres over lane->res_ov, lane->res_cig, lane's reads and, when it holds one, its quality
+// column) into owner's tables, on lane's stream
+void alignqc_count_resident(kslam_ctx *owner, kslam_ctx *lane, bool single);
 
 // ---- api_taxreads.hip
 // frees the selection of c and switches it off (kslam_set_taxon_reads(c, NULL, 0, 0), kslam_set_sam_annotations, kslam_set_index)

@@ -27,6 +27,7 @@
 #include "../../include/kslam_samunmapped.h"
 #include "../../include/kslam_readsplit.h"
 #include "../../include/kslam_coverage.h"
+#include "../../include/kslam_alignqc.h"
 #include "../../include/kslam_genes.h"
 #include "../../include/kslam_kreport.h"
 #include "../../include/kslam_readqc.h"
@@ -90,6 +91,9 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
   int qc_fd = -1;                     // kslam_stream_set_read_qc: where the read QC report goes
   uint32_t qc_cycles = 0;
   bool read_qc_set = false;
+  int aq_fd = -1;                     // kslam_stream_set_align_qc: where the alignment QC report goes
+  uint32_t aq_cycles = 0;
+  bool align_qc_set = false;
   int tr_fds[2] = {-1, -1};           // kslam_stream_set_taxon_reads: where the selected R1 / R2 records go
   bool taxreads_on = false, taxreads_set = false;
   std::vector<uint32_t> tr_ids;       // the chosen ids and the mode, as kslam_set_taxon_reads was given them before this call
@@ -128,6 +132,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     if (ctx) kslam_stream_set_kreport(ctx, -1);
     if (read_qc_set) kslam_set_read_qc(ctx, 0, 0);
     if (ctx) kslam_stream_set_read_qc(ctx, -1, 0);
+    if (align_qc_set) kslam_set_align_qc(ctx, 0, 0);
+    if (ctx) kslam_stream_set_align_qc(ctx, -1, 0);
     if (taxreads_set) kslam_set_taxon_reads(ctx, nullptr, 0, 0);
     if (ctx) kslam_stream_set_taxon_reads(ctx, nullptr);
     if (ctx) kslam_stream_set_reads_out(ctx, nullptr);   // the descriptors held for this call alone
@@ -202,6 +208,13 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       if (kslam_set_read_qc(ctx, 1, qc_cycles) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
       read_qc_set = true;
       if (kslam_read_qc_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+    }
+    // the alignment QC report (include/kslam_alignqc.h): the lanes count what they finish; the file follows the last batch
+    if (kslam_stream_get_align_qc(ctx, &aq_fd, &aq_cycles) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    if (aq_fd >= 0) {
+      if (kslam_set_align_qc(ctx, 1, aq_cycles) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
+      align_qc_set = true;
+      if (kslam_align_qc_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
     }
     const bool host_split = getenv("KSLAM_HOST_SAM_TEXT") && getenv("KSLAM_HOST_SAM_TEXT")[0] == '1';   // (A/B: the host twin for every batch)
     // the SAM records and the per-read lines written on the GPU (include/kslam_samtext.h); KSLAM_HOST_SAM_TEXT=1 keeps the
@@ -469,6 +482,26 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         });
         if (s != KSLAM_OK) err = g_err;
       }
+      // the alignment QC report likewise, with the quality column of the same parse
+      if (s == KSLAM_OK && align_qc_set && P->tail.pseudo_assembly && !(res.pair_stats.stages_done & KSLAM_TAIL_PSEUDO_ASM)) {
+        s = guarded([&] {
+          kslam_reads_columns cols;
+          memset(&cols, 0, sizeof cols);
+          struct Release { kslam_reads_columns *c; ~Release() { kslam_reads_free(c); } } release{&cols};
+          uint64_t c1 = 0, c2 = 0;
+          const kslam_status q = paired ? kslam_fastq_parse_pair(r1 + win.p1, win.e1 - win.p1, r2 + win.p2, win.e2 - win.p2, 0, 1,
+                                                                 P->tail.threads, &cols, &c1, &c2)
+                                        : kslam_fastq_parse(r1 + win.p1, win.e1 - win.p1, 0, 1, P->tail.threads, &cols, &c1);
+          if (q != KSLAM_OK) fail(q, kslam_tail_last_error());
+          if (cols.n_reads != res.n_reads || memcmp(cols.bases_off, res.reads_bases_off, sizeof(uint64_t) * (res.n_reads + 1)) != 0 ||
+              memcmp(cols.quality_off, cols.bases_off, sizeof(uint64_t) * (res.n_reads + 1)) != 0)
+            fail(KSLAM_ERR_INTERNAL, "the host's parse of a batch differs from the device's index");
+          if (kslam_align_qc_add(ctx, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, cols.bases, cols.bases_off, cols.n_reads,
+                                 res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs, cols.quality, paired ? 1 : 0) != KSLAM_OK)
+            fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+        });
+        if (s != KSLAM_OK) err = g_err;
+      }
       // the depth track likewise; it needs the reads' lengths alone, which came back with the batch
       if (s == KSLAM_OK && depth_set && P->tail.pseudo_assembly && !(res.pair_stats.stages_done & KSLAM_TAIL_PSEUDO_ASM)) {
         s = guarded([&] {
@@ -698,6 +731,14 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       qt.paired = paired ? 1 : 0;   // (a run that ends before its first batch is still the kind of run it was asked to be)
       const kslam_status w = kslam_read_qc_write(&qt, qc_fd);
       kslam_read_qc_release(ctx, &qt);
+      if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
+    }
+    if (align_qc_set) {
+      kslam_align_qc_tables at;
+      if (kslam_align_qc_take(ctx, &at) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      at.paired = paired ? 1 : 0;   // (a run that ends before its first batch is still the kind of run it was asked to be)
+      const kslam_status w = kslam_align_qc_write(&at, aq_fd);
+      kslam_align_qc_release(ctx, &at);
       if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
     }
     if (depth_set) {

@@ -43,6 +43,7 @@
 #include "../include/kslam_variants.h"
 #include "../include/kslam_depth.h"
 #include "../include/kslam_genes.h"
+#include "../include/kslam_alignqc.h"
 #include "../include/kslam_stream.h"
 
 namespace {
@@ -85,6 +86,9 @@ struct Options {
   std::string qc_out;                      // --qc-out (include/kslam_readqc.h)
   uint32_t qc_max_cycles = 0;
   bool qc_max_cycles_given = false;
+  std::string align_qc_out;                // --align-qc-out (include/kslam_alignqc.h)
+  uint32_t align_qc_max_cycles = 0;
+  bool align_qc_max_cycles_given = false;
   bool reads_out_bgzf = false;
   std::string extract_out;                 // --extract-out (include/kslam_taxreads.h)
   std::vector<uint32_t> extract_taxids;    // --extract-taxid, repeatable and comma lists
@@ -166,6 +170,10 @@ void usage(FILE *o) {
         "                                        content and quality per cycle, mean quality per read, GC content, Q20 / Q30 rates;\n"
         "                                        works with --just-align, needs no --sam-file\n"
         "  --qc-max-cycles arg (=512)            per-cycle rows of --qc-out, 1 to 65536; later cycles are pooled in one more row\n"
+        "  --align-qc-out arg                    write a QC report on the alignments to this file as JSON: error rate by cycle and by base\n"
+        "                                        quality, substitutions, indel lengths, edit distance, identity, insert sizes; works with\n"
+        "                                        --just-align and single-end, needs no --sam-file\n"
+        "  --align-qc-max-cycles arg (=512)      per-cycle rows of --align-qc-out, 1 to 65536; later cycles are pooled in one more row\n"
         "\n", o);
 }
 
@@ -173,7 +181,7 @@ Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
          PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT,
-         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, DEPTH_OUT, DEPTH_MIN, GENES_OUT, QC_OUT, QC_MAX_CYCLES, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
+         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, DEPTH_OUT, DEPTH_MIN, GENES_OUT, QC_OUT, QC_MAX_CYCLES, ALIGN_QC_OUT, ALIGN_QC_MAX_CYCLES, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -202,6 +210,8 @@ Options parse(int argc, char **argv) {
       {"depth-out", required_argument, nullptr, DEPTH_OUT}, {"depth-min", required_argument, nullptr, DEPTH_MIN},   // not in the reference: include/kslam_depth.h
       {"genes-out", required_argument, nullptr, GENES_OUT},   // not in the reference: include/kslam_genes.h
       {"qc-out", required_argument, nullptr, QC_OUT}, {"qc-max-cycles", required_argument, nullptr, QC_MAX_CYCLES},   // not in the reference: include/kslam_readqc.h
+      // not in the reference: include/kslam_alignqc.h
+      {"align-qc-out", required_argument, nullptr, ALIGN_QC_OUT}, {"align-qc-max-cycles", required_argument, nullptr, ALIGN_QC_MAX_CYCLES},
       {"kraken-report", required_argument, nullptr, KRAKEN_REPORT},   // not in the reference: include/kslam_kreport.h (Kraken 2's --report)
       // not in the reference: include/kslam_taxreads.h (KrakenTools' extract_kraken_reads.py)
       {"extract-taxid", required_argument, nullptr, EXTRACT_TAXID}, {"extract-out", required_argument, nullptr, EXTRACT_OUT},
@@ -246,6 +256,13 @@ Options parse(int argc, char **argv) {
       case GENES_OUT: o.genes_out = optarg; break;
       case DEPTH_MIN: o.depth_min = to_u32(optarg, "depth-min"); o.depth_min_given = true; break;
       case KRAKEN_REPORT: o.kraken_report = optarg; break;
+      case ALIGN_QC_OUT: o.align_qc_out = optarg; break;
+      case ALIGN_QC_MAX_CYCLES:
+        o.align_qc_max_cycles = to_u32(optarg, "align-qc-max-cycles");
+        if (o.align_qc_max_cycles < 1 || o.align_qc_max_cycles > KSLAM_ALIGN_QC_MAX_CYCLES)
+          die(std::string("the argument ('") + optarg + "') for option '--align-qc-max-cycles' is invalid: 1 to 65536");
+        o.align_qc_max_cycles_given = true;
+        break;
       case QC_OUT: o.qc_out = optarg; break;
       case QC_MAX_CYCLES:
         o.qc_max_cycles = to_u32(optarg, "qc-max-cycles");
@@ -304,6 +321,7 @@ Options parse(int argc, char **argv) {
   if (o.variants_min_depth_given && o.variants_out.empty()) die("option '--variants-min-depth' needs '--variants-out'");
   if (o.depth_min_given && o.depth_out.empty()) die("option '--depth-min' needs '--depth-out'");
   if (o.qc_max_cycles_given && o.qc_out.empty()) die("option '--qc-max-cycles' needs '--qc-out'");
+  if (o.align_qc_max_cycles_given && o.align_qc_out.empty()) die("option '--align-qc-max-cycles' needs '--align-qc-out'");
   return o;
 }
 
@@ -510,7 +528,7 @@ int run(const Options &o, const std::string &command_line) {
   kp.gap_extend = o.gap_extend;
   kp.score_threshold = o.score_threshold;
   // reportCigar = a SAM file was asked for (src/SLAM.h:169); the variants walk the CIGARs too (the SAM text follows sp.tail.report_cigar)
-  kp.report_cigar = (want_sam || !o.variants_out.empty() || !o.depth_out.empty()) ? 1 : 0;
+  kp.report_cigar = (want_sam || !o.variants_out.empty() || !o.depth_out.empty() || !o.align_qc_out.empty()) ? 1 : 0;
   kp.device = o.device;
   kslam_ctx *ctx = nullptr;
   if (kslam_create(&kp, &ctx) != KSLAM_OK) die(std::string("GPU context: ") + (ctx ? kslam_last_error(ctx) : "kslam_create failed"));
@@ -608,6 +626,12 @@ int run(const Options &o, const std::string &command_line) {
     if (qc_fd < 0) die("unable to open " + o.qc_out);
     if (kslam_stream_set_read_qc(ctx, qc_fd, o.qc_max_cycles) != KSLAM_OK) die(std::string("read QC: ") + kslam_last_error(ctx));
   }
+  int align_qc_fd = -1;
+  if (!o.align_qc_out.empty()) {
+    align_qc_fd = open(o.align_qc_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (align_qc_fd < 0) die("unable to open " + o.align_qc_out);
+    if (kslam_stream_set_align_qc(ctx, align_qc_fd, o.align_qc_max_cycles) != KSLAM_OK) die(std::string("alignment QC: ") + kslam_last_error(ctx));
+  }
   kslam_stream_params sp;
   memset(&sp, 0, sizeof sp);
   sp.pairs_per_batch = o.num_reads_at_once;
@@ -658,6 +682,7 @@ int run(const Options &o, const std::string &command_line) {
   if (genes_fd >= 0 && close(genes_fd) != 0) die("closing the gene table failed");
   if (kreport_fd >= 0 && close(kreport_fd) != 0) die("closing the Kraken-style report failed");
   if (qc_fd >= 0 && close(qc_fd) != 0) die("closing the read QC report failed");
+  if (align_qc_fd >= 0 && close(align_qc_fd) != 0) die("closing the alignment QC report failed");
   logl(cat("Found ", st.n_overlaps, " k-mer overlaps"));
   logl(cat("", st.n_read_pairs_aligned, " entries have k-mer overlaps"));
   if (paired && st.n_batches) logl(cat("Screening all alignment pairs with insert size >= ", st.first_max_insert_size, ""));
