@@ -9,14 +9,8 @@ namespace {
 
 AlignQcTable table_of(const kslam_ctx *owner) { return AlignQcTable{owner->aq.words.as<unsigned long long>(), owner->aq.C}; }
 
-void need_on(const kslam_ctx *c) {
-  if (!c->aq.on.load(std::memory_order_acquire)) throw StatusError{KSLAM_ERR_STATE, "the alignment QC report is switched off: call kslam_set_align_qc first"};
-}
-
-// every lane's adds are in memory before anybody reads or zeroes the tables
-void wait_for_lanes(kslam_ctx *c) {
-  for (auto *l : c->lanes) HIPCHK(hipStreamSynchronize(l->c->stream));
-}
+const char *const REPORT_IS = "the alignment QC report is";
+const char *const SWITCHED_OFF = "the alignment QC report is switched off: call kslam_set_align_qc first";
 
 void zero_state(kslam_ctx *c) {
   alignqc_zero_device(table_of(c), c->stream);
@@ -41,7 +35,8 @@ void alignqc_release(kslam_ctx *c) {
   kslam_ctx::AlignQc &v = c->aq;
   std::lock_guard<std::mutex> lk(v.mu);
   v.on.store(false, std::memory_order_release);
-  for (DevBuf *b : {&v.words, &v.up_ov, &v.up_groups, &v.up_pairs, &v.up_pool, &v.up_rbases, &v.up_rqual, &v.up_roff}) b->release();
+  v.words.release();
+  v.up.release_all();
   v.C = 0;
   v.n_entries = 0;
   v.paired = false;
@@ -60,10 +55,7 @@ void alignqc_count_resident(kslam_ctx *owner, kslam_ctx *lane, bool single) {
     if (!single) v.paired = true;
     table = table_of(owner);
   }
-  const VariantInputs in{lane->res_ov.as<kslam_overlap>(), lane->n_res, lane->pres.d_groups, lane->pres.n_read_pairs, lane->pres.d_pairs,
-                         lane->pres.n_pairs, lane->res_cig.as<uint32_t>(), lane->n_cig, lane->r_bases.as<uint8_t>(), lane->r_off.as<uint64_t>(),
-                         lane->n_reads, ix.g_bases.as<uint8_t>(), ix.g_off.as<uint64_t>(), ix.n_entries};
-  alignqc_count_device(in, lane->have_qual ? lane->r_qual.as<uint8_t>() : nullptr, !single, lane->max_read_len, table, lane->aqw, false,
+  alignqc_count_device(resident_inputs(lane, ix, true), lane->have_qual ? lane->r_qual.as<uint8_t>() : nullptr, !single, lane->max_read_len, table, lane->aqw, false,
                        thread_per_record(), lane->stream);
 }
 
@@ -73,7 +65,7 @@ extern "C" {
 
 kslam_status kslam_set_align_qc(kslam_ctx *c, int on, uint32_t max_cycles) {
   return guarded(c, [&] {
-    if (c->in_multi) throw StatusError{KSLAM_ERR_UNSUPPORTED, "the alignment QC report is not available on the contexts of a kslam_multi"};
+    if (refused_in_multi(c, REPORT_IS)) throw StatusError{KSLAM_ERR_UNSUPPORTED, c->err};
     if (!on) {
       if (c->aq.on.load(std::memory_order_acquire)) wait_for_lanes(c);
       alignqc_release(c);
@@ -106,18 +98,12 @@ kslam_status kslam_set_align_qc(kslam_ctx *c, int on, uint32_t max_cycles) {
   });
 }
 
-kslam_status kslam_get_align_qc(kslam_ctx *c, int *on, uint32_t *max_cycles) {
-  if (!c || !on || !max_cycles) return KSLAM_ERR_ARG;
-  std::lock_guard<std::mutex> lk(c->aq.mu);
-  *on = c->aq.on.load(std::memory_order_acquire) ? 1 : 0;
-  *max_cycles = *on ? c->aq.C : 0;
-  return KSLAM_OK;
-}
+kslam_status kslam_get_align_qc(kslam_ctx *c, int *on, uint32_t *max_cycles) { return get_switch(c, &kslam_ctx::aq, on, max_cycles); }
 
 kslam_status kslam_align_qc_reset(kslam_ctx *c) {
   return guarded(c, [&] {
     std::lock_guard<std::mutex> lk(c->aq.mu);
-    need_on(c);
+    need_on(c->aq.on, SWITCHED_OFF);
     wait_for_lanes(c);
     zero_state(c);
   });
@@ -132,59 +118,21 @@ kslam_status kslam_align_qc_add(kslam_ctx *c, const kslam_overlap *overlaps, uin
     if (paired && (n_reads & 1)) throw StatusError{KSLAM_ERR_ARG, "a paired batch holds an even number of reads"};
     kslam_ctx::AlignQc &v = c->aq;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->aq.on, SWITCHED_OFF);
     const GenomeIndex &ix = c->need_index();
     if (ix.n_entries != v.n_entries) throw StatusError{KSLAM_ERR_STATE, "the alignment QC report was switched on for another index"};
-    // nothing is launched for arrays that do not hold together
-    if (n_overlaps >= (1ull << 32)) throw StatusError{KSLAM_ERR_ARG, "2^32 or more overlap records"};
-    uint64_t max_len = 0;
-    for (uint64_t i = 0; i < n_reads; i++) {
-      if (read_offsets[i + 1] < read_offsets[i]) throw StatusError{KSLAM_ERR_ARG, "the read offsets must ascend"};
-      max_len = std::max(max_len, read_offsets[i + 1] - read_offsets[i]);
-    }
     const uint64_t n_rbytes = n_reads ? read_offsets[n_reads] : 0;
     if (n_rbytes && !read_bases) throw StatusError{KSLAM_ERR_ARG, "null argument"};
-    uint64_t next = 0;
-    for (uint64_t g = 0; g < n_read_pairs; g++) {
-      const kslam_read_pair &rp = read_pairs[g];
-      if (rp.first > n_pairs || rp.count > n_pairs - rp.first)
-        throw StatusError{KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": first + count lies outside the pairs array"};
-      if (rp.first < next) throw StatusError{KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": the groups' slices must ascend and not overlap"};
-      next = rp.first + rp.count;
-      for (uint64_t k = rp.first; k < rp.first + rp.count; k++)
-        for (uint32_t idx : {pairs[k].r1, pairs[k].r2}) {
-          if (idx == KSLAM_NO_OVERLAP) continue;
-          if (idx >= n_overlaps)
-            throw StatusError{KSLAM_ERR_ARG, "alignment pair " + std::to_string(k) + " refers to overlap record " + std::to_string(idx) + " of " + std::to_string(n_overlaps)};
-          const kslam_overlap &o = overlaps[idx];
-          if (o.cigar_off > n_cigar || o.cigar_len > n_cigar - o.cigar_off)
-            throw StatusError{KSLAM_ERR_ARG, "overlap record " + std::to_string(idx) + ": its CIGAR slice lies outside the pool"};
-          if (o.read >= n_reads)
-            throw StatusError{KSLAM_ERR_ARG, "overlap record " + std::to_string(idx) + " refers to read " + std::to_string(o.read) + " of " + std::to_string(n_reads)};
-        }
-    }
+    // nothing is launched for arrays that do not hold together
+    const kslam_batch::Arrays batch{overlaps, n_overlaps, n_cigar, read_offsets, n_reads, read_pairs, n_read_pairs, pairs, n_pairs};
+    uint64_t max_len = 0;
+    const std::string fault = kslam_batch::check(batch, kslam_batch::Level::records, &max_len);
+    if (!fault.empty()) throw StatusError{KSLAM_ERR_ARG, fault};
     if (paired) v.paired = true;
     c->aqw.ms = 0;
     hipStream_t s = c->stream;
-    v.up_ov.ensure((n_overlaps + 1) * sizeof(kslam_overlap));
-    v.up_groups.ensure((n_read_pairs + 1) * sizeof(kslam_read_pair));
-    v.up_pairs.ensure((n_pairs + 1) * sizeof(kslam_paired_overlap));
-    v.up_pool.ensure((n_cigar + 1) * sizeof(uint32_t));
-    v.up_rbases.ensure(n_rbytes + 64);
-    v.up_rqual.ensure(n_rbytes + 64);
-    v.up_roff.ensure((n_reads + 1) * sizeof(uint64_t));
-    if (n_overlaps) HIPCHK(hipMemcpyAsync(v.up_ov.p, overlaps, n_overlaps * sizeof(kslam_overlap), hipMemcpyHostToDevice, s));
-    if (n_read_pairs) HIPCHK(hipMemcpyAsync(v.up_groups.p, read_pairs, n_read_pairs * sizeof(kslam_read_pair), hipMemcpyHostToDevice, s));
-    if (n_pairs) HIPCHK(hipMemcpyAsync(v.up_pairs.p, pairs, n_pairs * sizeof(kslam_paired_overlap), hipMemcpyHostToDevice, s));
-    if (n_cigar) HIPCHK(hipMemcpyAsync(v.up_pool.p, cigar_pool, n_cigar * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    if (n_rbytes) HIPCHK(hipMemcpyAsync(v.up_rbases.p, read_bases, n_rbytes, hipMemcpyHostToDevice, s));
-    if (n_rbytes && read_quality) HIPCHK(hipMemcpyAsync(v.up_rqual.p, read_quality, n_rbytes, hipMemcpyHostToDevice, s));
-    if (n_reads) HIPCHK(hipMemcpyAsync(v.up_roff.p, read_offsets, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    HIPCHK(stream_wait(s));   // (pageable sources: the caller's arrays are free again)
-    const VariantInputs in{v.up_ov.as<kslam_overlap>(), n_overlaps, v.up_groups.as<kslam_read_pair>(), n_read_pairs,
-                           v.up_pairs.as<kslam_paired_overlap>(), n_pairs, v.up_pool.as<uint32_t>(), n_cigar, v.up_rbases.as<uint8_t>(),
-                           v.up_roff.as<uint64_t>(), n_reads, ix.g_bases.as<uint8_t>(), ix.g_off.as<uint64_t>(), ix.n_entries};
-    alignqc_count_device(in, read_quality ? v.up_rqual.as<uint8_t>() : nullptr, paired != 0, max_len, table_of(c), c->aqw, true, thread_per_record(), s);
+    const VariantInputs in = v.up.upload(batch, kslam_batch::Level::records, cigar_pool, BatchUpload::bases_and_quality, read_bases, read_quality, &ix, s);
+    alignqc_count_device(in, read_quality ? v.up.rqual.as<uint8_t>() : nullptr, paired != 0, max_len, table_of(c), c->aqw, true, thread_per_record(), s);
   });
 }
 
@@ -195,7 +143,7 @@ kslam_status kslam_align_qc_take(kslam_ctx *c, kslam_align_qc_tables *tables) {
     if (!tables) throw StatusError{KSLAM_ERR_ARG, "null argument"};
     kslam_ctx::AlignQc &v = c->aq;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->aq.on, SWITCHED_OFF);
     wait_for_lanes(c);
     hipStream_t s = c->stream;
     const uint32_t C = v.C;
@@ -259,7 +207,7 @@ kslam_status kslam_align_qc_kernel_ms(kslam_ctx *c, double *count_ms) {
 
 kslam_status kslam_stream_set_align_qc(kslam_ctx *c, int fd, uint32_t max_cycles) {
   if (!c) return KSLAM_ERR_ARG;
-  if (c->in_multi) { c->err = "the alignment QC report is not available on the contexts of a kslam_multi"; return KSLAM_ERR_UNSUPPORTED; }
+  if (refused_in_multi(c, REPORT_IS)) return KSLAM_ERR_UNSUPPORTED;
   if (max_cycles > KSLAM_ALIGN_QC_MAX_CYCLES) { c->err = "max_cycles must be 0 (= 512) or 1 .. 65536"; return KSLAM_ERR_ARG; }
   c->aq.stream_fd = fd >= 0 ? fd : -1;
   c->aq.stream_cycles = max_cycles;

@@ -13,9 +13,8 @@ CoverageTable table_of(const kslam_ctx *owner, const GenomeIndex &ix) {
                        v.word_off.as<uint64_t>(), ix.g_off.as<uint64_t>(), v.n_entries, v.n_words};
 }
 
-void need_on(const kslam_ctx *c) {
-  if (!c->cov.on.load(std::memory_order_acquire)) throw StatusError{KSLAM_ERR_STATE, "coverage is switched off: call kslam_set_coverage first"};
-}
+const char *const REPORT_IS = "the coverage table is";
+const char *const SWITCHED_OFF = "coverage is switched off: call kslam_set_coverage first";
 
 void zero_state(kslam_ctx *c) {
   kslam_ctx::Coverage &v = c->cov;
@@ -25,26 +24,30 @@ void zero_state(kslam_ctx *c) {
   HIPCHK(stream_wait(c->stream));
 }
 
-// every lane's marks are in memory before anybody reads or zeroes the table
-void wait_for_lanes(kslam_ctx *c) {
-  for (auto *l : c->lanes) HIPCHK(hipStreamSynchronize(l->c->stream));
-}
-
 }  // namespace
 
 void coverage_release(kslam_ctx *c) {
   kslam_ctx::Coverage &v = c->cov;
   std::lock_guard<std::mutex> lk(v.mu);
   v.on.store(false, std::memory_order_release);
-  for (DevBuf *b : {&v.bitmap, &v.rows, &v.skipped, &v.word_off, &v.up_ov, &v.up_groups, &v.up_pairs}) b->release();
+  for (DevBuf *b : {&v.bitmap, &v.rows, &v.skipped, &v.word_off}) b->release();
+  v.up.release_all();
   v.n_entries = v.n_words = 0;
 }
 
 void coverage_mark_resident(kslam_ctx *owner, kslam_ctx *lane) {
   const GenomeIndex &ix = lane->need_index();
-  if (ix.n_entries != owner->cov.n_entries) throw StatusError{KSLAM_ERR_STATE, "the coverage table was laid out for another index"};
-  coverage_mark_device(lane->res_ov.as<kslam_overlap>(), lane->n_res, lane->pres.d_groups, lane->pres.n_read_pairs, lane->pres.d_pairs,
-                       lane->pres.n_pairs, table_of(owner, ix), lane->covw, lane->stream);
+  kslam_ctx::Coverage &v = owner->cov;
+  CoverageTable table;
+  {   // the pass runs without the lock (the work buffers are the lane's own, the marks are atomics): the lanes do not wait for each
+      // other; the switch is set between batches and waits for the lanes' streams before it frees anything
+    std::lock_guard<std::mutex> lk(v.mu);
+    if (!v.on.load(std::memory_order_acquire)) throw StatusError{KSLAM_ERR_STATE, "the coverage table was switched off while a batch was in flight"};
+    if (ix.n_entries != v.n_entries) throw StatusError{KSLAM_ERR_STATE, "the coverage table was laid out for another index"};
+    table = table_of(owner, ix);
+  }
+  const VariantInputs in = resident_inputs(lane, ix, false);
+  coverage_mark_device(in.ov, in.n_ov, in.groups, in.n_groups, in.pairs, in.n_pairs, table, lane->covw, lane->stream);
 }
 
 }  // namespace kslam_api
@@ -53,7 +56,7 @@ extern "C" {
 
 kslam_status kslam_set_coverage(kslam_ctx *c, int on) {
   return guarded(c, [&] {
-    if (c->in_multi) throw StatusError{KSLAM_ERR_UNSUPPORTED, "the coverage table is not available on the contexts of a kslam_multi"};
+    if (refused_in_multi(c, REPORT_IS)) throw StatusError{KSLAM_ERR_UNSUPPORTED, c->err};
     if (!on) {
       if (c->cov.on.load(std::memory_order_acquire)) wait_for_lanes(c);
       coverage_release(c);
@@ -87,16 +90,12 @@ kslam_status kslam_set_coverage(kslam_ctx *c, int on) {
   });
 }
 
-kslam_status kslam_get_coverage(kslam_ctx *c, int *on) {
-  if (!c || !on) return KSLAM_ERR_ARG;
-  *on = c->cov.on.load(std::memory_order_acquire) ? 1 : 0;
-  return KSLAM_OK;
-}
+kslam_status kslam_get_coverage(kslam_ctx *c, int *on) { return get_switch(c, &kslam_ctx::cov, on); }
 
 kslam_status kslam_coverage_reset(kslam_ctx *c) {
   return guarded(c, [&] {
     std::lock_guard<std::mutex> lk(c->cov.mu);
-    need_on(c);
+    need_on(c->cov.on, SWITCHED_OFF);
     wait_for_lanes(c);
     zero_state(c);
   });
@@ -108,45 +107,23 @@ kslam_status kslam_coverage_add(kslam_ctx *c, const kslam_overlap *overlaps, uin
     if ((n_overlaps && !overlaps) || (n_read_pairs && !read_pairs) || (n_pairs && !pairs)) throw StatusError{KSLAM_ERR_ARG, "null argument"};
     kslam_ctx::Coverage &v = c->cov;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->cov.on, SWITCHED_OFF);
     const GenomeIndex &ix = c->need_index();
     // nothing is launched for arrays that do not hold together
-    if (n_overlaps >= (1ull << 32)) throw StatusError{KSLAM_ERR_ARG, "2^32 or more overlap records"};
-    uint64_t next = 0;
-    for (uint64_t g = 0; g < n_read_pairs; g++) {
-      const kslam_read_pair &rp = read_pairs[g];
-      if (rp.first > n_pairs || rp.count > n_pairs - rp.first)
-        throw StatusError{KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": first + count lies outside the pairs array"};
-      if (rp.first < next) throw StatusError{KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": the groups' slices must ascend and not overlap"};
-      next = rp.first + rp.count;
-      for (uint64_t k = rp.first; k < rp.first + rp.count; k++)
-        for (uint32_t idx : {pairs[k].r1, pairs[k].r2})
-          if (idx != KSLAM_NO_OVERLAP && idx >= n_overlaps)
-            throw StatusError{KSLAM_ERR_ARG, "alignment pair " + std::to_string(k) + " refers to overlap record " + std::to_string(idx) + " of " + std::to_string(n_overlaps)};
-    }
+    const kslam_batch::Arrays batch{overlaps, n_overlaps, 0, nullptr, 0, read_pairs, n_read_pairs, pairs, n_pairs};
+    const std::string fault = kslam_batch::check(batch, kslam_batch::Level::pairs);
+    if (!fault.empty()) throw StatusError{KSLAM_ERR_ARG, fault};
     hipStream_t s = c->stream;
-    v.up_ov.ensure((n_overlaps + 1) * sizeof(kslam_overlap));
-    v.up_groups.ensure((n_read_pairs + 1) * sizeof(kslam_read_pair));
-    v.up_pairs.ensure((n_pairs + 1) * sizeof(kslam_paired_overlap));
-    if (n_overlaps) HIPCHK(hipMemcpyAsync(v.up_ov.p, overlaps, n_overlaps * sizeof(kslam_overlap), hipMemcpyHostToDevice, s));
-    if (n_read_pairs) HIPCHK(hipMemcpyAsync(v.up_groups.p, read_pairs, n_read_pairs * sizeof(kslam_read_pair), hipMemcpyHostToDevice, s));
-    if (n_pairs) HIPCHK(hipMemcpyAsync(v.up_pairs.p, pairs, n_pairs * sizeof(kslam_paired_overlap), hipMemcpyHostToDevice, s));
-    HIPCHK(stream_wait(s));   // (pageable sources: the caller's arrays are free again)
-    coverage_mark_device(v.up_ov.as<kslam_overlap>(), n_overlaps, v.up_groups.as<kslam_read_pair>(), n_read_pairs,
-                         v.up_pairs.as<kslam_paired_overlap>(), n_pairs, table_of(c, ix), c->covw, s);
+    const VariantInputs in = v.up.upload(batch, kslam_batch::Level::pairs, nullptr, BatchUpload::no_columns, nullptr, nullptr, &ix, s);
+    coverage_mark_device(in.ov, in.n_ov, in.groups, in.n_groups, in.pairs, in.n_pairs, table_of(c, ix), c->covw, s);
   });
 }
 
 kslam_status kslam_coverage_take(kslam_ctx *c, kslam_entry_coverage **rows, uint64_t *n_entries, uint64_t *n_skipped) {
-  if (rows) *rows = nullptr;
-  if (n_entries) *n_entries = 0;
-  if (n_skipped) *n_skipped = 0;
-  kslam_entry_coverage *h = nullptr;
-  const kslam_status st = guarded(c, [&] {
-    if (!rows || !n_entries || !n_skipped) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+  return take_rows(c, rows, n_entries, n_skipped, [&](kslam_entry_coverage *&h) {
     kslam_ctx::Coverage &v = c->cov;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->cov.on, SWITCHED_OFF);
     const GenomeIndex &ix = c->need_index();
     wait_for_lanes(c);
     hipStream_t s = c->stream;
@@ -159,20 +136,13 @@ kslam_status kslam_coverage_take(kslam_ctx *c, kslam_entry_coverage **rows, uint
     v.count_ms = ms;
     *n_entries = v.n_entries;
   });
-  if (st != KSLAM_OK) {
-    if (h) pinned_put(c, h);
-    if (n_skipped) *n_skipped = 0;
-    return st;
-  }
-  *rows = h;
-  return KSLAM_OK;
 }
 
 kslam_status kslam_coverage_bitmap(kslam_ctx *c, uint64_t entry, uint64_t *words, uint64_t n_words) {
   return guarded(c, [&] {
     kslam_ctx::Coverage &v = c->cov;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->cov.on, SWITCHED_OFF);
     const GenomeIndex &ix = c->need_index();
     if (entry >= v.n_entries) throw StatusError{KSLAM_ERR_ARG, "no such entry"};
     const uint64_t len = ix.h_goff[entry + 1] - ix.h_goff[entry], want = (len + 63) / 64;
@@ -195,7 +165,7 @@ kslam_status kslam_coverage_kernel_ms(kslam_ctx *c, double *mark_ms, double *cou
 
 kslam_status kslam_stream_set_coverage(kslam_ctx *c, int fd) {
   if (!c) return KSLAM_ERR_ARG;
-  if (c->in_multi) { c->err = "the coverage table is not available on the contexts of a kslam_multi"; return KSLAM_ERR_UNSUPPORTED; }
+  if (refused_in_multi(c, REPORT_IS)) return KSLAM_ERR_UNSUPPORTED;
   c->cov.stream_fd = fd >= 0 ? fd : -1;
   return KSLAM_OK;
 }

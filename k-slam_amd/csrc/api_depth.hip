@@ -11,14 +11,8 @@ namespace {
 constexpr uint64_t DEP_MAX_KEYS = 0xFFFFFFFFull;        // the radix sort's limit
 constexpr uint64_t DEP_COMPACT_AT = 1ull << 27;         // pending keys: 1 GiB of them plus as much sort scratch
 
-void need_on(const kslam_ctx *c) {
-  if (!c->dep.on.load(std::memory_order_acquire)) throw StatusError{KSLAM_ERR_STATE, "the depth track is switched off: call kslam_set_depth first"};
-}
-
-// every lane's appends are in memory before anybody sorts or empties the arrays
-void wait_for_lanes(kslam_ctx *c) {
-  for (auto *l : c->lanes) HIPCHK(hipStreamSynchronize(l->c->stream));
-}
+const char *const REPORT_IS = "the depth track is";
+const char *const SWITCHED_OFF = "the depth track is switched off: call kslam_set_depth first";
 
 void empty_state(kslam_ctx::Depth &d) {
   d.n_pend = d.n_keys = d.n_records = d.n_skipped = d.n_iv = 0;
@@ -71,10 +65,10 @@ void depth_release(kslam_ctx *c) {
   std::lock_guard<std::mutex> lk(d.mu);
   d.on.store(false, std::memory_order_release);
   DepthWork &T = d.tw;
-  for (DevBuf *b : {&d.pending, &d.ckey, &d.cnet, &d.up_ov, &d.up_groups, &d.up_pairs, &d.up_pool, &d.up_roff, &T.alt, &T.head, &T.run, &T.starts, &T.pkey,
-                    &T.pnet, &T.mkey, &T.mnet, &T.keep, &T.at, &T.nkey, &T.nnet, &T.tile_sum, &T.depth, &T.rows, &T.scan_tmp, &T.totals, &T.sortws.hist,
-                    &T.sortws.status, &T.sortws.tickets, &T.sortws.digits})
+  for (DevBuf *b : {&d.pending, &d.ckey, &d.cnet, &T.alt, &T.head, &T.run, &T.starts, &T.pkey, &T.pnet, &T.mkey, &T.mnet, &T.keep, &T.at, &T.nkey, &T.nnet,
+                    &T.tile_sum, &T.depth, &T.rows, &T.scan_tmp, &T.totals, &T.sortws.hist, &T.sortws.status, &T.sortws.tickets, &T.sortws.digits})
     b->release();
+  d.up.release_all();
   empty_state(d);
   d.n_entries = d.max_key = 0;
 }
@@ -82,10 +76,7 @@ void depth_release(kslam_ctx *c) {
 void depth_emit_resident(kslam_ctx *owner, kslam_ctx *lane) {
   const GenomeIndex &ix = lane->need_index();
   if (ix.n_entries != owner->dep.n_entries) throw StatusError{KSLAM_ERR_STATE, "the depth track was laid out for another index"};
-  const VariantInputs in{lane->res_ov.as<kslam_overlap>(), lane->n_res, lane->pres.d_groups, lane->pres.n_read_pairs, lane->pres.d_pairs,
-                         lane->pres.n_pairs, lane->res_cig.as<uint32_t>(), lane->n_cig, nullptr, lane->r_off.as<uint64_t>(),
-                         lane->n_reads, nullptr, ix.g_off.as<uint64_t>(), ix.n_entries};
-  emit(owner, in, lane->depw, lane->stream, false);
+  emit(owner, resident_inputs(lane, ix, false), lane->depw, lane->stream, false);
 }
 
 }  // namespace kslam_api
@@ -94,7 +85,7 @@ extern "C" {
 
 kslam_status kslam_set_depth(kslam_ctx *c, int on) {
   return guarded(c, [&] {
-    if (c->in_multi) throw StatusError{KSLAM_ERR_UNSUPPORTED, "the depth track is not available on the contexts of a kslam_multi"};
+    if (refused_in_multi(c, REPORT_IS)) throw StatusError{KSLAM_ERR_UNSUPPORTED, c->err};
     if (!on) {
       if (c->dep.on.load(std::memory_order_acquire)) wait_for_lanes(c);
       depth_release(c);
@@ -116,16 +107,12 @@ kslam_status kslam_set_depth(kslam_ctx *c, int on) {
   });
 }
 
-kslam_status kslam_get_depth(kslam_ctx *c, int *on) {
-  if (!c || !on) return KSLAM_ERR_ARG;
-  *on = c->dep.on.load(std::memory_order_acquire) ? 1 : 0;
-  return KSLAM_OK;
-}
+kslam_status kslam_get_depth(kslam_ctx *c, int *on) { return get_switch(c, &kslam_ctx::dep, on); }
 
 kslam_status kslam_depth_reset(kslam_ctx *c) {
   return guarded(c, [&] {
     std::lock_guard<std::mutex> lk(c->dep.mu);
-    need_on(c);
+    need_on(c->dep.on, SWITCHED_OFF);
     wait_for_lanes(c);
     empty_state(c->dep);
   });
@@ -146,60 +133,23 @@ kslam_status kslam_depth_add(kslam_ctx *c, const kslam_overlap *overlaps, uint64
       throw StatusError{KSLAM_ERR_ARG, "null argument"};
     kslam_ctx::Depth &d = c->dep;
     std::lock_guard<std::mutex> lk(d.mu);
-    need_on(c);
+    need_on(c->dep.on, SWITCHED_OFF);
     const GenomeIndex &ix = c->need_index();
     // nothing is launched for arrays that do not hold together
-    if (n_overlaps >= (1ull << 32)) throw StatusError{KSLAM_ERR_ARG, "2^32 or more overlap records"};
-    for (uint64_t i = 0; i < n_reads; i++)
-      if (read_offsets[i + 1] < read_offsets[i]) throw StatusError{KSLAM_ERR_ARG, "the read offsets must ascend"};
-    uint64_t next = 0;
-    for (uint64_t g = 0; g < n_read_pairs; g++) {
-      const kslam_read_pair &rp = read_pairs[g];
-      if (rp.first > n_pairs || rp.count > n_pairs - rp.first)
-        throw StatusError{KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": first + count lies outside the pairs array"};
-      if (rp.first < next) throw StatusError{KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": the groups' slices must ascend and not overlap"};
-      next = rp.first + rp.count;
-      for (uint64_t k = rp.first; k < rp.first + rp.count; k++)
-        for (uint32_t idx : {pairs[k].r1, pairs[k].r2}) {
-          if (idx == KSLAM_NO_OVERLAP) continue;
-          if (idx >= n_overlaps)
-            throw StatusError{KSLAM_ERR_ARG, "alignment pair " + std::to_string(k) + " refers to overlap record " + std::to_string(idx) + " of " + std::to_string(n_overlaps)};
-          const kslam_overlap &o = overlaps[idx];
-          if (o.cigar_off > n_cigar || o.cigar_len > n_cigar - o.cigar_off)
-            throw StatusError{KSLAM_ERR_ARG, "overlap record " + std::to_string(idx) + ": its CIGAR slice lies outside the pool"};
-          if (o.read >= n_reads)
-            throw StatusError{KSLAM_ERR_ARG, "overlap record " + std::to_string(idx) + " refers to read " + std::to_string(o.read) + " of " + std::to_string(n_reads)};
-        }
-    }
+    const kslam_batch::Arrays batch{overlaps, n_overlaps, n_cigar, read_offsets, n_reads, read_pairs, n_read_pairs, pairs, n_pairs};
+    const std::string fault = kslam_batch::check(batch, kslam_batch::Level::records);
+    if (!fault.empty()) throw StatusError{KSLAM_ERR_ARG, fault};
     hipStream_t s = c->stream;
-    d.up_ov.ensure((n_overlaps + 1) * sizeof(kslam_overlap));
-    d.up_groups.ensure((n_read_pairs + 1) * sizeof(kslam_read_pair));
-    d.up_pairs.ensure((n_pairs + 1) * sizeof(kslam_paired_overlap));
-    d.up_pool.ensure((n_cigar + 1) * sizeof(uint32_t));
-    d.up_roff.ensure((n_reads + 1) * sizeof(uint64_t));
-    if (n_overlaps) HIPCHK(hipMemcpyAsync(d.up_ov.p, overlaps, n_overlaps * sizeof(kslam_overlap), hipMemcpyHostToDevice, s));
-    if (n_read_pairs) HIPCHK(hipMemcpyAsync(d.up_groups.p, read_pairs, n_read_pairs * sizeof(kslam_read_pair), hipMemcpyHostToDevice, s));
-    if (n_pairs) HIPCHK(hipMemcpyAsync(d.up_pairs.p, pairs, n_pairs * sizeof(kslam_paired_overlap), hipMemcpyHostToDevice, s));
-    if (n_cigar) HIPCHK(hipMemcpyAsync(d.up_pool.p, cigar_pool, n_cigar * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    if (n_reads) HIPCHK(hipMemcpyAsync(d.up_roff.p, read_offsets, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    HIPCHK(stream_wait(s));   // (pageable sources: the caller's arrays are free again)
-    const VariantInputs in{d.up_ov.as<kslam_overlap>(), n_overlaps, d.up_groups.as<kslam_read_pair>(), n_read_pairs,
-                           d.up_pairs.as<kslam_paired_overlap>(), n_pairs, d.up_pool.as<uint32_t>(), n_cigar, nullptr,
-                           d.up_roff.as<uint64_t>(), n_reads, nullptr, ix.g_off.as<uint64_t>(), ix.n_entries};
+    const VariantInputs in = d.up.upload(batch, kslam_batch::Level::records, cigar_pool, BatchUpload::no_columns, nullptr, nullptr, &ix, s);
     emit(c, in, c->depw, s, true);
   });
 }
 
 kslam_status kslam_depth_take(kslam_ctx *c, uint32_t min_depth, kslam_depth_row **rows, uint64_t *n_rows, kslam_depth_stats *stats) {
-  if (rows) *rows = nullptr;
-  if (n_rows) *n_rows = 0;
-  if (stats) memset(stats, 0, sizeof *stats);
-  kslam_depth_row *h = nullptr;
-  const kslam_status st = guarded(c, [&] {
-    if (!rows || !n_rows || !stats) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+  return take_rows(c, rows, n_rows, stats, [&](kslam_depth_row *&h) {
     kslam_ctx::Depth &d = c->dep;
     std::lock_guard<std::mutex> lk(d.mu);
-    need_on(c);
+    need_on(c->dep.on, SWITCHED_OFF);
     const GenomeIndex &ix = c->need_index();
     wait_for_lanes(c);
     hipStream_t s = c->stream;
@@ -226,14 +176,6 @@ kslam_status kslam_depth_take(kslam_ctx *c, uint32_t min_depth, kslam_depth_row 
     stats->covered_bases = out[1];
     stats->max_depth = out[2];
   });
-  if (st != KSLAM_OK) {
-    if (h) pinned_put(c, h);
-    if (n_rows) *n_rows = 0;
-    if (stats) memset(stats, 0, sizeof *stats);
-    return st;
-  }
-  *rows = h;
-  return KSLAM_OK;
 }
 
 kslam_status kslam_depth_kernel_ms(kslam_ctx *c, double *emit_ms, double *compact_ms, double *take_ms) {
@@ -246,7 +188,7 @@ kslam_status kslam_depth_kernel_ms(kslam_ctx *c, double *emit_ms, double *compac
 
 kslam_status kslam_stream_set_depth(kslam_ctx *c, int fd, uint32_t min_depth) {
   if (!c) return KSLAM_ERR_ARG;
-  if (c->in_multi) { c->err = "the depth track is not available on the contexts of a kslam_multi"; return KSLAM_ERR_UNSUPPORTED; }
+  if (refused_in_multi(c, REPORT_IS)) return KSLAM_ERR_UNSUPPORTED;
   c->dep.stream_fd = fd >= 0 ? fd : -1;
   c->dep.stream_min_depth = min_depth;
   return KSLAM_OK;

@@ -14,9 +14,8 @@ GeneTable table_of(const kslam_ctx *owner) {
                    v.sstop.as<int32_t>(), v.runmax.as<int32_t>(), v.rows.as<unsigned long long>(), v.stats.as<unsigned long long>()};
 }
 
-void need_on(const kslam_ctx *c) {
-  if (!c->gen.on.load(std::memory_order_acquire)) throw StatusError{KSLAM_ERR_STATE, "the gene table is switched off: call kslam_set_genes first"};
-}
+const char *const REPORT_IS = "the gene table is";
+const char *const SWITCHED_OFF = "the gene table is switched off: call kslam_set_genes first";
 
 // the annotations the state was laid out for are still the context's
 void need_same_annotations(const kslam_ctx *c) {
@@ -31,11 +30,6 @@ void zero_state(kslam_ctx *c) {
   HIPCHK(stream_wait(c->stream));
 }
 
-// every lane's counts are in memory before anybody reads or zeroes the table
-void wait_for_lanes(kslam_ctx *c) {
-  for (auto *l : c->lanes) HIPCHK(hipStreamSynchronize(l->c->stream));
-}
-
 // measurement and cross-check: KSLAM_GENES_LOOKUP=linear makes the count pass walk all genes of the entry (the same rows)
 bool linear_lookup() {
   const char *e = getenv("KSLAM_GENES_LOOKUP");
@@ -43,9 +37,10 @@ bool linear_lookup() {
 }
 
 void release_buffers(kslam_ctx::Genes &v) {
-  for (DevBuf *b : {&v.order, &v.sstart, &v.sstop, &v.runmax, &v.rows, &v.stats, &v.up_groups, &v.up_pairs, &v.lk_in, &v.lk_out, &v.tw.flag, &v.tw.pos,
+  for (DevBuf *b : {&v.order, &v.sstart, &v.sstop, &v.runmax, &v.rows, &v.stats, &v.lk_in, &v.lk_out, &v.tw.flag, &v.tw.pos,
                     &v.tw.rows, &v.tw.scan_tmp, &v.tw.totals})
     b->release();
+  v.up.release_all();
   v.n_entries = v.n_genes = 0;
 }
 
@@ -59,10 +54,19 @@ void genes_release(kslam_ctx *c) {
 }
 
 void genes_count_resident(kslam_ctx *owner, kslam_ctx *lane) {
-  need_same_annotations(owner);
-  if (lane->need_index().n_entries != owner->gen.n_entries) throw StatusError{KSLAM_ERR_STATE, "the gene table was laid out for another index"};
-  genes_count_device(lane->pres.d_groups, lane->pres.n_read_pairs, lane->pres.d_pairs, lane->pres.n_pairs, table_of(owner), lane->genw, linear_lookup(),
-                     lane->stream);
+  const GenomeIndex &ix = lane->need_index();
+  kslam_ctx::Genes &v = owner->gen;
+  GeneTable table;
+  {   // the pass runs without the lock (the work buffers are the lane's own, the counts are atomics): the lanes do not wait for each
+      // other; the switch is set between batches and waits for the lanes' streams before it frees anything
+    std::lock_guard<std::mutex> lk(v.mu);
+    if (!v.on.load(std::memory_order_acquire)) throw StatusError{KSLAM_ERR_STATE, "the gene table was switched off while a batch was in flight"};
+    need_same_annotations(owner);
+    if (ix.n_entries != v.n_entries) throw StatusError{KSLAM_ERR_STATE, "the gene table was laid out for another index"};
+    table = table_of(owner);
+  }
+  const VariantInputs in = resident_inputs(lane, ix, false);
+  genes_count_device(in.groups, in.n_groups, in.pairs, in.n_pairs, table, lane->genw, linear_lookup(), lane->stream);
 }
 
 }  // namespace kslam_api
@@ -71,7 +75,7 @@ extern "C" {
 
 kslam_status kslam_set_genes(kslam_ctx *c, int on) {
   return guarded(c, [&] {
-    if (c->in_multi) throw StatusError{KSLAM_ERR_UNSUPPORTED, "the gene table is not available on the contexts of a kslam_multi"};
+    if (refused_in_multi(c, REPORT_IS)) throw StatusError{KSLAM_ERR_UNSUPPORTED, c->err};
     if (!on) {
       if (c->gen.on.load(std::memory_order_acquire)) wait_for_lanes(c);
       genes_release(c);
@@ -121,16 +125,12 @@ kslam_status kslam_set_genes(kslam_ctx *c, int on) {
   });
 }
 
-kslam_status kslam_get_genes(kslam_ctx *c, int *on) {
-  if (!c || !on) return KSLAM_ERR_ARG;
-  *on = c->gen.on.load(std::memory_order_acquire) ? 1 : 0;
-  return KSLAM_OK;
-}
+kslam_status kslam_get_genes(kslam_ctx *c, int *on) { return get_switch(c, &kslam_ctx::gen, on); }
 
 kslam_status kslam_genes_reset(kslam_ctx *c) {
   return guarded(c, [&] {
     std::lock_guard<std::mutex> lk(c->gen.mu);
-    need_on(c);
+    need_on(c->gen.on, SWITCHED_OFF);
     wait_for_lanes(c);
     zero_state(c);
   });
@@ -142,38 +142,23 @@ kslam_status kslam_genes_add(kslam_ctx *c, const kslam_read_pair *read_pairs, ui
     if ((n_read_pairs && !read_pairs) || (n_pairs && !pairs)) throw StatusError{KSLAM_ERR_ARG, "null argument"};
     kslam_ctx::Genes &v = c->gen;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->gen.on, SWITCHED_OFF);
     need_same_annotations(c);
     // nothing is launched for arrays that do not hold together
-    uint64_t next = 0;
-    for (uint64_t g = 0; g < n_read_pairs; g++) {
-      const kslam_read_pair &rp = read_pairs[g];
-      if (rp.first > n_pairs || rp.count > n_pairs - rp.first)
-        throw StatusError{KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": first + count lies outside the pairs array"};
-      if (rp.first < next) throw StatusError{KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": the groups' slices must ascend and not overlap"};
-      next = rp.first + rp.count;
-    }
+    const kslam_batch::Arrays batch{nullptr, 0, 0, nullptr, 0, read_pairs, n_read_pairs, pairs, n_pairs};
+    const std::string fault = kslam_batch::check(batch, kslam_batch::Level::groups);
+    if (!fault.empty()) throw StatusError{KSLAM_ERR_ARG, fault};
     hipStream_t s = c->stream;
-    v.up_groups.ensure((n_read_pairs + 1) * sizeof(kslam_read_pair));
-    v.up_pairs.ensure((n_pairs + 1) * sizeof(kslam_paired_overlap));
-    if (n_read_pairs) HIPCHK(hipMemcpyAsync(v.up_groups.p, read_pairs, n_read_pairs * sizeof(kslam_read_pair), hipMemcpyHostToDevice, s));
-    if (n_pairs) HIPCHK(hipMemcpyAsync(v.up_pairs.p, pairs, n_pairs * sizeof(kslam_paired_overlap), hipMemcpyHostToDevice, s));
-    HIPCHK(stream_wait(s));   // (pageable sources: the caller's arrays are free again)
-    genes_count_device(v.up_groups.as<kslam_read_pair>(), n_read_pairs, v.up_pairs.as<kslam_paired_overlap>(), n_pairs, table_of(c), c->genw,
-                       linear_lookup(), s);
+    const VariantInputs in = v.up.upload(batch, kslam_batch::Level::groups, nullptr, BatchUpload::no_columns, nullptr, nullptr, nullptr, s);
+    genes_count_device(in.groups, in.n_groups, in.pairs, in.n_pairs, table_of(c), c->genw, linear_lookup(), s);
   });
 }
 
 kslam_status kslam_genes_take(kslam_ctx *c, kslam_gene_row **rows, uint64_t *n_rows, kslam_gene_stats *stats) {
-  if (rows) *rows = nullptr;
-  if (n_rows) *n_rows = 0;
-  if (stats) memset(stats, 0, sizeof *stats);
-  kslam_gene_row *h = nullptr;
-  const kslam_status st = guarded(c, [&] {
-    if (!rows || !n_rows || !stats) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+  return take_rows(c, rows, n_rows, stats, [&](kslam_gene_row *&h) {
     kslam_ctx::Genes &v = c->gen;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->gen.on, SWITCHED_OFF);
     need_same_annotations(c);
     wait_for_lanes(c);
     hipStream_t s = c->stream;
@@ -193,14 +178,6 @@ kslam_status kslam_genes_take(kslam_ctx *c, kslam_gene_row **rows, uint64_t *n_r
     stats->n_rows = n;
     *n_rows = n;
   });
-  if (st != KSLAM_OK) {
-    if (h) pinned_put(c, h);
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (n_rows) *n_rows = 0;
-    return st;
-  }
-  *rows = h;
-  return KSLAM_OK;
 }
 
 kslam_status kslam_genes_lookup(kslam_ctx *c, const uint32_t *entries, const int32_t *starts, const int32_t *stops, uint64_t n, int64_t *genes_out,
@@ -210,7 +187,7 @@ kslam_status kslam_genes_lookup(kslam_ctx *c, const uint32_t *entries, const int
     if (n >= (1ull << 32)) throw StatusError{KSLAM_ERR_ARG, "2^32 triples or more"};
     kslam_ctx::Genes &v = c->gen;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->gen.on, SWITCHED_OFF);
     need_same_annotations(c);
     if (!n) return;
     hipStream_t s = c->stream;
@@ -239,7 +216,7 @@ kslam_status kslam_genes_kernel_ms(kslam_ctx *c, double *build_ms, double *count
 
 kslam_status kslam_stream_set_genes(kslam_ctx *c, int fd) {
   if (!c) return KSLAM_ERR_ARG;
-  if (c->in_multi) { c->err = "the gene table is not available on the contexts of a kslam_multi"; return KSLAM_ERR_UNSUPPORTED; }
+  if (refused_in_multi(c, REPORT_IS)) return KSLAM_ERR_UNSUPPORTED;
   c->gen.stream_fd = fd >= 0 ? fd : -1;
   return KSLAM_OK;
 }

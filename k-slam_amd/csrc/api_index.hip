@@ -90,13 +90,7 @@ void run_extract(kslam_ctx *c, const uint8_t *d_bases, const uint64_t *d_off, ui
 std::shared_ptr<GenomeIndex> new_index(kslam_ctx *c, uint64_t n_entries) {
   c->index.reset();
   for (auto *l : c->lanes) l->c->index.reset();
-  coverage_release(c);   // (include/kslam_coverage.h) the table was laid out for the old index's entries
-  variants_release(c);   // (include/kslam_variants.h) the keys hold the old index's base positions
-  depth_release(c);      // (include/kslam_depth.h) likewise, and the spare position per entry besides
-  kreport_release(c);    // (include/kslam_kreport.h) the annotations, and the tree with them, belong to the old index's entries
-  taxreads_release(c);   // (include/kslam_taxreads.h) likewise
-  genes_release(c);      // (include/kslam_genes.h) likewise: the gene columns belong to the old index's entries
-  alignqc_release(c);    // (include/kslam_alignqc.h) its counts are of alignments to the old index's entries
+  release_index_bound_reports(c);
   auto ix = std::make_shared<GenomeIndex>();
   ix->n_entries = n_entries;
   ix->h_goff.assign(n_entries + 1, 0);

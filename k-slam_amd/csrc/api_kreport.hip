@@ -14,20 +14,14 @@ KreportTable table_of(const kslam_ctx *owner) {
   return KreportTable{v.direct.as<unsigned long long>(), v.keys.as<uint32_t>(), v.nodes.as<uint32_t>(), v.n_nodes};
 }
 
-void need_on(const kslam_ctx *c) {
-  if (!c->kr.on.load(std::memory_order_acquire)) throw StatusError{KSLAM_ERR_STATE, "the report is switched off: call kslam_set_kreport first"};
-}
+const char *const REPORT_IS = "the Kraken-style report is";
+const char *const SWITCHED_OFF = "the report is switched off: call kslam_set_kreport first";
 
 void zero_state(kslam_ctx *c) {
   kslam_ctx::Kreport &v = c->kr;
   HIPCHK(hipMemsetAsync(v.direct.p, 0, (v.n_nodes + 1) * sizeof(uint64_t), c->stream));
   HIPCHK(stream_wait(c->stream));
   v.n_items = 0;
-}
-
-// every lane's counts are in memory before anybody reads or zeroes the state
-void wait_for_lanes(kslam_ctx *c) {
-  for (auto *l : c->lanes) HIPCHK(hipStreamSynchronize(l->c->stream));
 }
 
 // n device ids into owner's state with W on stream s; under owner->kr.mu.  The refusal comes before anything is written.
@@ -91,7 +85,7 @@ extern "C" {
 
 kslam_status kslam_set_kreport(kslam_ctx *c, int on) {
   return guarded(c, [&] {
-    if (c->in_multi) throw StatusError{KSLAM_ERR_UNSUPPORTED, "the Kraken-style report is not available on the contexts of a kslam_multi"};
+    if (refused_in_multi(c, REPORT_IS)) throw StatusError{KSLAM_ERR_UNSUPPORTED, c->err};
     if (!on) {
       if (c->kr.on.load(std::memory_order_acquire)) wait_for_lanes(c);
       kreport_release(c);
@@ -121,16 +115,12 @@ kslam_status kslam_set_kreport(kslam_ctx *c, int on) {
   });
 }
 
-kslam_status kslam_get_kreport(kslam_ctx *c, int *on) {
-  if (!c || !on) return KSLAM_ERR_ARG;
-  *on = c->kr.on.load(std::memory_order_acquire) ? 1 : 0;
-  return KSLAM_OK;
-}
+kslam_status kslam_get_kreport(kslam_ctx *c, int *on) { return get_switch(c, &kslam_ctx::kr, on); }
 
 kslam_status kslam_kreport_reset(kslam_ctx *c) {
   return guarded(c, [&] {
     std::lock_guard<std::mutex> lk(c->kr.mu);
-    need_on(c);
+    need_on(c->kr.on, SWITCHED_OFF);
     wait_for_lanes(c);
     zero_state(c);
   });
@@ -141,7 +131,7 @@ kslam_status kslam_kreport_add(kslam_ctx *c, const uint32_t *tax_ids, uint64_t n
     if (n && !tax_ids) throw StatusError{KSLAM_ERR_ARG, "null argument"};
     kslam_ctx::Kreport &v = c->kr;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->kr.on, SWITCHED_OFF);
     if (!n) {
       c->krw.ms = 0;
       return;
@@ -155,15 +145,10 @@ kslam_status kslam_kreport_add(kslam_ctx *c, const uint32_t *tax_ids, uint64_t n
 }
 
 kslam_status kslam_kreport_take(kslam_ctx *c, kslam_kreport_row **rows, uint64_t *n_rows, kslam_kreport_stats *stats) {
-  if (rows) *rows = nullptr;
-  if (n_rows) *n_rows = 0;
-  if (stats) memset(stats, 0, sizeof *stats);
-  kslam_kreport_row *h = nullptr;
-  const kslam_status st = guarded(c, [&] {
-    if (!rows || !n_rows || !stats) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+  return take_rows(c, rows, n_rows, stats, [&](kslam_kreport_row *&h) {
     kslam_ctx::Kreport &v = c->kr;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->kr.on, SWITCHED_OFF);
     if (!c->annot.up || c->annot.n_nodes != v.n_nodes) throw StatusError{KSLAM_ERR_STATE, "the report's state was laid out for another taxonomy tree"};
     wait_for_lanes(c);
     hipStream_t s = c->stream;
@@ -184,14 +169,6 @@ kslam_status kslam_kreport_take(kslam_ctx *c, kslam_kreport_row **rows, uint64_t
     stats->n_rows = n;
     *n_rows = n;
   });
-  if (st != KSLAM_OK) {
-    if (h) pinned_put(c, h);
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (n_rows) *n_rows = 0;
-    return st;
-  }
-  *rows = h;
-  return KSLAM_OK;
 }
 
 kslam_status kslam_kreport_kernel_ms(kslam_ctx *c, double *add_ms, double *take_ms) {
@@ -203,7 +180,7 @@ kslam_status kslam_kreport_kernel_ms(kslam_ctx *c, double *add_ms, double *take_
 
 kslam_status kslam_stream_set_kreport(kslam_ctx *c, int fd) {
   if (!c) return KSLAM_ERR_ARG;
-  if (c->in_multi) { c->err = "the Kraken-style report is not available on the contexts of a kslam_multi"; return KSLAM_ERR_UNSUPPORTED; }
+  if (refused_in_multi(c, REPORT_IS)) return KSLAM_ERR_UNSUPPORTED;
   c->kr.stream_fd = fd >= 0 ? fd : -1;
   return KSLAM_OK;
 }

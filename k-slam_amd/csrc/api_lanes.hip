@@ -245,25 +245,25 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
         });
       }
     }
+    // The reports fed by the batch's final alignment pairs: a report that is switched on sees the batch when everything before
+    // went well and this lane holds the final pairs.  (The report looks at its switch again under its own lock.)
+    auto feed = [&](const std::atomic<bool> &on, auto &&pass) {
+      if (on.load(std::memory_order_acquire) && st == KSLAM_OK && primary->pairing.stages && !pseudo_left && c->have_pairs) st = guarded(c, pass);
+    };
     // (kslam_set_coverage) the batch's final alignment pairs into the owner's coverage table: bit and counter atomics on this
     // lane's stream, outside the compute token like the split above.  A batch whose pseudo-assembly is left to the host goes
     // in through kslam_coverage_add after the host stage.
-    if (primary->cov.on.load(std::memory_order_acquire) && st == KSLAM_OK && primary->pairing.stages && !pseudo_left && c->have_pairs)
-      st = guarded(c, [&] { coverage_mark_resident(primary, c); });
+    feed(primary->cov.on, [&] { coverage_mark_resident(primary, c); });
     // (kslam_set_variants) the batch's mismatch events and covered intervals into the owner's state, on this lane's stream and
     // outside the compute token as well; the batches left to the host go in through kslam_variants_add after the host stage
-    if (primary->var.on.load(std::memory_order_acquire) && st == KSLAM_OK && primary->pairing.stages && !pseudo_left && c->have_pairs)
-      st = guarded(c, [&] { variants_emit_resident(primary, c); });
+    feed(primary->var.on, [&] { variants_emit_resident(primary, c); });
     // (kslam_set_depth) the batch's M runs as interval boundaries into the owner's state, likewise
-    if (primary->dep.on.load(std::memory_order_acquire) && st == KSLAM_OK && primary->pairing.stages && !pseudo_left && c->have_pairs)
-      st = guarded(c, [&] { depth_emit_resident(primary, c); });
+    feed(primary->dep.on, [&] { depth_emit_resident(primary, c); });
     // (kslam_set_genes) the batch's final alignment pairs into the owner's per-gene counters, likewise
-    if (primary->gen.on.load(std::memory_order_acquire) && st == KSLAM_OK && primary->pairing.stages && !pseudo_left && c->have_pairs)
-      st = guarded(c, [&] { genes_count_resident(primary, c); });
+    feed(primary->gen.on, [&] { genes_count_resident(primary, c); });
     // (kslam_set_align_qc) the batch's contributing records and live pairs into the owner's per-cycle tables, likewise; the batches
     // left to the host go in through kslam_align_qc_add after the host stage
-    if (primary->aq.on.load(std::memory_order_acquire) && st == KSLAM_OK && primary->pairing.stages && !pseudo_left && c->have_pairs)
-      st = guarded(c, [&] { alignqc_count_resident(primary, c, job->single); });
+    feed(primary->aq.on, [&] { alignqc_count_resident(primary, c, job->single); });
     t3 = now();
     // with the SAM records written on the device the host has no use for the rows, the CIGAR pool, the per-row details and
     // the MD text (0.7 GB per batch of configs[1]): they stay where they are, only their counts travel

@@ -12,14 +12,8 @@ ReadQcTable table_of(const kslam_ctx *owner) {
   return ReadQcTable{v.words.as<unsigned long long>(), v.n_words, v.C};
 }
 
-void need_on(const kslam_ctx *c) {
-  if (!c->rq.on.load(std::memory_order_acquire)) throw StatusError{KSLAM_ERR_STATE, "the read QC report is switched off: call kslam_set_read_qc first"};
-}
-
-// every lane's adds are in memory before anybody reads or zeroes the tables
-void wait_for_lanes(kslam_ctx *c) {
-  for (auto *l : c->lanes) HIPCHK(hipStreamSynchronize(l->c->stream));
-}
+const char *const REPORT_IS = "the read QC report is";
+const char *const SWITCHED_OFF = "the read QC report is switched off: call kslam_set_read_qc first";
 
 void zero_state(kslam_ctx *c) {
   readqc_zero_device(table_of(c), c->stream);
@@ -62,7 +56,7 @@ extern "C" {
 
 kslam_status kslam_set_read_qc(kslam_ctx *c, int on, uint32_t max_cycles) {
   return guarded(c, [&] {
-    if (c->in_multi) throw StatusError{KSLAM_ERR_UNSUPPORTED, "the read QC report is not available on the contexts of a kslam_multi"};
+    if (refused_in_multi(c, REPORT_IS)) throw StatusError{KSLAM_ERR_UNSUPPORTED, c->err};
     if (!on) {
       if (c->rq.on.load(std::memory_order_acquire)) wait_for_lanes(c);
       readqc_release(c);
@@ -93,18 +87,12 @@ kslam_status kslam_set_read_qc(kslam_ctx *c, int on, uint32_t max_cycles) {
   });
 }
 
-kslam_status kslam_get_read_qc(kslam_ctx *c, int *on, uint32_t *max_cycles) {
-  if (!c || !on || !max_cycles) return KSLAM_ERR_ARG;
-  std::lock_guard<std::mutex> lk(c->rq.mu);
-  *on = c->rq.on.load(std::memory_order_acquire) ? 1 : 0;
-  *max_cycles = *on ? c->rq.C : 0;
-  return KSLAM_OK;
-}
+kslam_status kslam_get_read_qc(kslam_ctx *c, int *on, uint32_t *max_cycles) { return get_switch(c, &kslam_ctx::rq, on, max_cycles); }
 
 kslam_status kslam_read_qc_reset(kslam_ctx *c) {
   return guarded(c, [&] {
     std::lock_guard<std::mutex> lk(c->rq.mu);
-    need_on(c);
+    need_on(c->rq.on, SWITCHED_OFF);
     wait_for_lanes(c);
     zero_state(c);
   });
@@ -116,7 +104,7 @@ kslam_status kslam_read_qc_add(kslam_ctx *c, const char *bases, const uint64_t *
     if (paired && (n_reads & 1)) throw StatusError{KSLAM_ERR_ARG, "a paired batch holds an even number of reads"};
     kslam_ctx::ReadQc &v = c->rq;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->rq.on, SWITCHED_OFF);
     // nothing is launched for offsets that do not hold together
     uint64_t max_len = 0;
     for (uint64_t i = 0; i < n_reads; i++) {
@@ -150,7 +138,7 @@ kslam_status kslam_read_qc_take(kslam_ctx *c, kslam_read_qc_tables *tables) {
     if (!tables) throw StatusError{KSLAM_ERR_ARG, "null argument"};
     kslam_ctx::ReadQc &v = c->rq;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->rq.on, SWITCHED_OFF);
     wait_for_lanes(c);
     hipStream_t s = c->stream;
     const uint64_t nw = v.n_words;
@@ -199,7 +187,7 @@ kslam_status kslam_read_qc_kernel_ms(kslam_ctx *c, double *count_ms, uint64_t *b
 
 kslam_status kslam_stream_set_read_qc(kslam_ctx *c, int fd, uint32_t max_cycles) {
   if (!c) return KSLAM_ERR_ARG;
-  if (c->in_multi) { c->err = "the read QC report is not available on the contexts of a kslam_multi"; return KSLAM_ERR_UNSUPPORTED; }
+  if (refused_in_multi(c, REPORT_IS)) return KSLAM_ERR_UNSUPPORTED;
   if (max_cycles > KSLAM_READ_QC_MAX_CYCLES) { c->err = "max_cycles must be 0 (= 512) or 1 .. 65536"; return KSLAM_ERR_ARG; }
   c->rq.stream_fd = fd >= 0 ? fd : -1;
   c->rq.stream_cycles = max_cycles;

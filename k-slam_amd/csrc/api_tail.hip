@@ -440,9 +440,7 @@ kslam_status kslam_set_sam_annotations(kslam_ctx *c, const kslam_index_view *iv,
     if (!iv->locus_tag_off || !iv->taxonomy_id) throw StatusError{KSLAM_ERR_ARG, "index view needs locus tags and taxonomy ids"};
     if (iv->n_genes && (!iv->gene_first || !iv->gene_start || !iv->gene_stop || !iv->gene_name_off || !iv->protein_id_off || !iv->product_off))
       throw StatusError{KSLAM_ERR_ARG, "index view has n_genes > 0 but no gene columns"};
-    kreport_release(c);   // (include/kslam_kreport.h) the counters were laid out for the old tree's nodes
-    taxreads_release(c);  // (include/kslam_taxreads.h) the mask was laid out for them too
-    genes_release(c);     // (include/kslam_genes.h) the lookup index was built from the old gene columns
+    release_tree_bound_reports(c);
     for (auto &b : c->annot_bufs) b.release();
     c->annot_bufs.clear();
     c->annot_bufs.reserve(24);

@@ -9,14 +9,8 @@ namespace {
 
 constexpr uint64_t VAR_MAX_KEYS = 0xFFFFFFFFull;   // the radix sort's limit
 
-void need_on(const kslam_ctx *c) {
-  if (!c->var.on.load(std::memory_order_acquire)) throw StatusError{KSLAM_ERR_STATE, "the variants are switched off: call kslam_set_variants first"};
-}
-
-// every lane's appends are in memory before anybody sorts or empties the arrays
-void wait_for_lanes(kslam_ctx *c) {
-  for (auto *l : c->lanes) HIPCHK(hipStreamSynchronize(l->c->stream));
-}
+const char *const REPORT_IS = "the variants are";
+const char *const SWITCHED_OFF = "the variants are switched off: call kslam_set_variants first";
 
 void empty_state(kslam_ctx::Variants &v) {
   v.n_ev = v.n_iv = v.n_records = v.n_skipped = 0;
@@ -51,10 +45,10 @@ void variants_release(kslam_ctx *c) {
   std::lock_guard<std::mutex> lk(v.mu);
   v.on.store(false, std::memory_order_release);
   VariantTakeWork &T = v.tw;
-  for (DevBuf *b : {&v.events, &v.begins, &v.ends, &v.up_ov, &v.up_groups, &v.up_pairs, &v.up_pool, &v.up_rbases, &v.up_roff, &T.alt, &T.head, &T.run,
-                    &T.starts, &T.fwd, &T.rev, &T.depth, &T.keep, &T.out_at, &T.rows, &T.scan_tmp, &T.totals, &T.sortws.hist, &T.sortws.status,
-                    &T.sortws.tickets, &T.sortws.digits})
+  for (DevBuf *b : {&v.events, &v.begins, &v.ends, &T.alt, &T.head, &T.run, &T.starts, &T.fwd, &T.rev, &T.depth, &T.keep, &T.out_at, &T.rows, &T.scan_tmp,
+                    &T.totals, &T.sortws.hist, &T.sortws.status, &T.sortws.tickets, &T.sortws.digits})
     b->release();
+  v.up.release_all();
   empty_state(v);
   v.n_entries = v.total_bases = 0;
 }
@@ -62,10 +56,7 @@ void variants_release(kslam_ctx *c) {
 void variants_emit_resident(kslam_ctx *owner, kslam_ctx *lane) {
   const GenomeIndex &ix = lane->need_index();
   if (ix.n_entries != owner->var.n_entries) throw StatusError{KSLAM_ERR_STATE, "the variants were laid out for another index"};
-  const VariantInputs in{lane->res_ov.as<kslam_overlap>(), lane->n_res, lane->pres.d_groups, lane->pres.n_read_pairs, lane->pres.d_pairs,
-                         lane->pres.n_pairs, lane->res_cig.as<uint32_t>(), lane->n_cig, lane->r_bases.as<uint8_t>(), lane->r_off.as<uint64_t>(),
-                         lane->n_reads, ix.g_bases.as<uint8_t>(), ix.g_off.as<uint64_t>(), ix.n_entries};
-  emit(owner, in, lane->varw, lane->stream, false);
+  emit(owner, resident_inputs(lane, ix, true), lane->varw, lane->stream, false);
 }
 
 }  // namespace kslam_api
@@ -74,7 +65,7 @@ extern "C" {
 
 kslam_status kslam_set_variants(kslam_ctx *c, int on) {
   return guarded(c, [&] {
-    if (c->in_multi) throw StatusError{KSLAM_ERR_UNSUPPORTED, "the variants are not available on the contexts of a kslam_multi"};
+    if (refused_in_multi(c, REPORT_IS)) throw StatusError{KSLAM_ERR_UNSUPPORTED, c->err};
     if (!on) {
       if (c->var.on.load(std::memory_order_acquire)) wait_for_lanes(c);
       variants_release(c);
@@ -97,16 +88,12 @@ kslam_status kslam_set_variants(kslam_ctx *c, int on) {
   });
 }
 
-kslam_status kslam_get_variants(kslam_ctx *c, int *on) {
-  if (!c || !on) return KSLAM_ERR_ARG;
-  *on = c->var.on.load(std::memory_order_acquire) ? 1 : 0;
-  return KSLAM_OK;
-}
+kslam_status kslam_get_variants(kslam_ctx *c, int *on) { return get_switch(c, &kslam_ctx::var, on); }
 
 kslam_status kslam_variants_reset(kslam_ctx *c) {
   return guarded(c, [&] {
     std::lock_guard<std::mutex> lk(c->var.mu);
-    need_on(c);
+    need_on(c->var.on, SWITCHED_OFF);
     wait_for_lanes(c);
     empty_state(c->var);
   });
@@ -120,65 +107,26 @@ kslam_status kslam_variants_add(kslam_ctx *c, const kslam_overlap *overlaps, uin
       throw StatusError{KSLAM_ERR_ARG, "null argument"};
     kslam_ctx::Variants &v = c->var;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->var.on, SWITCHED_OFF);
     const GenomeIndex &ix = c->need_index();
-    // nothing is launched for arrays that do not hold together
-    if (n_overlaps >= (1ull << 32)) throw StatusError{KSLAM_ERR_ARG, "2^32 or more overlap records"};
-    for (uint64_t i = 0; i < n_reads; i++)
-      if (read_offsets[i + 1] < read_offsets[i]) throw StatusError{KSLAM_ERR_ARG, "the read offsets must ascend"};
     const uint64_t n_rbytes = n_reads ? read_offsets[n_reads] : 0;
     if (n_rbytes && !read_bases) throw StatusError{KSLAM_ERR_ARG, "null argument"};
-    uint64_t next = 0;
-    for (uint64_t g = 0; g < n_read_pairs; g++) {
-      const kslam_read_pair &rp = read_pairs[g];
-      if (rp.first > n_pairs || rp.count > n_pairs - rp.first)
-        throw StatusError{KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": first + count lies outside the pairs array"};
-      if (rp.first < next) throw StatusError{KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": the groups' slices must ascend and not overlap"};
-      next = rp.first + rp.count;
-      for (uint64_t k = rp.first; k < rp.first + rp.count; k++)
-        for (uint32_t idx : {pairs[k].r1, pairs[k].r2}) {
-          if (idx == KSLAM_NO_OVERLAP) continue;
-          if (idx >= n_overlaps)
-            throw StatusError{KSLAM_ERR_ARG, "alignment pair " + std::to_string(k) + " refers to overlap record " + std::to_string(idx) + " of " + std::to_string(n_overlaps)};
-          const kslam_overlap &o = overlaps[idx];
-          if (o.cigar_off > n_cigar || o.cigar_len > n_cigar - o.cigar_off)
-            throw StatusError{KSLAM_ERR_ARG, "overlap record " + std::to_string(idx) + ": its CIGAR slice lies outside the pool"};
-          if (o.read >= n_reads)
-            throw StatusError{KSLAM_ERR_ARG, "overlap record " + std::to_string(idx) + " refers to read " + std::to_string(o.read) + " of " + std::to_string(n_reads)};
-        }
-    }
+    // nothing is launched for arrays that do not hold together
+    const kslam_batch::Arrays batch{overlaps, n_overlaps, n_cigar, read_offsets, n_reads, read_pairs, n_read_pairs, pairs, n_pairs};
+    const std::string fault = kslam_batch::check(batch, kslam_batch::Level::records);
+    if (!fault.empty()) throw StatusError{KSLAM_ERR_ARG, fault};
     hipStream_t s = c->stream;
-    v.up_ov.ensure((n_overlaps + 1) * sizeof(kslam_overlap));
-    v.up_groups.ensure((n_read_pairs + 1) * sizeof(kslam_read_pair));
-    v.up_pairs.ensure((n_pairs + 1) * sizeof(kslam_paired_overlap));
-    v.up_pool.ensure((n_cigar + 1) * sizeof(uint32_t));
-    v.up_rbases.ensure(n_rbytes + 64);
-    v.up_roff.ensure((n_reads + 1) * sizeof(uint64_t));
-    if (n_overlaps) HIPCHK(hipMemcpyAsync(v.up_ov.p, overlaps, n_overlaps * sizeof(kslam_overlap), hipMemcpyHostToDevice, s));
-    if (n_read_pairs) HIPCHK(hipMemcpyAsync(v.up_groups.p, read_pairs, n_read_pairs * sizeof(kslam_read_pair), hipMemcpyHostToDevice, s));
-    if (n_pairs) HIPCHK(hipMemcpyAsync(v.up_pairs.p, pairs, n_pairs * sizeof(kslam_paired_overlap), hipMemcpyHostToDevice, s));
-    if (n_cigar) HIPCHK(hipMemcpyAsync(v.up_pool.p, cigar_pool, n_cigar * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    if (n_rbytes) HIPCHK(hipMemcpyAsync(v.up_rbases.p, read_bases, n_rbytes, hipMemcpyHostToDevice, s));
-    if (n_reads) HIPCHK(hipMemcpyAsync(v.up_roff.p, read_offsets, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    HIPCHK(stream_wait(s));   // (pageable sources: the caller's arrays are free again)
-    const VariantInputs in{v.up_ov.as<kslam_overlap>(), n_overlaps, v.up_groups.as<kslam_read_pair>(), n_read_pairs,
-                           v.up_pairs.as<kslam_paired_overlap>(), n_pairs, v.up_pool.as<uint32_t>(), n_cigar, v.up_rbases.as<uint8_t>(),
-                           v.up_roff.as<uint64_t>(), n_reads, ix.g_bases.as<uint8_t>(), ix.g_off.as<uint64_t>(), ix.n_entries};
+    const VariantInputs in = v.up.upload(batch, kslam_batch::Level::records, cigar_pool, BatchUpload::bases, read_bases, nullptr, &ix, s);
     emit(c, in, c->varw, s, true);
   });
 }
 
 kslam_status kslam_variants_take(kslam_ctx *c, uint32_t min_alt, uint32_t min_depth, kslam_variant_row **rows, uint64_t *n_rows,
                                  kslam_variant_stats *stats) {
-  if (rows) *rows = nullptr;
-  if (n_rows) *n_rows = 0;
-  if (stats) memset(stats, 0, sizeof *stats);
-  kslam_variant_row *h = nullptr;
-  const kslam_status st = guarded(c, [&] {
-    if (!rows || !n_rows || !stats) throw StatusError{KSLAM_ERR_ARG, "null argument"};
+  return take_rows(c, rows, n_rows, stats, [&](kslam_variant_row *&h) {
     kslam_ctx::Variants &v = c->var;
     std::lock_guard<std::mutex> lk(v.mu);
-    need_on(c);
+    need_on(c->var.on, SWITCHED_OFF);
     const GenomeIndex &ix = c->need_index();
     wait_for_lanes(c);
     hipStream_t s = c->stream;
@@ -201,14 +149,6 @@ kslam_status kslam_variants_take(kslam_ctx *c, uint32_t min_alt, uint32_t min_de
     stats->n_events = v.n_ev;
     stats->n_sites = n_sites;
   });
-  if (st != KSLAM_OK) {
-    if (h) pinned_put(c, h);
-    if (n_rows) *n_rows = 0;
-    if (stats) memset(stats, 0, sizeof *stats);
-    return st;
-  }
-  *rows = h;
-  return KSLAM_OK;
 }
 
 kslam_status kslam_variants_kernel_ms(kslam_ctx *c, double *emit_ms, double *take_ms) {
@@ -220,7 +160,7 @@ kslam_status kslam_variants_kernel_ms(kslam_ctx *c, double *emit_ms, double *tak
 
 kslam_status kslam_stream_set_variants(kslam_ctx *c, int fd, uint32_t min_alt, uint32_t min_depth) {
   if (!c) return KSLAM_ERR_ARG;
-  if (c->in_multi) { c->err = "the variants are not available on the contexts of a kslam_multi"; return KSLAM_ERR_UNSUPPORTED; }
+  if (refused_in_multi(c, REPORT_IS)) return KSLAM_ERR_UNSUPPORTED;
   c->var.stream_fd = fd >= 0 ? fd : -1;
   c->var.stream_min_alt = min_alt;
   c->var.stream_min_depth = min_depth;

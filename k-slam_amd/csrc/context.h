@@ -7,6 +7,10 @@
 //   api_tail.hip   the widened path on the device: qualities, per-row details, pairing / screens / pseudo-assembly, SAM text
 //   api_lanes.hip  the pipelined entry (worker lanes, FASTQ text in)
 //   api_multi.hip  several devices: shard export / merge, kslam_multi_*
+//   api_readsplit.hip  the reads split by outcome, cut out of the uploaded text
+//   api_taxreads.hip   the reads of chosen taxa, likewise
+//   api_coverage.hip, api_variants.hip, api_depth.hip, api_kreport.hip, api_genes.hip, api_readqc.hip, api_alignqc.hip
+//                  the opt-in reports the lanes feed, one file each; what they share is in api_reports.h (included below)
 #pragma once
 #include <sys/mman.h>
 
@@ -31,6 +35,7 @@
 #include "../../include/kslam_alignqc.h"
 #include "../host/workers.hpp"
 #include "../host/inflate.hpp"
+#include "../host/batch_check.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -59,6 +64,55 @@ struct GenomeIndex {
   uint32_t bucket_bits = 8;
   DevBuf g_filter;            // membership filter over the genome k-mers (filter.hip); filter_bits = 0: off
   uint32_t filter_bits = 0;
+};
+
+// One batch's arrays on the device, as a report's kslam_*_add got them from the host.  Every report state holds one of its own:
+// the adds of different reports hold different mutexes and may run at the same time.
+struct BatchUpload {
+  enum Columns { no_columns, bases, bases_and_quality };   // of the reads, besides their offsets
+  DevBuf ov, groups, pairs, pool, rbases, rqual, roff;
+
+  // Uploads what `level` checked (kslam_batch::check) -- the groups and the pairs; from Level::pairs the overlap records; from
+  // Level::records the CIGAR pool and the read offsets -- and the reads' columns asked for, on s, and waits: the caller's arrays
+  // are free again.  What the report does not take stays null in the batch handed back; the entries' bases come with the reads'.
+  VariantInputs upload(const kslam_batch::Arrays &a, kslam_batch::Level level, const uint32_t *cigar_pool, Columns columns, const char *read_bases,
+                       const char *read_quality, const GenomeIndex *ix, hipStream_t s) {
+    const bool with_ov = level >= kslam_batch::Level::pairs, with_records = level >= kslam_batch::Level::records;
+    const uint64_t n_rbytes = columns != no_columns && a.n_reads ? a.read_offsets[a.n_reads] : 0;
+    if (with_ov) ov.ensure((a.n_overlaps + 1) * sizeof(kslam_overlap));
+    groups.ensure((a.n_read_pairs + 1) * sizeof(kslam_read_pair));
+    pairs.ensure((a.n_pairs + 1) * sizeof(kslam_paired_overlap));
+    if (with_records) pool.ensure((a.n_cigar + 1) * sizeof(uint32_t));
+    if (columns != no_columns) rbases.ensure(n_rbytes + 64);
+    if (columns == bases_and_quality) rqual.ensure(n_rbytes + 64);
+    if (with_records) roff.ensure((a.n_reads + 1) * sizeof(uint64_t));
+    if (with_ov && a.n_overlaps) HIPCHK(hipMemcpyAsync(ov.p, a.overlaps, a.n_overlaps * sizeof(kslam_overlap), hipMemcpyHostToDevice, s));
+    if (a.n_read_pairs) HIPCHK(hipMemcpyAsync(groups.p, a.read_pairs, a.n_read_pairs * sizeof(kslam_read_pair), hipMemcpyHostToDevice, s));
+    if (a.n_pairs) HIPCHK(hipMemcpyAsync(pairs.p, a.pairs, a.n_pairs * sizeof(kslam_paired_overlap), hipMemcpyHostToDevice, s));
+    if (with_records && a.n_cigar) HIPCHK(hipMemcpyAsync(pool.p, cigar_pool, a.n_cigar * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if (n_rbytes) HIPCHK(hipMemcpyAsync(rbases.p, read_bases, n_rbytes, hipMemcpyHostToDevice, s));
+    if (n_rbytes && columns == bases_and_quality && read_quality) HIPCHK(hipMemcpyAsync(rqual.p, read_quality, n_rbytes, hipMemcpyHostToDevice, s));
+    if (with_records && a.n_reads) HIPCHK(hipMemcpyAsync(roff.p, a.read_offsets, (a.n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    HIPCHK(stream_wait(s));   // (pageable sources)
+    const bool with_bases = columns != no_columns;
+    return VariantInputs{with_ov ? ov.as<kslam_overlap>() : nullptr,
+                         with_ov ? a.n_overlaps : 0,
+                         groups.as<kslam_read_pair>(),
+                         a.n_read_pairs,
+                         pairs.as<kslam_paired_overlap>(),
+                         a.n_pairs,
+                         with_records ? pool.as<uint32_t>() : nullptr,
+                         with_records ? a.n_cigar : 0,
+                         with_bases ? rbases.as<uint8_t>() : nullptr,
+                         with_records ? roff.as<uint64_t>() : nullptr,
+                         with_records ? a.n_reads : 0,
+                         ix && with_bases ? ix->g_bases.as<uint8_t>() : nullptr,
+                         ix ? ix->g_off.as<uint64_t>() : nullptr,
+                         ix ? ix->n_entries : 0};
+  }
+  void release_all() {
+    for (DevBuf *b : {&ov, &groups, &pairs, &pool, &rbases, &rqual, &roff}) b->release();
+  }
 };
 
 struct kslam_ctx {
@@ -152,7 +206,7 @@ struct kslam_ctx {
     std::atomic<bool> on{false};
     uint64_t n_entries = 0, n_words = 0;
     DevBuf bitmap, rows, skipped, word_off;
-    DevBuf up_ov, up_groups, up_pairs;   // kslam_coverage_add's uploads
+    BatchUpload up;               // kslam_coverage_add's
     hipEvent_t ev_count[2]{};
     double count_ms = 0;
     int stream_fd = -1;           // kslam_stream_set_coverage
@@ -168,7 +222,7 @@ struct kslam_ctx {
     uint64_t n_ev = 0, n_iv = 0, n_records = 0, n_skipped = 0;
     bool sorted = false;          // nothing was appended since kslam_variants_take sorted the arrays
     VariantTakeWork tw;
-    DevBuf up_ov, up_groups, up_pairs, up_pool, up_rbases, up_roff;   // kslam_variants_add's uploads
+    BatchUpload up;               // kslam_variants_add's
     hipEvent_t ev_take[2]{};
     double take_ms = 0;
     int stream_fd = -1;           // kslam_stream_set_variants
@@ -186,7 +240,7 @@ struct kslam_ctx {
     uint64_t n_pend = 0, n_keys = 0, n_records = 0, n_skipped = 0, n_iv = 0;
     uint64_t compact_at = 0;      // kslam_depth_set_compact_at; 0: the default
     DepthWork tw;
-    DevBuf up_ov, up_groups, up_pairs, up_pool, up_roff;   // kslam_depth_add's uploads
+    BatchUpload up;               // kslam_depth_add's
     hipEvent_t ev[4]{};           // around a compaction, around a take
     double compact_ms = 0, take_ms = 0;
     int stream_fd = -1;           // kslam_stream_set_depth
@@ -217,7 +271,7 @@ struct kslam_ctx {
     uint64_t n_entries = 0, n_genes = 0;   // of the annotations the state was laid out for
     DevBuf order, sstart, sstop, runmax;   // the lookup index: 16 bytes per gene
     DevBuf rows, stats;           // u64 [4 * n_genes], u64 [4]
-    DevBuf up_groups, up_pairs;   // kslam_genes_add's uploads
+    BatchUpload up;               // kslam_genes_add's
     DevBuf lk_in, lk_out;         // kslam_genes_lookup's triples and answers
     GenesTakeWork tw;
     hipEvent_t ev_take[2]{};
@@ -248,7 +302,7 @@ struct kslam_ctx {
     uint64_t n_entries = 0;       // of the index the switch was set for
     DevBuf words;                 // u64 [KSLAM_ALIGN_QC_WORDS(C)]
     bool paired = false;          // a batch counted since the last reset was paired
-    DevBuf up_ov, up_groups, up_pairs, up_pool, up_rbases, up_rqual, up_roff;   // kslam_align_qc_add's uploads
+    BatchUpload up;               // kslam_align_qc_add's
     int stream_fd = -1;           // kslam_stream_set_align_qc
     uint32_t stream_cycles = 0;
     std::mutex mu;                // add / take / reset / the lanes' launches / the switch: one at a time
@@ -439,60 +493,8 @@ void split_resident(kslam_ctx *c, bool single, const kslam_read_pair *d_groups, 
                     kslam_reads_out *out);
 void free_reads_out(kslam_ctx *c, kslam_reads_out *out);
 
-// ---- api_coverage.hip
-// frees the coverage state of c and switches it off (kslam_set_coverage(c, 0), kslam_set_index)
-void coverage_release(kslam_ctx *c);
-// the batch `lane` has just finished (lane->pres over lane->res_ov) into owner's table, on lane's stream
-void coverage_mark_resident(kslam_ctx *owner, kslam_ctx *lane);
-
-// ---- api_variants.hip
-// frees the variants state of c and switches it off (kslam_set_variants(c, 0), kslam_set_index)
-void variants_release(kslam_ctx *c);
-// the batch `lane` has just finished (lane->pres over lane->res_ov, lane->res_cig and lane's reads) into owner's state, on lane's stream
-void variants_emit_resident(kslam_ctx *owner, kslam_ctx *lane);
-
-// ---- api_depth.hip
-// frees the depth state of c and switches it off (kslam_set_depth(c, 0), kslam_set_index)
-void depth_release(kslam_ctx *c);
-// the batch `lane` has just finished into owner's state, on lane's stream
-void depth_emit_resident(kslam_ctx *owner, kslam_ctx *lane);
-
-// ---- api_kreport.hip
-// frees the report state of c and switches it off (kslam_set_kreport(c, 0), kslam_set_sam_annotations, kslam_set_index)
-void kreport_release(kslam_ctx *c);
-// the n taxonomy ids `lane` has just computed (lane->samw.tax_ids) into owner's state, on lane's stream
-void kreport_count_resident(kslam_ctx *owner, kslam_ctx *lane, uint64_t n);
-// the id -> node table of c's device tree (c->annot), uploaded into the two buffers; waits for c's stream
-void id_node_table(kslam_ctx *c, DevBuf &d_keys, DevBuf &d_nodes);
-
-// ---- api_genes.hip
-// frees the gene table of c and switches it off (kslam_set_genes(c, 0), kslam_set_sam_annotations, kslam_set_index)
-void genes_release(kslam_ctx *c);
-// the batch `lane` has just finished (lane->pres) into owner's table, on lane's stream
-void genes_count_resident(kslam_ctx *owner, kslam_ctx *lane);
-
-// ---- api_readqc.hip
-// frees the read QC state of c and switches it off (kslam_set_read_qc(c, 0, 0))
-void readqc_release(kslam_ctx *c);
-// the batch resident on `lane` (lane->r_bases, r_qual, r_off: the columns cut out of the text it uploaded) into owner's tables,
-// on lane's stream; does not wait
-void readqc_count_resident(kslam_ctx *owner, kslam_ctx *lane, bool single);
-
-// ---- api_alignqc.hip
-// frees the alignment QC state of c and switches it off (kslam_set_align_qc(c, 0, 0), kslam_set_index)
-void alignqc_release(kslam_ctx *c);
-// the batch `lane` has just finished (lane->pres over lane->res_ov, lane->res_cig, lane's reads and, when it holds one, its quality
-// column) into owner's tables, on lane's stream
-void alignqc_count_resident(kslam_ctx *owner, kslam_ctx *lane, bool single);
-
-// ---- api_taxreads.hip
-// frees the selection of c and switches it off (kslam_set_taxon_reads(c, NULL, 0, 0), kslam_set_sam_annotations, kslam_set_index)
-void taxreads_release(kslam_ctx *c);
-// the batch resident on c (indexed by fastq_index_device: c->fqw) selected by owner's S: d_ids[g] is the taxonomy id of
-// d_groups[g].  Blocks from c's page-locked pool: out->data[0] / [1] the selected R1 / R2.
-void taxreads_resident(kslam_ctx *owner, kslam_ctx *c, bool single, const kslam_read_pair *d_groups, const uint32_t *d_ids, uint64_t n_groups,
-                       bool bgzf, int deflate, kslam_reads_out *out);
-
 }  // namespace kslam_api
+
+#include "api_reports.h"
 
 using namespace kslam_api;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/kslam_alignqc.h"
+#include "batch_check.hpp"
 #include "workers.hpp"
 
 namespace {
@@ -226,31 +227,14 @@ extern "C" kslam_status kslam_tail_align_qc(const char *entry_bases, const uint6
         (n_read_pairs && !read_pairs) || (n_pairs && !pairs))
       fail(KSLAM_ERR_ARG, "null argument");
     const uint64_t C = resolve_cycles(max_cycles);
-    if (n_overlaps >= (1ull << 32)) fail(KSLAM_ERR_ARG, "2^32 or more overlap records");
     if (paired && (n_reads & 1)) fail(KSLAM_ERR_ARG, "a paired batch holds an even number of reads");
-    for (uint64_t i = 0; i < n_reads; i++)
-      if (read_offsets[i + 1] < read_offsets[i]) fail(KSLAM_ERR_ARG, "the read offsets must ascend");
     if (n_reads && read_offsets[n_reads] && !read_bases) fail(KSLAM_ERR_ARG, "null argument");
     if (n_entries && entry_offsets[n_entries] && !entry_bases) fail(KSLAM_ERR_ARG, "null argument");
     // ---- the contributing set, and the pairs ----
-    std::vector<uint8_t> named(n_overlaps, 0);
-    uint64_t next = 0;
-    for (uint64_t g = 0; g < n_read_pairs; g++) {
-      const kslam_read_pair &rp = read_pairs[g];
-      if (rp.first > n_pairs || rp.count > n_pairs - rp.first) fail(KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": first + count lies outside the pairs array");
-      if (rp.first < next) fail(KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": the groups' slices must ascend and not overlap");
-      next = rp.first + rp.count;
-      for (uint64_t k = rp.first; k < rp.first + rp.count; k++)
-        for (uint32_t idx : {pairs[k].r1, pairs[k].r2}) {
-          if (idx == KSLAM_NO_OVERLAP) continue;
-          if (idx >= n_overlaps) fail(KSLAM_ERR_ARG, "alignment pair " + std::to_string(k) + " refers to overlap record " + std::to_string(idx) + " of " + std::to_string(n_overlaps));
-          const kslam_overlap &o = overlaps[idx];
-          if (o.cigar_off > n_cigar || o.cigar_len > n_cigar - o.cigar_off)
-            fail(KSLAM_ERR_ARG, "overlap record " + std::to_string(idx) + ": its CIGAR slice lies outside the pool");
-          if (o.read >= n_reads) fail(KSLAM_ERR_ARG, "overlap record " + std::to_string(idx) + " refers to read " + std::to_string(o.read) + " of " + std::to_string(n_reads));
-          named[idx] = 1;
-        }
-    }
+    std::vector<uint8_t> named(n_overlaps < (1ull << 32) ? n_overlaps : 0, 0);   // (2^32 or more: refused before anything is named)
+    const std::string fault = kslam_batch::check({overlaps, n_overlaps, n_cigar, read_offsets, n_reads, read_pairs, n_read_pairs, pairs, n_pairs},
+                                                 kslam_batch::Level::records, nullptr, [&](uint32_t idx) { named[idx] = 1; });
+    if (!fault.empty()) fail(KSLAM_ERR_ARG, fault);
     const uint64_t nw = KSLAM_ALIGN_QC_WORDS(C);
     block = (uint64_t *)calloc(nw, sizeof(uint64_t));
     if (!block) fail(KSLAM_ERR_OOM, "out of host memory");

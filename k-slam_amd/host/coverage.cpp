@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/kslam_coverage.h"
+#include "batch_check.hpp"
 #include "workers.hpp"
 
 namespace {
@@ -20,14 +21,8 @@ extern "C" kslam_status kslam_tail_coverage(const uint64_t *entry_lengths, uint6
   return guarded([&] {
     if ((n_entries && (!entry_lengths || !rows)) || !n_skipped || (n_overlaps && !overlaps) || (n_read_pairs && !read_pairs) || (n_pairs && !pairs))
       fail(KSLAM_ERR_ARG, "null argument");
-    if (n_overlaps >= (1ull << 32)) fail(KSLAM_ERR_ARG, "2^32 or more overlap records");
-    uint64_t next = 0;
-    for (uint64_t g = 0; g < n_read_pairs; g++) {
-      const kslam_read_pair &rp = read_pairs[g];
-      if (rp.first > n_pairs || rp.count > n_pairs - rp.first) fail(KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": first + count lies outside the pairs array");
-      if (rp.first < next) fail(KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": the groups' slices must ascend and not overlap");
-      next = rp.first + rp.count;
-    }
+    const std::string fault = kslam_batch::check({overlaps, n_overlaps, 0, nullptr, 0, read_pairs, n_read_pairs, pairs, n_pairs}, kslam_batch::Level::pairs);
+    if (!fault.empty()) fail(KSLAM_ERR_ARG, fault);
     *n_skipped = 0;
     if (n_entries) memset(rows, 0, sizeof(kslam_entry_coverage) * n_entries);
     std::vector<uint64_t> base(n_entries + 1, 0);
@@ -42,7 +37,6 @@ extern "C" kslam_status kslam_tail_coverage(const uint64_t *entry_lengths, uint6
         if (p.entry < n_entries) rows[p.entry].alignments++;
         for (uint32_t idx : {p.r1, p.r2}) {
           if (idx == KSLAM_NO_OVERLAP) continue;
-          if (idx >= n_overlaps) fail(KSLAM_ERR_ARG, "alignment pair " + std::to_string(k) + " refers to overlap record " + std::to_string(idx) + " of " + std::to_string(n_overlaps));
           const kslam_overlap &o = overlaps[idx];
           if (o.entry >= n_entries || o.ref_begin < 0 || o.ref_end < o.ref_begin || (uint64_t)o.ref_end >= entry_lengths[o.entry]) {
             ++*n_skipped;

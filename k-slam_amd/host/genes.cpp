@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/kslam_genes.h"
+#include "batch_check.hpp"
 #include "workers.hpp"
 
 namespace {
@@ -55,13 +56,8 @@ extern "C" kslam_status kslam_tail_genes(const kslam_index_view *index, const ks
   return guarded([&] {
     if (!rows_out || !n_rows || !stats || (n_read_pairs && !read_pairs) || (n_pairs && !pairs)) fail(KSLAM_ERR_ARG, "null argument");
     need_gene_columns(index);
-    uint64_t next = 0;
-    for (uint64_t g = 0; g < n_read_pairs; g++) {
-      const kslam_read_pair &rp = read_pairs[g];
-      if (rp.first > n_pairs || rp.count > n_pairs - rp.first) fail(KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": first + count lies outside the pairs array");
-      if (rp.first < next) fail(KSLAM_ERR_ARG, "read pair " + std::to_string(g) + ": the groups' slices must ascend and not overlap");
-      next = rp.first + rp.count;
-    }
+    const std::string fault = kslam_batch::check({nullptr, 0, 0, nullptr, 0, read_pairs, n_read_pairs, pairs, n_pairs}, kslam_batch::Level::groups);
+    if (!fault.empty()) fail(KSLAM_ERR_ARG, fault);
     const uint64_t G = index->n_genes;
     std::vector<kslam_gene_row> table(G);
     for (uint64_t g = 0; g < G; g++) table[g] = kslam_gene_row{g, 0, 0, 0};

@@ -180,42 +180,28 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       if (tr_ids.empty()) fail(KSLAM_ERR_STATE, "kslam_stream_set_taxon_reads without chosen ids: call kslam_set_taxon_reads first");
       if (kslam_get_reads_out_bgzf(ctx, &tr_bgzf) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
     }
+    // a report for this call: switched on -- `set` tells wind_down to switch it off again -- and emptied of what an earlier call left
+    auto started = [&](kslam_status switched_on, bool &set, kslam_status (*reset)(kslam_ctx *)) {
+      if (switched_on != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
+      set = true;
+      if (reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+    };
     // the per-entry coverage table (include/kslam_coverage.h): the lanes mark what they finish; the report follows the last batch
     if (kslam_stream_get_coverage(ctx, &cov_fd) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
-    if (cov_fd >= 0) {
-      if (kslam_set_coverage(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
-      coverage_set = true;
-      if (kslam_coverage_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
-    }
+    if (cov_fd >= 0) started(kslam_set_coverage(ctx, 1), coverage_set, kslam_coverage_reset);
     // the SNV table (include/kslam_variants.h): the lanes pile up what they finish; the VCF file follows the last batch
     if (kslam_stream_get_variants(ctx, &var_fd, &var_min_alt, &var_min_depth) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
-    if (var_fd >= 0) {
-      if (kslam_set_variants(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
-      variants_set = true;
-      if (kslam_variants_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
-    }
+    if (var_fd >= 0) started(kslam_set_variants(ctx, 1), variants_set, kslam_variants_reset);
     // the depth track (include/kslam_depth.h): the lanes add what they finish; the bedGraph file follows the last batch
     if (kslam_stream_get_depth(ctx, &dep_fd, &dep_min) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
-    if (dep_fd >= 0) {
-      if (kslam_set_depth(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
-      depth_set = true;
-      if (kslam_depth_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
-    }
+    if (dep_fd >= 0) started(kslam_set_depth(ctx, 1), depth_set, kslam_depth_reset);
     // the read QC report (include/kslam_readqc.h): the lanes count the columns of every batch they take in; the file follows the
     // last batch.  It needs neither the tree nor the pairing.
     if (kslam_stream_get_read_qc(ctx, &qc_fd, &qc_cycles) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
-    if (qc_fd >= 0) {
-      if (kslam_set_read_qc(ctx, 1, qc_cycles) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
-      read_qc_set = true;
-      if (kslam_read_qc_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
-    }
+    if (qc_fd >= 0) started(kslam_set_read_qc(ctx, 1, qc_cycles), read_qc_set, kslam_read_qc_reset);
     // the alignment QC report (include/kslam_alignqc.h): the lanes count what they finish; the file follows the last batch
     if (kslam_stream_get_align_qc(ctx, &aq_fd, &aq_cycles) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
-    if (aq_fd >= 0) {
-      if (kslam_set_align_qc(ctx, 1, aq_cycles) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
-      align_qc_set = true;
-      if (kslam_align_qc_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
-    }
+    if (aq_fd >= 0) started(kslam_set_align_qc(ctx, 1, aq_cycles), align_qc_set, kslam_align_qc_reset);
     const bool host_split = getenv("KSLAM_HOST_SAM_TEXT") && getenv("KSLAM_HOST_SAM_TEXT")[0] == '1';   // (A/B: the host twin for every batch)
     // the SAM records and the per-read lines written on the GPU (include/kslam_samtext.h); KSLAM_HOST_SAM_TEXT=1 keeps the
     // host formatter for everything (A/B, and the route of a batch the device hands back without text)
@@ -229,24 +215,14 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     // the Kraken-style report (include/kslam_kreport.h): the lanes count the taxonomy ids they make, the batches classified here
     // go in through kslam_kreport_add; the file follows the last batch.  Behind the annotations: they bring the device tree.
     if (kslam_stream_get_kreport(ctx, &kr_fd) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
-    if (kr_fd >= 0) {
-      if (!taxdb) fail(KSLAM_ERR_STATE, "the Kraken-style report needs a taxonomy tree (not available with --just-align)");
-    }
+    if (kr_fd >= 0 && !taxdb) fail(KSLAM_ERR_STATE, "the Kraken-style report needs a taxonomy tree (not available with --just-align)");
     if (kslam_stream_get_genes(ctx, &gen_fd) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
     if ((kr_fd >= 0 || taxreads_on || gen_fd >= 0) && !device_text && kslam_set_sam_annotations(ctx, index, taxdb) != KSLAM_OK)
       fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
     // the per-gene abundance table (include/kslam_genes.h): the lanes count what they finish; the file follows the last batch.
     // Behind the annotations: they bring the gene columns, and setting them drops the table.
-    if (gen_fd >= 0) {
-      if (kslam_set_genes(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
-      genes_set = true;
-      if (kslam_genes_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
-    }
-    if (kr_fd >= 0) {
-      if (kslam_set_kreport(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
-      kreport_set = true;
-      if (kslam_kreport_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
-    }
+    if (gen_fd >= 0) started(kslam_set_genes(ctx, 1), genes_set, kslam_genes_reset);
+    if (kr_fd >= 0) started(kslam_set_kreport(ctx, 1), kreport_set, kslam_kreport_reset);
     // the chosen taxa again, on the tree that is on the device now: the lanes select the batches whose ids they make, the others
     // go through kslam_tail_taxon_reads behind the classification on this side
     if (taxreads_on) {
@@ -385,6 +361,26 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       std::string tax_error;
       std::thread tax_thread;
       const uint32_t *host_ids = nullptr;   // the batch's taxonomy ids when kslam_tail_classify made them here
+      // the batch's pseudo-assembly was left to this stage: no lane fed it to the reports that count final alignment pairs
+      const bool pseudo_left = P->tail.pseudo_assembly && !(res.pair_stats.stages_done & KSLAM_TAIL_PSEUDO_ASM);
+      // The lanes keep the read bases and qualities on the device, so whoever needs them for a batch handled here has the batch's
+      // window parsed into columns (host/fastq.cpp, the same records the device indexed): once per batch, on first use.
+      kslam_reads_columns cols;
+      memset(&cols, 0, sizeof cols);
+      struct Release { kslam_reads_columns *c; ~Release() { kslam_reads_free(c); } } release{&cols};
+      bool parsed = false;
+      auto columns = [&]() -> const kslam_reads_columns & {
+        if (parsed) return cols;
+        uint64_t c1 = 0, c2 = 0;
+        const kslam_status q = paired ? kslam_fastq_parse_pair(r1 + win.p1, win.e1 - win.p1, r2 + win.p2, win.e2 - win.p2, 0, 1,
+                                                               P->tail.threads, &cols, &c1, &c2)
+                                      : kslam_fastq_parse(r1 + win.p1, win.e1 - win.p1, 0, 1, P->tail.threads, &cols, &c1);
+        if (q != KSLAM_OK) fail(q, kslam_tail_last_error());
+        if (cols.n_reads != res.n_reads || memcmp(cols.bases_off, res.reads_bases_off, sizeof(uint64_t) * (res.n_reads + 1)) != 0)
+          fail(KSLAM_ERR_INTERNAL, "the host's parse of a batch differs from the device's index");
+        parsed = true;
+        return cols;
+      };
       auto tax_part = [&] {
           tax_status = guarded([&] {
             const double t1 = now_ms();
@@ -419,9 +415,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
           if (tax_status != KSLAM_OK) tax_error = g_err;
       };
       kslam_status s = guarded([&] {
-        const bool on_gpu = (res.pair_stats.stages_done & KSLAM_TAIL_PSEUDO_ASM) != 0;
-        if (P->tail.pseudo_assembly && !on_gpu) st.batches_pseudo_on_host++;
-        const kslam_tail_params *tp = (on_gpu || !P->tail.pseudo_assembly) ? &host_write : &host_all;
+        if (pseudo_left) st.batches_pseudo_on_host++;
+        const kslam_tail_params *tp = pseudo_left ? &host_all : &host_write;
         kslam_tail_stats ps;
         memset(&ps, 0, sizeof ps);
         const double t0 = now_ms();
@@ -448,69 +443,42 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
         s = guarded([&] { write_reads_out(res, ro, win); });
         if (s != KSLAM_OK) err = g_err;
       }
-      // coverage: the lane marked the batch unless its pseudo-assembly was left to this stage, which has just finished its read pairs
-      if (s == KSLAM_OK && coverage_set && P->tail.pseudo_assembly && !(res.pair_stats.stages_done & KSLAM_TAIL_PSEUDO_ASM)) {
-        s = guarded([&] {
-          if (kslam_coverage_add(ctx, res.overlaps, res.n_overlaps, res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK)
-            fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
-        });
+      // The reports that count final alignment pairs: a lane fed them the batch unless its pseudo-assembly was left to this stage,
+      // which has just finished its read pairs.
+      auto add = [&](bool report_set, auto &&call) {
+        if (s != KSLAM_OK || !report_set || !pseudo_left) return;
+        s = guarded(call);
         if (s != KSLAM_OK) err = g_err;
-      }
-      // the per-gene table likewise
-      if (s == KSLAM_OK && genes_set && P->tail.pseudo_assembly && !(res.pair_stats.stages_done & KSLAM_TAIL_PSEUDO_ASM)) {
-        s = guarded([&] {
-          if (kslam_genes_add(ctx, res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
-        });
-        if (s != KSLAM_OK) err = g_err;
-      }
-      // the variants likewise; the lanes keep the read bases on the device, so the batch's window is parsed into columns first
-      if (s == KSLAM_OK && variants_set && P->tail.pseudo_assembly && !(res.pair_stats.stages_done & KSLAM_TAIL_PSEUDO_ASM)) {
-        s = guarded([&] {
-          kslam_reads_columns cols;
-          memset(&cols, 0, sizeof cols);
-          struct Release { kslam_reads_columns *c; ~Release() { kslam_reads_free(c); } } release{&cols};
-          uint64_t c1 = 0, c2 = 0;
-          const kslam_status q = paired ? kslam_fastq_parse_pair(r1 + win.p1, win.e1 - win.p1, r2 + win.p2, win.e2 - win.p2, 0, 1,
-                                                                 P->tail.threads, &cols, &c1, &c2)
-                                        : kslam_fastq_parse(r1 + win.p1, win.e1 - win.p1, 0, 1, P->tail.threads, &cols, &c1);
-          if (q != KSLAM_OK) fail(q, kslam_tail_last_error());
-          if (cols.n_reads != res.n_reads || memcmp(cols.bases_off, res.reads_bases_off, sizeof(uint64_t) * (res.n_reads + 1)) != 0)
-            fail(KSLAM_ERR_INTERNAL, "the host's parse of a batch differs from the device's index");
-          if (kslam_variants_add(ctx, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, cols.bases, cols.bases_off, cols.n_reads,
-                                 res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK)
-            fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
-        });
-        if (s != KSLAM_OK) err = g_err;
-      }
-      // the alignment QC report likewise, with the quality column of the same parse
-      if (s == KSLAM_OK && align_qc_set && P->tail.pseudo_assembly && !(res.pair_stats.stages_done & KSLAM_TAIL_PSEUDO_ASM)) {
-        s = guarded([&] {
-          kslam_reads_columns cols;
-          memset(&cols, 0, sizeof cols);
-          struct Release { kslam_reads_columns *c; ~Release() { kslam_reads_free(c); } } release{&cols};
-          uint64_t c1 = 0, c2 = 0;
-          const kslam_status q = paired ? kslam_fastq_parse_pair(r1 + win.p1, win.e1 - win.p1, r2 + win.p2, win.e2 - win.p2, 0, 1,
-                                                                 P->tail.threads, &cols, &c1, &c2)
-                                        : kslam_fastq_parse(r1 + win.p1, win.e1 - win.p1, 0, 1, P->tail.threads, &cols, &c1);
-          if (q != KSLAM_OK) fail(q, kslam_tail_last_error());
-          if (cols.n_reads != res.n_reads || memcmp(cols.bases_off, res.reads_bases_off, sizeof(uint64_t) * (res.n_reads + 1)) != 0 ||
-              memcmp(cols.quality_off, cols.bases_off, sizeof(uint64_t) * (res.n_reads + 1)) != 0)
-            fail(KSLAM_ERR_INTERNAL, "the host's parse of a batch differs from the device's index");
-          if (kslam_align_qc_add(ctx, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, cols.bases, cols.bases_off, cols.n_reads,
-                                 res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs, cols.quality, paired ? 1 : 0) != KSLAM_OK)
-            fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
-        });
-        if (s != KSLAM_OK) err = g_err;
-      }
-      // the depth track likewise; it needs the reads' lengths alone, which came back with the batch
-      if (s == KSLAM_OK && depth_set && P->tail.pseudo_assembly && !(res.pair_stats.stages_done & KSLAM_TAIL_PSEUDO_ASM)) {
-        s = guarded([&] {
-          if (kslam_depth_add(ctx, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, res.reads_bases_off, res.n_reads, res.read_pairs,
-                              res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK)
-            fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
-        });
-        if (s != KSLAM_OK) err = g_err;
-      }
+      };
+      add(coverage_set, [&] {
+        if (kslam_coverage_add(ctx, res.overlaps, res.n_overlaps, res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK)
+          fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      });
+      add(genes_set, [&] {
+        if (kslam_genes_add(ctx, res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      });
+      // the variants need the read bases
+      add(variants_set, [&] {
+        const kslam_reads_columns &rc = columns();
+        if (kslam_variants_add(ctx, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, rc.bases, rc.bases_off, rc.n_reads, res.read_pairs,
+                               res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK)
+          fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      });
+      // the alignment QC report the quality column as well
+      add(align_qc_set, [&] {
+        const kslam_reads_columns &rc = columns();
+        if (memcmp(rc.quality_off, rc.bases_off, sizeof(uint64_t) * (res.n_reads + 1)) != 0)
+          fail(KSLAM_ERR_INTERNAL, "the host's parse of a batch differs from the device's index");
+        if (kslam_align_qc_add(ctx, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, rc.bases, rc.bases_off, rc.n_reads, res.read_pairs,
+                               res.n_read_pairs, res.pairs, res.n_pairs, rc.quality, paired ? 1 : 0) != KSLAM_OK)
+          fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      });
+      // the depth track the reads' lengths alone, which came back with the batch
+      add(depth_set, [&] {
+        if (kslam_depth_add(ctx, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, res.reads_bases_off, res.n_reads, res.read_pairs,
+                            res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK)
+          fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      });
       if (s == KSLAM_OK && writer && (res.text_flags & KSLAM_TEXT_SAM)) {
         s = guarded([&] {   // written on the GPU: the page-locked block joins the writer's queue as it is and goes back to the
                             // context's pool once it is in the file
@@ -545,24 +513,14 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
             return 0;
           };
           // BAM: the same stage writing records (kslam_tail_finish_write_rows_bam), gathered and compressed the same way
-          // SEQ / QUAL (include/kslam_samseq.h): the twin with the switch on, either record kind.  The lanes keep the bases
-          // and qualities on the device, so a batch that is formatted here has its window parsed into columns first
-          // (host/fastq.cpp, the same records the device indexed); the rows then read what the device's rows read.
-          kslam_reads_columns cols;
-          memset(&cols, 0, sizeof cols);
-          struct Release { kslam_reads_columns *c; ~Release() { kslam_reads_free(c); } } release{&cols};
+          // SEQ / QUAL (include/kslam_samseq.h): the twin with the switch on, either record kind, over the batch's parsed
+          // columns; the rows then read what the device's rows read.
           kslam_reads_view seq_reads = reads;
           if (seq) {
-            uint64_t c1 = 0, c2 = 0;
-            const kslam_status q = paired ? kslam_fastq_parse_pair(r1 + win.p1, win.e1 - win.p1, r2 + win.p2, win.e2 - win.p2, 0, 1,
-                                                                   P->tail.threads, &cols, &c1, &c2)
-                                          : kslam_fastq_parse(r1 + win.p1, win.e1 - win.p1, 0, 1, P->tail.threads, &cols, &c1);
-            if (q != KSLAM_OK) fail(q, kslam_tail_last_error());
-            if (cols.n_reads != res.n_reads || memcmp(cols.bases_off, res.reads_bases_off, sizeof(uint64_t) * (res.n_reads + 1)) != 0)
-              fail(KSLAM_ERR_INTERNAL, "the host's parse of a batch differs from the device's index");
-            seq_reads.bases = cols.bases;
-            seq_reads.quality = cols.quality;
-            seq_reads.quality_off = cols.quality_off;
+            const kslam_reads_columns &rc = columns();
+            seq_reads.bases = rc.bases;
+            seq_reads.quality = rc.quality;
+            seq_reads.quality_off = rc.quality_off;
           }
           const kslam_write_fn wr = bgzf ? append : kslam_write_queued;
           void *const wu = bgzf ? (void *)&text : (void *)writer;
