@@ -1,0 +1,207 @@
+"""ctypes plumbing for include/kslam_consensus.h: the consensus sequence of every entry the reads align to, called on the GPU
+from the pile-up of each batch (one row and one sequence per reported entry), its host twin, the FASTA writer and a parser for
+the file."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import tail as _T
+from .variants import _arrays
+
+# every symbol include/kslam_consensus.h declares
+EXPORTS = ["kslam_consensus_add", "kslam_consensus_kernel_ms", "kslam_consensus_reset", "kslam_consensus_set_slice", "kslam_consensus_take",
+           "kslam_consensus_write", "kslam_get_consensus", "kslam_set_consensus", "kslam_stream_get_consensus", "kslam_stream_set_consensus",
+           "kslam_tail_consensus"]
+ROW_DT = np.dtype([("entry", "<u4"), ("pad", "<u4"), ("seq_off", "<u8"), ("seq_len", "<u8"), ("entry_len", "<u8"), ("covered", "<u8"),
+                   ("substitutions", "<u8"), ("deleted", "<u8"), ("insertions", "<u8"), ("inserted_bases", "<u8"), ("ambiguous", "<u8")])
+STAT_NAMES = ("n_records", "n_skipped", "n_intervals", "n_del_intervals", "n_events", "n_insertions", "n_ins_unanchored",
+              "n_ins_unrepresentable", "n_entries_touched", "n_entries_reported")
+FILL_N, FILL_REF = 0, 1
+MAX_INS = 32
+DEFAULT_SLICE = 1 << 26
+TAG = "kslam_consensus"
+HEADER_FIELDS = ("entry_length", "covered", "substitutions", "deletions", "insertions", "ambiguous")
+_ready = False
+
+
+class Stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in STAT_NAMES]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in STAT_NAMES}
+
+
+class Params(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("call_permille", C.c_uint32), ("fill", C.c_uint32), ("min_covered", C.c_uint32)]
+
+
+def _fill(fill):
+    if isinstance(fill, str):
+        if fill.upper() not in ("N", "REF"):
+            raise ValueError("fill is 'N' or 'REF'")
+        return FILL_REF if fill.upper() == "REF" else FILL_N
+    return int(fill)
+
+
+def params(min_depth=1, call_permille=500, fill=FILL_N, min_covered=1):
+    return Params(int(min_depth), int(call_permille), _fill(fill), int(min_covered))
+
+
+def lib():
+    global _ready
+    L = _T.lib()
+    if not _ready:
+        vp, u64, P = C.c_void_p, C.c_uint64, C.POINTER
+        batch = [vp, u64, vp, u64, vp, vp, u64, vp, u64, vp, u64]   # overlaps, pool, read bases + offsets, read pairs, pairs
+        L.kslam_set_consensus.argtypes = [vp, C.c_int]
+        L.kslam_get_consensus.argtypes = [vp, P(C.c_int)]
+        L.kslam_consensus_reset.argtypes = [vp]
+        L.kslam_consensus_add.argtypes = [vp] + batch
+        L.kslam_consensus_set_slice.argtypes = [vp, u64]
+        L.kslam_consensus_take.argtypes = [vp, P(Params), P(vp), P(u64), P(vp), P(Stats)]
+        L.kslam_consensus_kernel_ms.argtypes = [vp, P(C.c_double), P(C.c_double)]
+        L.kslam_tail_consensus.argtypes = [vp, vp, u64] + batch + [P(Params), P(vp), P(u64), P(vp), P(Stats)]
+        L.kslam_consensus_write.argtypes = [P(_T.IndexView), vp, u64, vp, C.c_int]
+        L.kslam_stream_set_consensus.argtypes = [vp, C.c_int, P(Params)]
+        L.kslam_stream_get_consensus.argtypes = [vp, P(C.c_int), P(Params)]
+        L.kslam_free_pinned.argtypes = [vp, vp]
+        L.kslam_free_pinned.restype = None
+        L.kslam_free.argtypes = [vp]
+        L.kslam_free.restype = None
+        _ready = True
+    return L
+
+
+def set_consensus(ctx, on=True):
+    """kslam_set_consensus: needs an index, ctx.set_pairing and a context with report_cigar; off frees the state"""
+    ctx._chk(lib().kslam_set_consensus(ctx._h, int(on)))
+
+
+def get_consensus(ctx):
+    on = C.c_int()
+    ctx._chk(lib().kslam_get_consensus(ctx._h, C.byref(on)))
+    return bool(on.value)
+
+
+def reset(ctx):
+    ctx._chk(lib().kslam_consensus_reset(ctx._h))
+
+
+def add(ctx, overlaps, cigar_pool, read_bases, read_offsets, read_pairs, pairs):
+    """kslam_consensus_add: one batch's arrays from the host (as kslam_amd.variants.add)"""
+    keep, args = _arrays(overlaps, cigar_pool, read_bases, read_offsets, read_pairs, pairs)
+    ctx._chk(lib().kslam_consensus_add(ctx._h, *args))
+
+
+def set_slice(ctx, slice_positions=0):
+    """kslam_consensus_set_slice: the positions one pass of take calls (0: the default)"""
+    ctx._chk(lib().kslam_consensus_set_slice(ctx._h, int(slice_positions)))
+
+
+def _result(rows, n, seq, st):
+    out = np.frombuffer(C.string_at(rows.value, n.value * ROW_DT.itemsize), dtype=ROW_DT).copy() if n.value else np.zeros(0, dtype=ROW_DT)
+    total = int(out["seq_off"][-1] + out["seq_len"][-1]) if n.value else 0
+    # (ctypes.string_at takes its size as a C int: the sequences of a large database are longer)
+    return out, (bytes((C.c_char * total).from_address(seq.value)) if total else b""), st.as_dict()
+
+
+def take(ctx, min_depth=1, call_permille=500, fill=FILL_N, min_covered=1):
+    """kslam_consensus_take -> (rows: ROW_DT array, seq: bytes, stats: dict); row i's sequence is seq[seq_off : seq_off + seq_len]"""
+    L = lib()
+    p = params(min_depth, call_permille, fill, min_covered)
+    rows, n, seq, st = C.c_void_p(), C.c_uint64(), C.c_void_p(), Stats()
+    ctx._chk(L.kslam_consensus_take(ctx._h, C.byref(p), C.byref(rows), C.byref(n), C.byref(seq), C.byref(st)))
+    out = _result(rows, n, seq, st)
+    L.kslam_free_pinned(ctx._h, rows)
+    L.kslam_free_pinned(ctx._h, seq)
+    return out
+
+
+def kernel_ms(ctx):
+    """(device ms of the last kslam_consensus_add's emit passes, of the last take)"""
+    a, b = C.c_double(), C.c_double()
+    ctx._chk(lib().kslam_consensus_kernel_ms(ctx._h, C.byref(a), C.byref(b)))
+    return float(a.value), float(b.value)
+
+
+def tail_consensus(entry_bases, entry_offsets, overlaps, cigar_pool, read_bases, read_offsets, read_pairs, pairs, min_depth=1, call_permille=500,
+                   fill=FILL_N, min_covered=1):
+    """kslam_tail_consensus (host twin) -> (rows, seq, stats)"""
+    L = lib()
+    gb = np.ascontiguousarray(np.frombuffer(entry_bases, dtype=np.uint8) if isinstance(entry_bases, (bytes, bytearray)) else entry_bases, dtype=np.uint8)
+    go = np.ascontiguousarray(entry_offsets, dtype=np.uint64)
+    keep, args = _arrays(overlaps, cigar_pool, read_bases, read_offsets, read_pairs, pairs)
+    p = params(min_depth, call_permille, fill, min_covered)
+    rows, n, seq, st = C.c_void_p(), C.c_uint64(), C.c_void_p(), Stats()
+    n_entries = max(len(go) - 1, 0)
+    _T._chk(L.kslam_tail_consensus(gb.ctypes.data if len(gb) else None, go.ctypes.data if n_entries else None, n_entries, *args, C.byref(p),
+                                   C.byref(rows), C.byref(n), C.byref(seq), C.byref(st)))
+    out = _result(rows, n, seq, st)
+    L.kslam_free(rows)
+    L.kslam_free(seq)
+    return out
+
+
+def sequences(rows, seq):
+    """the rows' sequences as a list of bytes"""
+    return [bytes(seq[int(r["seq_off"]):int(r["seq_off"] + r["seq_len"])]) for r in rows]
+
+
+def write(index, rows, seq, fd):
+    """kslam_consensus_write: index a kslam_amd.tail index view (e.g. kslam_amd.db.Database), rows a ROW_DT array, seq their bytes"""
+    r = np.ascontiguousarray(rows, dtype=ROW_DT)
+    s = bytes(seq)
+    _T._chk(lib().kslam_consensus_write(C.byref(index.view), r.ctypes.data if len(r) else None, len(r), C.c_char_p(s) if s else None, int(fd)))
+
+
+def report_bytes(index, rows, seq):
+    """the FASTA file as bytes (through a pipe-free temporary descriptor)"""
+    fd = os.memfd_create("kslam_consensus")
+    try:
+        write(index, rows, seq, fd)
+        os.lseek(fd, 0, os.SEEK_SET)
+        out = b""
+        while True:
+            piece = os.read(fd, 1 << 20)
+            if not piece:
+                return out
+            out += piece
+    finally:
+        os.close(fd)
+
+
+def stream_set_consensus(ctx, fd, min_depth=1, call_permille=500, fill=FILL_N, min_covered=1):
+    """kslam_stream_set_consensus: the descriptor the NEXT kslam_stream_classify on ctx writes its FASTA file to (-1: none)"""
+    p = params(min_depth, call_permille, fill, min_covered)
+    ctx._chk(lib().kslam_stream_set_consensus(ctx._h, int(fd) if fd is not None else -1, C.byref(p)))
+
+
+def parse(text):
+    """the file -> list of (locus: str, fields: dict of the header's integers by HEADER_FIELDS, sequence: str); raises ValueError
+    for a header of another kind, a sequence line before a header, an empty line or a line longer than 60"""
+    if isinstance(text, bytes):
+        text = text.decode()
+    lines = text.split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    out = []
+    for line in lines:
+        if line.startswith(">"):
+            f = line[1:].split(" ")
+            if len(f) != 2 + len(HEADER_FIELDS) or f[1] != TAG or not f[0]:
+                raise ValueError("not a consensus header: " + line)
+            fields = {}
+            for name, kv in zip(HEADER_FIELDS, f[2:]):
+                k, _, v = kv.partition("=")
+                if k != name or not v.isdigit():
+                    raise ValueError("not a consensus header: " + line)
+                fields[name] = int(v)
+            out.append([f[0], fields, []])
+        else:
+            if not out:
+                raise ValueError("a sequence line before the first header")
+            if not line or len(line) > 60 or (out[-1][2] and len(out[-1][2][-1]) != 60):
+                raise ValueError("a sequence line of another kind")
+            out[-1][2].append(line)
+    return [(locus, fields, "".join(parts)) for locus, fields, parts in out]

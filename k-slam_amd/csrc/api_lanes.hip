@@ -257,6 +257,8 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
     // (kslam_set_variants) the batch's mismatch events and covered intervals into the owner's state, on this lane's stream and
     // outside the compute token as well; the batches left to the host go in through kslam_variants_add after the host stage
     feed(primary->var.on, [&] { variants_emit_resident(primary, c); });
+    // (kslam_set_consensus) the batch's intervals, events and insertions into the owner's state, likewise
+    feed(primary->cns.on, [&] { consensus_emit_resident(primary, c); });
     // (kslam_set_depth) the batch's M runs as interval boundaries into the owner's state, likewise
     feed(primary->dep.on, [&] { depth_emit_resident(primary, c); });
     // (kslam_set_genes) the batch's final alignment pairs into the owner's per-gene counters, likewise

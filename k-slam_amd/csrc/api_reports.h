@@ -1,5 +1,5 @@
 // api_reports.h -- what the opt-in reports behind the C ABI share (api_coverage.hip, api_variants.hip, api_depth.hip,
-// api_kreport.hip, api_genes.hip, api_readqc.hip, api_alignqc.hip; the reads of chosen taxa, api_taxreads.hip, are released with
+// api_kreport.hip, api_genes.hip, api_readqc.hip, api_alignqc.hip, api_consensus.hip; the reads of chosen taxa, api_taxreads.hip, are released with
 // them): their entry points for the lanes, the lists of what an index or a tree takes with it, and the shell of their ABI
 // functions.  Each file keeps what is its own: its table layout, its switch-on preconditions, its zeroing, its take.
 // Included from context.h, behind the context.
@@ -53,6 +53,12 @@ void alignqc_release(kslam_ctx *c);
 // column) into owner's tables, on lane's stream
 void alignqc_count_resident(kslam_ctx *owner, kslam_ctx *lane, bool single);
 
+// ---- api_consensus.hip
+// frees the consensus state of c and switches it off (kslam_set_consensus(c, 0), kslam_set_index)
+void consensus_release(kslam_ctx *c);
+// the batch `lane` has just finished (as variants_emit_resident sees it) into owner's state, on lane's stream
+void consensus_emit_resident(kslam_ctx *owner, kslam_ctx *lane);
+
 // ---- api_taxreads.hip
 // frees the selection of c and switches it off (kslam_set_taxon_reads(c, NULL, 0, 0), kslam_set_sam_annotations, kslam_set_index)
 void taxreads_release(kslam_ctx *c);
@@ -77,6 +83,7 @@ inline void release_index_bound_reports(kslam_ctx *c) {
   taxreads_release(c);   // (include/kslam_taxreads.h) likewise
   genes_release(c);      // (include/kslam_genes.h) likewise: the gene columns belong to the old index's entries
   alignqc_release(c);    // (include/kslam_alignqc.h) its counts are of alignments to the old index's entries
+  consensus_release(c);  // (include/kslam_consensus.h) the keys hold the old index's base positions
 }
 
 // ---- the batch a lane has just finished, as the reports' kernels see it ----

@@ -9,7 +9,8 @@
 //   api_multi.hip  several devices: shard export / merge, kslam_multi_*
 //   api_readsplit.hip  the reads split by outcome, cut out of the uploaded text
 //   api_taxreads.hip   the reads of chosen taxa, likewise
-//   api_coverage.hip, api_variants.hip, api_depth.hip, api_kreport.hip, api_genes.hip, api_readqc.hip, api_alignqc.hip
+//   api_coverage.hip, api_variants.hip, api_depth.hip, api_kreport.hip, api_genes.hip, api_readqc.hip, api_alignqc.hip,
+//   api_consensus.hip
 //                  the opt-in reports the lanes feed, one file each; what they share is in api_reports.h (included below)
 #pragma once
 #include <sys/mman.h>
@@ -18,6 +19,7 @@
 #include "samtext.h"
 #include "bgzf.h"
 #include "inflate.h"
+#include "consensus.h"
 #include "../../include/kslam_samtext.h"
 #include "../../include/kslam_bgzf.h"
 #include "../../include/kslam_inflate.h"
@@ -230,6 +232,24 @@ struct kslam_ctx {
     std::mutex mu;                // append / take / reset / the switch: one at a time
   } var;
   VariantEmitWork varw;           // this context's own emit passes (a lane's batches; on the primary: kslam_variants_add)
+
+  // ---- the consensus caller (consensus.hip, include/kslam_consensus.h) ----
+  struct Consensus {              // on the context the switch was set on; its lanes append to it (lane_main)
+    std::atomic<bool> on{false};
+    uint64_t n_entries = 0, total_bases = 0;
+    DevBuf ev, mb, me, db, de, ins;   // the keys, append-only between two resets; n[kind] of them are in use
+    uint64_t n[CNS_KINDS] = {0, 0, 0, 0}, n_records = 0, n_skipped = 0, n_unanchored = 0, n_unrepresentable = 0;
+    bool sorted = false;          // nothing was appended since kslam_consensus_take sorted the arrays
+    uint64_t slice = KSLAM_CONSENSUS_DEFAULT_SLICE;   // kslam_consensus_set_slice
+    ConsensusTakeWork tw;
+    BatchUpload up;               // kslam_consensus_add's
+    hipEvent_t ev_take[2]{};
+    double take_ms = 0;
+    int stream_fd = -1;           // kslam_stream_set_consensus
+    kslam_consensus_params stream_params{1, 500, KSLAM_CONSENSUS_FILL_N, 1};
+    std::mutex mu;                // append / take / reset / the switch: one at a time
+  } cns;
+  ConsensusEmitWork cnsw;         // this context's own emit passes (a lane's batches; on the primary: kslam_consensus_add)
 
   // ---- the depth track (depth.hip, include/kslam_depth.h) ----
   struct Depth {                  // on the context the switch was set on; its lanes append to it (lane_main)

@@ -33,6 +33,7 @@
 #include "../../include/kslam_readqc.h"
 #include "../../include/kslam_taxreads.h"
 #include "../../include/kslam_variants.h"
+#include "../../include/kslam_consensus.h"
 #include "../../include/kslam_depth.h"
 #include "workers.hpp"
 
@@ -83,6 +84,9 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
   int var_fd = -1;                   // kslam_stream_set_variants: where the VCF file goes
   uint32_t var_min_alt = 2, var_min_depth = 1;
   bool variants_set = false;
+  int cns_fd = -1;                   // kslam_stream_set_consensus: where the consensus FASTA goes
+  kslam_consensus_params cns_params{1, 500, KSLAM_CONSENSUS_FILL_N, 1};
+  bool consensus_set = false;
   int dep_fd = -1;                    // kslam_stream_set_depth: where the bedGraph file goes
   uint32_t dep_min = 1;
   bool depth_set = false;
@@ -126,6 +130,8 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     if (ctx) kslam_stream_set_genes(ctx, -1);
     if (variants_set) kslam_set_variants(ctx, 0);
     if (ctx) kslam_stream_set_variants(ctx, -1, 2, 1);
+    if (consensus_set) kslam_set_consensus(ctx, 0);
+    if (ctx) kslam_stream_set_consensus(ctx, -1, nullptr);
     if (depth_set) kslam_set_depth(ctx, 0);
     if (ctx) kslam_stream_set_depth(ctx, -1, 1);
     if (kreport_set) kslam_set_kreport(ctx, 0);
@@ -192,6 +198,9 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
     // the SNV table (include/kslam_variants.h): the lanes pile up what they finish; the VCF file follows the last batch
     if (kslam_stream_get_variants(ctx, &var_fd, &var_min_alt, &var_min_depth) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
     if (var_fd >= 0) started(kslam_set_variants(ctx, 1), variants_set, kslam_variants_reset);
+    // the consensus caller (include/kslam_consensus.h): the lanes pile up what they finish; the FASTA file follows the last batch
+    if (kslam_stream_get_consensus(ctx, &cns_fd, &cns_params) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    if (cns_fd >= 0) started(kslam_set_consensus(ctx, 1), consensus_set, kslam_consensus_reset);
     // the depth track (include/kslam_depth.h): the lanes add what they finish; the bedGraph file follows the last batch
     if (kslam_stream_get_depth(ctx, &dep_fd, &dep_min) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
     if (dep_fd >= 0) started(kslam_set_depth(ctx, 1), depth_set, kslam_depth_reset);
@@ -464,6 +473,13 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
                                res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK)
           fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
       });
+      // the consensus caller likewise
+      add(consensus_set, [&] {
+        const kslam_reads_columns &rc = columns();
+        if (kslam_consensus_add(ctx, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, rc.bases, rc.bases_off, rc.n_reads, res.read_pairs,
+                                res.n_read_pairs, res.pairs, res.n_pairs) != KSLAM_OK)
+          fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      });
       // the alignment QC report the quality column as well
       add(align_qc_set, [&] {
         const kslam_reads_columns &rc = columns();
@@ -681,6 +697,17 @@ extern "C" kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_
       if (kslam_variants_take(ctx, var_min_alt, var_min_depth, &rows, &n_rows, &vs) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
       const kslam_status w = kslam_variants_write(index, rows, n_rows, &vs, var_fd);
       kslam_free_pinned(ctx, rows);
+      if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
+    }
+    if (consensus_set) {
+      kslam_consensus_row *rows = nullptr;
+      uint64_t n_rows = 0;
+      char *seq = nullptr;
+      kslam_consensus_stats cs;
+      if (kslam_consensus_take(ctx, &cns_params, &rows, &n_rows, &seq, &cs) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      const kslam_status w = kslam_consensus_write(index, rows, n_rows, seq, cns_fd);
+      kslam_free_pinned(ctx, rows);
+      kslam_free_pinned(ctx, seq);
       if (w != KSLAM_OK) fail(w, kslam_tail_last_error());
     }
     if (read_qc_set) {

@@ -56,7 +56,7 @@ class StreamStats(C.Structure):
 
 def classify_stream_native(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_batch, params, taxdb=None, report=None,
                            sam_fd=-1, per_read_fd=-1, sam_header=None, max_pairs_total=0, depth=0, passes=1, host_threads=0, pool_threads=0,
-                           reads_out_fds=None, coverage_fd=-1, variants_fd=None, variants_min_alt=2, variants_min_depth=1, kreport_fd=-1,
+                           reads_out_fds=None, coverage_fd=-1, variants_fd=None, variants_min_alt=2, variants_min_depth=1, kreport_fd=-1, consensus_fd=None, consensus_params=None,
                            taxon_reads_fds=None, depth_fd=None, depth_min=1, read_qc_fd=-1, read_qc_max_cycles=0, genes_fd=-1,
                            align_qc_fd=-1, align_qc_max_cycles=0):
     """kslam_stream_classify: the same loop as classify_stream below, inside the library (no Python between the batches).
@@ -65,6 +65,8 @@ def classify_stream_native(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_bat
     coverage_fd: an open descriptor for the per-entry coverage report (kslam_amd.coverage; -1 = none).
     variants_fd: an open descriptor for the VCF file of the SNV table (kslam_amd.variants; None = none) with its two thresholds;
     the context needs report_cigar.
+    consensus_fd: an open descriptor for the consensus FASTA (kslam_amd.consensus; None = none) with consensus_params =
+    (min_depth, call_permille, fill, min_covered), None = (1, 500, N, 1); the context needs report_cigar.
     depth_fd: an open descriptor for the bedGraph file of the depth track (kslam_amd.depth; None = none) with its threshold
     depth_min; the context needs report_cigar.  (`depth` is the pipeline's depth, not this.)
     kreport_fd: an open descriptor for the Kraken-style report (kslam_amd.kreport; -1 = none); needs a taxdb.
@@ -89,6 +91,9 @@ def classify_stream_native(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_bat
     if coverage_fd >= 0:
         from . import coverage as CV
         CV.stream_set_coverage(ctx, coverage_fd)
+    if consensus_fd is not None and consensus_fd >= 0:
+        from . import consensus as CN
+        CN.stream_set_consensus(ctx, consensus_fd, *(consensus_params or (1, 500, 0, 1)))
     if variants_fd is not None and variants_fd >= 0:
         from . import variants as VR
         VR.stream_set_variants(ctx, variants_fd, variants_min_alt, variants_min_depth)

@@ -41,6 +41,7 @@
 #include "../include/kslam_samtext.h"
 #include "../include/kslam_taxreads.h"
 #include "../include/kslam_variants.h"
+#include "../include/kslam_consensus.h"
 #include "../include/kslam_depth.h"
 #include "../include/kslam_genes.h"
 #include "../include/kslam_alignqc.h"
@@ -79,6 +80,9 @@ struct Options {
   std::string db, out, sam, classified_out, unclassified_out, coverage_out, variants_out, kraken_report;
   uint32_t variants_min_alt = 2, variants_min_depth = 1;
   bool variants_min_alt_given = false, variants_min_depth_given = false;
+  std::string consensus_out;               // --consensus-out (include/kslam_consensus.h)
+  kslam_consensus_params consensus{1, 500, KSLAM_CONSENSUS_FILL_N, 1};
+  const char *consensus_dependent = nullptr;   // the first of --consensus-min-depth / -call-permille / -fill / -min-covered given
   std::string depth_out;                   // --depth-out (include/kslam_depth.h)
   std::string genes_out;                   // --genes-out (include/kslam_genes.h)
   uint32_t depth_min = 1;
@@ -161,6 +165,14 @@ void usage(FILE *o) {
         "                                        VCF 4.2 (sites only: DP, AO, SAF, SAR, AF); works with --just-align, needs no --sam-file\n"
         "  --variants-min-alt arg (=2)           report a site only when at least arg reads carry the alternate base\n"
         "  --variants-min-depth arg (=1)         report a site only when at least arg reads cover it\n"
+        "  --consensus-out arg                   write the consensus sequence of every entry the reads cover to this file as FASTA, called\n"
+        "                                        per position from the pile-up with substitutions, deletions and insertions (as samtools\n"
+        "                                        consensus gives); works with --just-align and single-end, needs no --sam-file\n"
+        "  --consensus-min-depth arg (=1)        call a position only when at least arg reads cover it (at least 1)\n"
+        "  --consensus-call-permille arg (=500)  call a base, a deletion or an insertion only when more than arg of 1000 reads at the\n"
+        "                                        position carry it (500 to 999); else N\n"
+        "  --consensus-fill arg (=n)             n: write N where the depth is below --consensus-min-depth; ref: the entry's own base\n"
+        "  --consensus-min-covered arg (=1)      write an entry only when at least arg of its positions are covered\n"
         "  --depth-out arg                       write the depth along every entry to this file as bedGraph (locus, start, end, depth;\n"
         "                                        0-based, half-open, as bedtools genomecov -bg); works with --just-align, needs no --sam-file\n"
         "  --depth-min arg (=1)                  write only the runs whose depth is at least arg\n"
@@ -181,7 +193,7 @@ Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
          PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT,
-         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, DEPTH_OUT, DEPTH_MIN, GENES_OUT, QC_OUT, QC_MAX_CYCLES, ALIGN_QC_OUT, ALIGN_QC_MAX_CYCLES, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
+         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, CONSENSUS_OUT, CONSENSUS_MIN_DEPTH, CONSENSUS_PERMILLE, CONSENSUS_FILL, CONSENSUS_MIN_COVERED, DEPTH_OUT, DEPTH_MIN, GENES_OUT, QC_OUT, QC_MAX_CYCLES, ALIGN_QC_OUT, ALIGN_QC_MAX_CYCLES, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -207,6 +219,10 @@ Options parse(int argc, char **argv) {
       // not in the reference: include/kslam_variants.h
       {"variants-out", required_argument, nullptr, VARIANTS_OUT}, {"variants-min-alt", required_argument, nullptr, VARIANTS_MIN_ALT},
       {"variants-min-depth", required_argument, nullptr, VARIANTS_MIN_DEPTH},
+      // not in the reference: include/kslam_consensus.h
+      {"consensus-out", required_argument, nullptr, CONSENSUS_OUT}, {"consensus-min-depth", required_argument, nullptr, CONSENSUS_MIN_DEPTH},
+      {"consensus-call-permille", required_argument, nullptr, CONSENSUS_PERMILLE}, {"consensus-fill", required_argument, nullptr, CONSENSUS_FILL},
+      {"consensus-min-covered", required_argument, nullptr, CONSENSUS_MIN_COVERED},
       {"depth-out", required_argument, nullptr, DEPTH_OUT}, {"depth-min", required_argument, nullptr, DEPTH_MIN},   // not in the reference: include/kslam_depth.h
       {"genes-out", required_argument, nullptr, GENES_OUT},   // not in the reference: include/kslam_genes.h
       {"qc-out", required_argument, nullptr, QC_OUT}, {"qc-max-cycles", required_argument, nullptr, QC_MAX_CYCLES},   // not in the reference: include/kslam_readqc.h
@@ -252,6 +268,28 @@ Options parse(int argc, char **argv) {
       case READS_OUT_BGZF: o.reads_out_bgzf = true; break;
       case COVERAGE_OUT: o.coverage_out = optarg; break;
       case VARIANTS_OUT: o.variants_out = optarg; break;
+      case CONSENSUS_OUT: o.consensus_out = optarg; break;
+      case CONSENSUS_MIN_DEPTH:
+        o.consensus.min_depth = to_u32(optarg, "consensus-min-depth");
+        if (o.consensus.min_depth < 1) die(std::string("the argument ('") + optarg + "') for option '--consensus-min-depth' is invalid: at least 1");
+        if (!o.consensus_dependent) o.consensus_dependent = "consensus-min-depth";
+        break;
+      case CONSENSUS_PERMILLE:
+        o.consensus.call_permille = to_u32(optarg, "consensus-call-permille");
+        if (o.consensus.call_permille < 500 || o.consensus.call_permille > 999)
+          die(std::string("the argument ('") + optarg + "') for option '--consensus-call-permille' is invalid: 500 to 999");
+        if (!o.consensus_dependent) o.consensus_dependent = "consensus-call-permille";
+        break;
+      case CONSENSUS_FILL:
+        if (strcmp(optarg, "n") != 0 && strcmp(optarg, "ref") != 0)
+          die(std::string("the argument ('") + optarg + "') for option '--consensus-fill' is invalid");
+        o.consensus.fill = strcmp(optarg, "ref") == 0 ? KSLAM_CONSENSUS_FILL_REF : KSLAM_CONSENSUS_FILL_N;
+        if (!o.consensus_dependent) o.consensus_dependent = "consensus-fill";
+        break;
+      case CONSENSUS_MIN_COVERED:
+        o.consensus.min_covered = to_u32(optarg, "consensus-min-covered");
+        if (!o.consensus_dependent) o.consensus_dependent = "consensus-min-covered";
+        break;
       case DEPTH_OUT: o.depth_out = optarg; break;
       case GENES_OUT: o.genes_out = optarg; break;
       case DEPTH_MIN: o.depth_min = to_u32(optarg, "depth-min"); o.depth_min_given = true; break;
@@ -319,6 +357,7 @@ Options parse(int argc, char **argv) {
   if (o.extract_exclude && o.extract_taxids.empty()) die("option '--extract-exclude' needs '--extract-taxid'");
   if (o.variants_min_alt_given && o.variants_out.empty()) die("option '--variants-min-alt' needs '--variants-out'");
   if (o.variants_min_depth_given && o.variants_out.empty()) die("option '--variants-min-depth' needs '--variants-out'");
+  if (o.consensus_dependent && o.consensus_out.empty()) die(std::string("option '--") + o.consensus_dependent + "' needs '--consensus-out'");
   if (o.depth_min_given && o.depth_out.empty()) die("option '--depth-min' needs '--depth-out'");
   if (o.qc_max_cycles_given && o.qc_out.empty()) die("option '--qc-max-cycles' needs '--qc-out'");
   if (o.align_qc_max_cycles_given && o.align_qc_out.empty()) die("option '--align-qc-max-cycles' needs '--align-qc-out'");
@@ -528,7 +567,7 @@ int run(const Options &o, const std::string &command_line) {
   kp.gap_extend = o.gap_extend;
   kp.score_threshold = o.score_threshold;
   // reportCigar = a SAM file was asked for (src/SLAM.h:169); the variants walk the CIGARs too (the SAM text follows sp.tail.report_cigar)
-  kp.report_cigar = (want_sam || !o.variants_out.empty() || !o.depth_out.empty() || !o.align_qc_out.empty()) ? 1 : 0;
+  kp.report_cigar = (want_sam || !o.variants_out.empty() || !o.consensus_out.empty() || !o.depth_out.empty() || !o.align_qc_out.empty()) ? 1 : 0;
   kp.device = o.device;
   kslam_ctx *ctx = nullptr;
   if (kslam_create(&kp, &ctx) != KSLAM_OK) die(std::string("GPU context: ") + (ctx ? kslam_last_error(ctx) : "kslam_create failed"));
@@ -601,6 +640,12 @@ int run(const Options &o, const std::string &command_line) {
     kreport_fd = open(o.kraken_report.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (kreport_fd < 0) die("unable to open " + o.kraken_report);
     if (kslam_stream_set_kreport(ctx, kreport_fd) != KSLAM_OK) die(std::string("Kraken-style report: ") + kslam_last_error(ctx));
+  }
+  int consensus_fd = -1;
+  if (!o.consensus_out.empty()) {
+    consensus_fd = open(o.consensus_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (consensus_fd < 0) die("unable to open " + o.consensus_out);
+    if (kslam_stream_set_consensus(ctx, consensus_fd, &o.consensus) != KSLAM_OK) die(std::string("consensus: ") + kslam_last_error(ctx));
   }
   int variants_fd = -1;
   if (!o.variants_out.empty()) {
@@ -678,6 +723,7 @@ int run(const Options &o, const std::string &command_line) {
     if (fd >= 0 && close(fd) != 0) die("closing a file of extracted reads failed");
   if (coverage_fd >= 0 && close(coverage_fd) != 0) die("closing the coverage file failed");
   if (variants_fd >= 0 && close(variants_fd) != 0) die("closing the variants file failed");
+  if (consensus_fd >= 0 && close(consensus_fd) != 0) die("closing the consensus file failed");
   if (depth_fd >= 0 && close(depth_fd) != 0) die("closing the depth file failed");
   if (genes_fd >= 0 && close(genes_fd) != 0) die("closing the gene table failed");
   if (kreport_fd >= 0 && close(kreport_fd) != 0) die("closing the Kraken-style report failed");
