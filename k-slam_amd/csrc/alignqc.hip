@@ -2,7 +2,7 @@
 //
 // When a lane has finished a batch, its final read pairs, their alignment-pair records, the overlap records those index, the
 // CIGAR pool, the read bases, the quality column (text route) and the entry bases lie in device memory.  The contributing set
-// is the variants' (contributing_list_device: k_var_flag, scan, k_var_list -- called, not copied), so a record named by three
+// is the variants' (contributing_list_device: k_var_flag, scan, k_scatter_list -- called, not copied), so a record named by three
 // live pairs is counted once.  Several lanes count into one state from their own streams, so every update of the global tables
 // is a device-scope atomic; every accumulator is an integer add, so the result does not depend on who counted what in which
 // order.
@@ -11,8 +11,8 @@
 // length; a wave-uniform loop walks the CIGAR words, and inside an M run the wave takes 64 consecutive columns per step: lane j
 // loads entry[g + j], the read byte at the cycle of q + j and its quality byte.  A forward record reads ascending addresses, a
 // reverse one descending ones; both are contiguous, so the loads coalesce at any alignment.  Lane j holds cycle c0 +- j: two lanes
-// of one instruction never share a per-cycle row below C.  The whole CIGAR is checked first by the same wave (a uniform loop),
-// and that check decides skip-or-count before any counter moves.  The walk is ONE template, aq_walk<WAVE>: the instantiation
+// of one instruction never share a per-cycle row below C.  The whole CIGAR is checked first by the same wave (record_frame,
+// pileup_walk.h: a uniform loop), and that check decides skip-or-count before any counter moves.  The walk is ONE template, aq_walk<WAVE>: the instantiation
 // with WAVE = false is the one-thread-per-record baseline (a column at a time, every add an atomic of its own), kept to be
 // measured against (KSLAM_ALIGNQC_WALK=thread selects it; tools/alignqc_bench.py); the product uses WAVE = true.
 //   tile         grid = (runs of the list, tiles of AQ_TILE cycle rows, streams).  A workgroup owns AQ_TILE consecutive cycle
@@ -54,14 +54,14 @@
 // 64 bits wide.
 // Occupancy: AQ_BLOCK = 1024 threads (16 waves); LDS = 160 * 96 * 4 (s_q, s_c) + 2 * 96 * 8 (row C) + (12 + 16 + 130) * 8 +
 // 166 * 4 = 64 944 bytes, so two workgroups fit the 160 KB of a CU: 32 waves, 8 per SIMD, which leaves 64 VGPRs per lane; the
-// wave instantiation needs 45.  (The baseline instantiation needs 105 and gets one workgroup per CU.)
+// wave instantiation needs 47.  (The baseline instantiation needs 105 and gets one workgroup per CU.)
 // Pair pass (k_aq_pairs): one thread per alignment-pair RECORD, liveness as k_var_flag finds it; the three pair counters are
 // ballots, insert_sum a wave sum (wave_add.h), equal insert bins are combined inside the wave before the atomic.  n_read_pairs
 // is a ballot over the groups (k_aq_groups).
-// Bounds: a record is walked only after read < n_reads, entry < n_entries, its CIGAR slice inside the pool and every M, I and D
-// run inside the read and the entry held; a lane loads entry[rp + j] and read / quality[cycle] only for j below the run's
+// Bounds: a record is walked only after record_frame held (pileup_walk.h: read < n_reads, entry < n_entries, its CIGAR slice inside
+// the pool and every M, I and D run inside the read and the entry); a lane loads entry[rp + j] and read / quality[cycle] only for j below the run's
 // length, so every index lies inside the entry and the read; a row index below C is < row_end <= C; the bins are clamped.
-#include "common.h"
+#include "pileup_walk.h"
 #include "wave_add.h"
 #include "../../include/kslam_alignqc.h"
 
@@ -87,14 +87,6 @@ constexpr uint64_t AQ_SUBST = NSC, AQ_ILEN = AQ_SUBST + 16, AQ_DLEN = AQ_ILEN + 
 __host__ __device__ inline uint64_t aq_cqc(uint32_t C) { return AQ_CYCLE + ((uint64_t)C + 1) * NC; }
 __host__ __device__ inline uint64_t aq_cqm(uint32_t C) { return aq_cqc(C) + ((uint64_t)C + 1) * NQ; }
 
-// complement of reverseComplement: A<->T, C<->G, upper case only
-__device__ inline uint32_t complement(uint32_t c) {
-  const uint32_t at = (c == 'A' || c == 'T') ? (uint32_t)('A' ^ 'T') : 0u;
-  const uint32_t cg = (c == 'C' || c == 'G') ? (uint32_t)('C' ^ 'G') : 0u;
-  return c ^ at ^ cg;
-}
-// A 0, C 1, G 2, T 3 (upper case), anything else 4
-__device__ inline uint32_t acgt(uint32_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
 __device__ inline uint32_t qual_col(uint32_t q) { return q - 33u <= 93u ? q - 33u : 94u; }
 
 // how many of the group's lanes hold p: the wavefront's, or the one thread's
@@ -149,39 +141,14 @@ __device__ inline void aq_walk(const kslam_overlap &o, const VariantInputs &in, 
     acc.s[0]++;
     if (!rqual) acc.s[3]++;
   }
-  bool fits = o.entry < in.n_entries && o.cigar_len != 0 && o.ref_begin >= 0 &&
-              // (kslam_align_qc_add refuses these before anything is launched, and a lane's records do not have them)
-              o.read < in.n_reads && o.cigar_off <= in.n_cig && o.cigar_len <= in.n_cig - o.cigar_off;
-  uint64_t rb = 0, gb = 0;
-  int64_t L = 0, ref_len = 0;
-  const uint32_t *__restrict__ cig = in.pool + (fits ? o.cigar_off : 0);
-  const int64_t q0 = o.query_begin > 0 ? o.query_begin : 0;
-  if (fits) {   // the whole CIGAR against the read and the entry, before anything is counted
-    rb = in.roff[o.read];
-    L = (int64_t)(in.roff[o.read + 1] - rb);
-    gb = in.goff[o.entry];
-    ref_len = (int64_t)(in.goff[o.entry + 1] - gb);
-    int64_t rp = o.ref_begin, qp = q0;
-    for (uint32_t k = 0; k < o.cigar_len && fits; k++) {
-      const uint32_t c = cig[k], op = c & 15u;
-      const int64_t len = c >> 4;
-      if (op == 0) {
-        fits = !(rp + len > ref_len || qp + len > L);
-        rp += len;
-        qp += len;
-      } else if (op == 1) {
-        fits = !(qp + len > L);
-        qp += len;
-      } else if (op == 2) {
-        fits = !(rp + len > ref_len);
-        rp += len;
-      }
-    }
-  }
-  if (!fits) {
+  RecordFrame f;   // (every lane holds the same record: the return is wave-uniform)
+  if (!record_frame(o, in, f)) {
     if (T.owns_rec) acc.s[2]++;
     return;
   }
+  const uint32_t *__restrict__ cig = f.cig;
+  const uint64_t rb = f.rb, gb = f.gb;
+  const int64_t L = f.L, q0 = f.q0;
   const uint8_t *__restrict__ ref = in.gbases + gb;
   const uint8_t *__restrict__ read = in.rbases + rb;
   const uint8_t *__restrict__ qual = rqual ? rqual + rb : nullptr;

@@ -28,7 +28,7 @@ void check_params(const kslam_consensus_params &p) {
 
 // One batch into owner's state: counted on W / s without the lock (the work buffers are the caller's own), appended under it.
 // The write pass has finished when the lock is let go, so that whoever grows the arrays next copies complete keys.
-void emit(kslam_ctx *owner, const VariantInputs &in, ConsensusEmitWork &W, hipStream_t s, bool locked) {
+void emit(kslam_ctx *owner, const VariantInputs &in, EmitWork &W, hipStream_t s, bool locked) {
   consensus_count_device(in, W, s);
   kslam_ctx::Consensus &v = owner->cns;
   std::unique_lock<std::mutex> lk(v.mu, std::defer_lock);

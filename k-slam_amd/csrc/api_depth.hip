@@ -34,19 +34,19 @@ void compact(kslam_ctx::Depth &d, hipStream_t s) {
 }
 
 // One batch into owner's state: counted on W / s without the lock (the work buffers are the caller's own), appended under it.
-void emit(kslam_ctx *owner, const VariantInputs &in, DepthEmitWork &W, hipStream_t s, bool locked) {
+void emit(kslam_ctx *owner, const VariantInputs &in, EmitWork &W, hipStream_t s, bool locked) {
   depth_count_device(in, W, s);
   kslam_ctx::Depth &d = owner->dep;
   std::unique_lock<std::mutex> lk(d.mu, std::defer_lock);
   if (!locked) lk.lock();
   if (!d.on.load(std::memory_order_acquire)) throw StatusError{KSLAM_ERR_STATE, "the depth track was switched off while a batch was in flight"};
-  const uint64_t n_new = 2 * W.n_iv;
+  const uint64_t n_new = 2 * W.n[0];
   if (n_new > DEP_MAX_KEYS) throw StatusError{KSLAM_ERR_UNSUPPORTED, "more than 2^32 - 1 depth keys in one batch (the radix sort's limit): the batch was not added"};
   if (n_new > DEP_MAX_KEYS - d.n_pend) compact(d, s);   // (a threshold set beyond the sort's limit)
   ensure_keep(d.pending, (d.n_pend + n_new + 1) * sizeof(uint64_t), d.n_pend * sizeof(uint64_t), s);
   depth_write_device(in, W, d.pending.as<uint64_t>() + d.n_pend, s);
   d.n_pend += n_new;
-  d.n_iv += W.n_iv;
+  d.n_iv += W.n[0];
   d.n_records += W.n_list;
   d.n_skipped += W.n_skipped;
   if (d.n_pend > (d.compact_at ? d.compact_at : DEP_COMPACT_AT)) {

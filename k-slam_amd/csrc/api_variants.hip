@@ -19,23 +19,23 @@ void empty_state(kslam_ctx::Variants &v) {
 
 // One batch into owner's state: counted on W / s without the lock (the work buffers are the caller's own), appended under it.
 // The write pass has finished when the lock is let go, so that whoever grows the arrays next copies complete keys.
-void emit(kslam_ctx *owner, const VariantInputs &in, VariantEmitWork &W, hipStream_t s, bool locked) {
+void emit(kslam_ctx *owner, const VariantInputs &in, EmitWork &W, hipStream_t s, bool locked) {
   variants_count_device(in, W, s);
   kslam_ctx::Variants &v = owner->var;
   std::unique_lock<std::mutex> lk(v.mu, std::defer_lock);
   if (!locked) lk.lock();
   if (!v.on.load(std::memory_order_acquire)) throw StatusError{KSLAM_ERR_STATE, "the variants were switched off while a batch was in flight"};
-  if (W.n_ev > VAR_MAX_KEYS - v.n_ev || W.n_iv > VAR_MAX_KEYS - v.n_iv)
+  if (W.n[VAR_EV] > VAR_MAX_KEYS - v.n_ev || W.n[VAR_IV] > VAR_MAX_KEYS - v.n_iv)
     throw StatusError{KSLAM_ERR_UNSUPPORTED, "more than 2^32 - 1 stored events or intervals (the radix sort's limit): the batch was not added"};
-  ensure_keep(v.events, (v.n_ev + W.n_ev + 1) * sizeof(uint64_t), v.n_ev * sizeof(uint64_t), s);
-  ensure_keep(v.begins, (v.n_iv + W.n_iv + 1) * sizeof(uint64_t), v.n_iv * sizeof(uint64_t), s);
-  ensure_keep(v.ends, (v.n_iv + W.n_iv + 1) * sizeof(uint64_t), v.n_iv * sizeof(uint64_t), s);
+  ensure_keep(v.events, (v.n_ev + W.n[VAR_EV] + 1) * sizeof(uint64_t), v.n_ev * sizeof(uint64_t), s);
+  ensure_keep(v.begins, (v.n_iv + W.n[VAR_IV] + 1) * sizeof(uint64_t), v.n_iv * sizeof(uint64_t), s);
+  ensure_keep(v.ends, (v.n_iv + W.n[VAR_IV] + 1) * sizeof(uint64_t), v.n_iv * sizeof(uint64_t), s);
   variants_write_device(in, W, v.events.as<uint64_t>() + v.n_ev, v.begins.as<uint64_t>() + v.n_iv, v.ends.as<uint64_t>() + v.n_iv, s);
-  v.n_ev += W.n_ev;
-  v.n_iv += W.n_iv;
+  v.n_ev += W.n[VAR_EV];
+  v.n_iv += W.n[VAR_IV];
   v.n_records += W.n_list;
   v.n_skipped += W.n_skipped;
-  if (W.n_ev || W.n_iv) v.sorted = false;
+  if (W.n[VAR_EV] || W.n[VAR_IV]) v.sorted = false;
 }
 
 }  // namespace

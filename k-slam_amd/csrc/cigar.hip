@@ -67,12 +67,6 @@ __global__ void k_class_mask(const uint32_t *__restrict__ bw, const uint8_t *__r
   if ((threadIdx.x & 63) == 0 && v) atomicOr(mask, v);
 }
 
-__global__ void k_scatter_list(const uint32_t *__restrict__ flags, const uint32_t *__restrict__ pos, uint64_t n,
-                               uint32_t *__restrict__ list) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && flags[i]) list[pos[i]] = (uint32_t)i;
-}
-
 __global__ void k_max_bw(const uint32_t *__restrict__ bw, const uint32_t *__restrict__ list, uint32_t m,
                          uint32_t *__restrict__ out) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -821,8 +815,7 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
       exclusive_scan_u32(W.flags.as<uint32_t>(), W.pos.as<uint32_t>(), n, d_tot, W.scan_tmp.p, s);
       uint64_t m = 0;
       read_back(&m, d_tot, sizeof m, s);
-      if (m) hipLaunchKernelGGL(k_scatter_list, dim3(nb), dim3(256), 0, s, W.flags.as<uint32_t>(),
-                                W.pos.as<uint32_t>(), n, W.list.as<uint32_t>());
+      if (m) scatter_list_device(W.flags.as<uint32_t>(), W.pos.as<uint32_t>(), n, W.list.as<uint32_t>(), s);
       return m;
     };
     // what every launch of this call shares; a launch sets its slice of a list and what differs from these

@@ -838,7 +838,7 @@ void readqc_zero_device(const ReadQcTable &T, hipStream_t s);
 
 // ------------------------------------------------------------ variants.hip
 // The SNV table (include/kslam_variants.h).  The state -- three arrays of 8-byte keys -- belongs to the context the switch was
-// set on (context.h: kslam_ctx::Variants); each lane counts its batch with a VariantEmitWork of its own and appends under the
+// set on (context.h: kslam_ctx::Variants); each lane counts its batch with an EmitWork of its own and appends under the
 // state's lock.
 struct VariantInputs {            // one batch as the kernels see it
   const kslam_overlap *ov;
@@ -856,22 +856,51 @@ struct VariantInputs {            // one batch as the kernels see it
   const uint64_t *goff;
   uint64_t n_entries;
 };
-struct VariantEmitWork {
+// What the emit passes of the three pile-up reports share (variants.hip, depth.hip, consensus.hip): the contributing list, what
+// each listed record emits of each KIND of key (SNV table: events, intervals; depth track: M runs; consensus: consensus.h), the
+// scans that lay out the slots, the batch's totals.
+constexpr int PILEUP_BLOCK = 256;   // threads per workgroup of the three reports' emit and take passes
+inline unsigned pileup_blocks(uint64_t n) { return (unsigned)((n + PILEUP_BLOCK - 1) / PILEUP_BLOCK); }
+constexpr int EMIT_MAX_KINDS = 4;
+constexpr int EMIT_TOTALS = 8;   // u64: [0] the list's length, [1 + kind] the kind's sum, [5] skipped, [6] unanchored, [7] unrepresentable
+struct EmitWork {
   DevBuf flag, pos, list;        // u32 per overlap record: named by a live pair, its place in the list; the list
-  DevBuf cnt_ev, cnt_iv;         // u32 per listed record
-  DevBuf off_ev, off_iv;         // u64 per listed record: its first slot
+  DevBuf cnt;                    // u32 [kinds][n_list]: what each listed record emits of each kind
+  DevBuf off;                    // u64 [kinds][n_list]: its first slot
   DevBuf scan_tmp, totals;
-  uint64_t n_list = 0, n_ev = 0, n_iv = 0, n_skipped = 0;   // of the batch counted last
+  int kinds = 0;                 // of the batch counted last, as what follows
+  uint64_t n_list = 0, n[EMIT_MAX_KINDS] = {0, 0, 0, 0}, n_skipped = 0;
+  uint64_t n_unanchored = 0, n_unrepresentable = 0;   // (insertions the consensus does not store; 0 for the others)
   hipEvent_t ev[2]{};            // before the first pass, after the last
   float ms = 0;
-  VariantEmitWork() = default;
-  VariantEmitWork(const VariantEmitWork &) = delete;
-  VariantEmitWork &operator=(const VariantEmitWork &) = delete;
-  ~VariantEmitWork() {
+  EmitWork() = default;
+  EmitWork(const EmitWork &) = delete;
+  EmitWork &operator=(const EmitWork &) = delete;
+  ~EmitWork() {
     for (auto e : ev)
       if (e) (void)hipEventDestroy(e);
   }
 };
+// one thread per listed record x: cnt[kind * n_list + x] = what it emits of each kind; tallies[0 .. 2] += skipped, unanchored,
+// unrepresentable
+using EmitCountKernel = void (*)(VariantInputs in, const uint32_t *list, uint64_t n_list, uint32_t *cnt, unsigned long long *tallies);
+// the contributing list, the counting walk and one scan per kind; fills W.n_list / n / n_skipped / ... (waits for the stream)
+void emit_count_device(const VariantInputs &in, EmitWork &W, int kinds, EmitCountKernel count, hipStream_t s);
+// after the write kernel: waits for the stream and fills W.ms
+void emit_written(EmitWork &W, hipStream_t s);
+// the writing walk of the batch counted last, unless it emits nothing: write(in, list, n_list, cnt, off, at), one thread per
+// listed record, the keys from `at` on (the caller made room for W.n[kind] of each); waits for the stream and fills W.ms
+template <class Out>
+void emit_write_device(const VariantInputs &in, EmitWork &W, void (*write)(VariantInputs, const uint32_t *, uint64_t, const uint32_t *, const uint64_t *, Out),
+                       const Out &at, hipStream_t s) {
+  uint64_t any = 0;
+  for (int kind = 0; kind < W.kinds; kind++) any |= W.n[kind];
+  if (W.n_list && any)
+    hipLaunchKernelGGL(write, dim3(pileup_blocks(W.n_list)), dim3(PILEUP_BLOCK), 0, s, in, W.list.as<uint32_t>(), W.n_list, W.cnt.as<uint32_t>(),
+                       W.off.as<uint64_t>(), at);
+  emit_written(W, s);
+}
+enum { VAR_EV = 0, VAR_IV = 1, VAR_KINDS = 2 };   // the SNV table's kinds
 struct VariantTakeWork {
   SortWorkspace sortws;
   DevBuf alt;                    // the sort's second buffer
@@ -879,20 +908,26 @@ struct VariantTakeWork {
   DevBuf starts, fwd, rev, depth, keep, out_at;   // u32 per run
   DevBuf rows, scan_tmp, totals;
 };
-// passes 1-4: flags, list, counting walk, scans; fills W.n_list / n_ev / n_iv / n_skipped (waits for the stream)
-void variants_count_device(const VariantInputs &in, VariantEmitWork &W, hipStream_t s);
-// pass 6: the keys of the batch counted last, from d_events / d_begins / d_ends on (the caller made room for W.n_ev / W.n_iv);
-// waits for the stream and fills W.ms
-void variants_write_device(const VariantInputs &in, VariantEmitWork &W, uint64_t *d_events, uint64_t *d_begins, uint64_t *d_ends, hipStream_t s);
+// passes 1-4: flags, list, counting walk, scans; fills W.n_list / n[VAR_EV] / n[VAR_IV] / n_skipped (waits for the stream)
+void variants_count_device(const VariantInputs &in, EmitWork &W, hipStream_t s);
+// pass 6: the keys of the batch counted last, from d_events / d_begins / d_ends on (the caller made room for W.n[VAR_EV] /
+// W.n[VAR_IV]); waits for the stream and fills W.ms
+void variants_write_device(const VariantInputs &in, EmitWork &W, uint64_t *d_events, uint64_t *d_begins, uint64_t *d_ends, hipStream_t s);
 // sorts the three arrays in place unless `sorted`, then the rows that pass the filter into T.rows (device); waits for the stream
 void variants_take_device(VariantTakeWork &T, DevBuf &events, uint64_t n_ev, DevBuf &begins, DevBuf &ends, uint64_t n_iv, bool sorted,
                           const uint64_t *d_goff, const uint8_t *d_gbases, uint64_t n_entries, uint64_t total_bases, uint32_t min_alt,
                           uint32_t min_depth, uint64_t *n_sites_out, uint64_t *n_rows_out, hipStream_t s);
-// passes 1-2 alone, shared with depth.hip: the overlap records a live pair names as a list in `list`; returns its length (waits
-// for the stream).  totals: 4 u64, zeroed here; [0] ends as the list's length
+// passes 1-2 alone, shared by every report that walks the contributing records: the overlap records a live pair names as a list
+// in `list`; returns its length (waits for the stream).  totals: EMIT_TOTALS u64, zeroed here; [0] ends as the list's length
 uint64_t contributing_list_device(const VariantInputs &in, DevBuf &flag, DevBuf &pos, DevBuf &list, DevBuf &scan_tmp, DevBuf &totals, hipStream_t s);
 // sorts n u64 keys of `buf` (scratch: `alt`, at least as large) with as many radix passes as max_key needs; the sorted keys end in `buf`
 void sort_keys(DevBuf &buf, DevBuf &alt, uint64_t n, uint64_t max_key, SortWorkspace &ws, hipStream_t s);
+// list[pos[i]] = i for every i < n with flag[i] (pos: the exclusive scan of the flags)
+void scatter_list_device(const uint32_t *flag, const uint32_t *pos, uint64_t n, uint32_t *list, hipStream_t s);
+// over n sorted keys: head[i] = 1 where a run of keys that are equal but for their low bit begins
+void run_heads_device(const uint64_t *key, uint64_t n, uint32_t *head, hipStream_t s);
+// starts[run[i]] = i for every i < n with head[i] (run: the exclusive scan of the heads)
+void run_starts_device(const uint32_t *head, const uint32_t *run, uint64_t n, uint32_t *starts, hipStream_t s);
 
 // ------------------------------------------------------------ alignqc.hip
 // The alignment QC report (include/kslam_alignqc.h).  The state -- one block of 64-bit counters -- belongs to the context the
@@ -902,7 +937,7 @@ struct AlignQcTable {             // what the passes see
   uint32_t C;                    // cycle rows without the pooled one
 };
 struct AlignQcWork {
-  DevBuf flag, pos, list;        // as VariantEmitWork
+  DevBuf flag, pos, list;        // as EmitWork
   DevBuf scan_tmp, totals;
   hipEvent_t ev[2]{};            // around the count pass
   float ms = 0;                  // its device time, last batch counted with `timed`
@@ -927,21 +962,6 @@ void alignqc_zero_device(const AlignQcTable &T, hipStream_t s);
 // key = g_off[entry] + entry + pos, so that the boundary after the last base of entry e is not the first base of entry e + 1.
 // Pending: u64 (key << 1) | is_end, two per M run, appended per batch.  Compacted: distinct keys ascending with their net change
 // (i64: begins less ends; a count must hold 2^32 - 1, which a signed 32-bit change does not), none of them 0.
-struct DepthEmitWork {
-  DevBuf flag, pos, list;        // as VariantEmitWork
-  DevBuf cnt, off;               // per listed record: its M runs (u32), its first run's slot (u64)
-  DevBuf scan_tmp, totals;
-  uint64_t n_list = 0, n_iv = 0, n_skipped = 0;   // of the batch counted last
-  hipEvent_t ev[2]{};
-  float ms = 0;
-  DepthEmitWork() = default;
-  DepthEmitWork(const DepthEmitWork &) = delete;
-  DepthEmitWork &operator=(const DepthEmitWork &) = delete;
-  ~DepthEmitWork() {
-    for (auto e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
 struct DepthWork {                // compaction and take; used under the state's lock
   SortWorkspace sortws;
   DevBuf alt;                    // the sort's second buffer
@@ -953,10 +973,11 @@ struct DepthWork {                // compaction and take; used under the state's
   DevBuf tile_sum, depth;        // take: i64 per scan tile; u32 per boundary: the depth from it on
   DevBuf rows, scan_tmp, totals;
 };
-// the list, the counting walk and the scan; fills W.n_list / n_iv / n_skipped (waits for the stream).  in.rbases / in.gbases are not read
-void depth_count_device(const VariantInputs &in, DepthEmitWork &W, hipStream_t s);
-// the writing walk: 2 * W.n_iv pending keys from d_pending on (the caller made room); waits for the stream and fills W.ms
-void depth_write_device(const VariantInputs &in, DepthEmitWork &W, uint64_t *d_pending, hipStream_t s);
+// the list, the counting walk and the scan; fills W.n_list / n[0] (M runs) / n_skipped (waits for the stream).  in.rbases /
+// in.gbases are not read
+void depth_count_device(const VariantInputs &in, EmitWork &W, hipStream_t s);
+// the writing walk: 2 * W.n[0] pending keys from d_pending on (the caller made room); waits for the stream and fills W.ms
+void depth_write_device(const VariantInputs &in, EmitWork &W, uint64_t *d_pending, hipStream_t s);
 // sort, reduce, merge, drop: n_pend pending keys into the compacted list (ckey / cnet, *n_keys of them).  Throws
 // KSLAM_ERR_UNSUPPORTED before the compacted list is touched when the merge would pass 2^32 - 1 records.  Waits for the stream.
 void depth_compact_device(DepthWork &T, DevBuf &pending, uint64_t n_pend, DevBuf &ckey, DevBuf &cnet, uint64_t *n_keys, uint64_t max_key, hipStream_t s);

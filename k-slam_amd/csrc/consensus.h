@@ -1,30 +1,13 @@
 // consensus.h -- the consensus caller's device side as the ABI sees it (include/kslam_consensus.h; kernels: consensus.hip).
 // The state -- six append-only arrays of keys -- belongs to the context the switch was set on (context.h: kslam_ctx::Consensus);
-// each lane counts its batch with a ConsensusEmitWork of its own and appends under the state's lock.
+// each lane counts its batch with an EmitWork of its own (common.h) and appends under the state's lock.
 #pragma once
 #include "common.h"
 #include "../../include/kslam_consensus.h"
 
 namespace kslam {
 
-enum { CNS_EV = 0, CNS_M = 1, CNS_D = 2, CNS_INS = 3, CNS_KINDS = 4 };   // the kinds of keys a record emits
-
-struct ConsensusEmitWork {
-  DevBuf flag, pos, list, list_tot;   // as VariantEmitWork (contributing_list_device)
-  DevBuf cnt;                         // u32 [CNS_KINDS][n_list]: what each listed record emits of each kind
-  DevBuf off;                         // u64 [CNS_KINDS][n_list]: its first slot
-  DevBuf scan_tmp, totals;            // totals: u64 [8] = the four kinds' sums, skipped, unanchored, unrepresentable
-  uint64_t n_list = 0, n[CNS_KINDS] = {0, 0, 0, 0}, n_skipped = 0, n_unanchored = 0, n_unrepresentable = 0;   // of the batch counted last
-  hipEvent_t ev[2]{};                 // before the first pass, after the last
-  float ms = 0;
-  ConsensusEmitWork() = default;
-  ConsensusEmitWork(const ConsensusEmitWork &) = delete;
-  ConsensusEmitWork &operator=(const ConsensusEmitWork &) = delete;
-  ~ConsensusEmitWork() {
-    for (auto e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
+enum { CNS_EV = 0, CNS_M = 1, CNS_D = 2, CNS_INS = 3, CNS_KINDS = 4 };   // the kinds of keys a record emits (EmitWork's n[kind])
 
 struct ConsensusKeys {                // the state's arrays (or where a batch's keys go)
   uint64_t *ev;                       // (g << 3) | code
@@ -52,10 +35,10 @@ struct ConsensusCall {                // one take, as the host sees it
 };
 
 // the contributing list, the counting walk and the four scans; fills W.n_list / n / n_skipped / ... (waits for the stream)
-void consensus_count_device(const VariantInputs &in, ConsensusEmitWork &W, hipStream_t s);
+void consensus_count_device(const VariantInputs &in, EmitWork &W, hipStream_t s);
 // the writing walk: the keys of the batch counted last, from `at` on (the caller made room for W.n[kind] of each); waits for
 // the stream and fills W.ms
-void consensus_write_device(const VariantInputs &in, ConsensusEmitWork &W, const ConsensusKeys &at, hipStream_t s);
+void consensus_write_device(const VariantInputs &in, EmitWork &W, const ConsensusKeys &at, hipStream_t s);
 // sorts the six arrays in place (insertions: by key, then by bases)
 void consensus_sort_device(ConsensusTakeWork &T, DevBuf &ev, DevBuf &mb, DevBuf &me, DevBuf &db, DevBuf &de, DevBuf &ins, const uint64_t n[CNS_KINDS],
                            uint64_t total_bases, hipStream_t s);

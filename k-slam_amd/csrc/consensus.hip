@@ -9,14 +9,14 @@
 //   ins       two words per stored insertion: [0] the bases at 2 bits each, the first one highest; [1] (anchor << 6) | (len - 1)
 // Per batch (consensus_count_device, consensus_write_device):
 //   1-2. variants.hip's flag / scan / list passes (contributing_list_device): the overlap records a live pair names, once each
-//   3. k_cns_count   one thread per listed record: cns_walk<CountSink> checks the CIGAR whole against the read and the entry,
-//                    then walks it; what it would emit of each kind is counted, and the runs that are not stored are tallied
+//   3. k_cns_count   one thread per listed record: walk_record (pileup_walk.h) checks the CIGAR whole against the read and the
+//                    entry, then walks it into a CnsSink<CountEmit>; what it would emit of each kind is counted, and the I runs
+//                    that are not stored are tallied
 //   4. four scans    lay out the slots
 //   5. the caller makes room (api_consensus.hip: under the state's lock)
-//   6. k_cns_write   the same walk function writes the keys through a WriteSink
-// The walk is the SNV table's chunk loop with wider sinks: ONE loop over 16-column chunks of M runs, one unaligned 16-byte load
-// per chunk and stream, the alphabet looked at only on the columns that differ; D runs and I runs are handled on the way from
-// one M run to the next, an I run's bases (at most 32) bytewise.
+//   6. k_cns_write   the same walk writes the keys through a CnsSink<WriteEmit>
+// The walk is the SNV table's and the depth track's, with the widest sink: every differing column, the D runs, and the I runs,
+// whose bases (at most 32) are read bytewise by this sink alone.
 // On request (consensus_sort_device, consensus_take_device): radix_sort of the six arrays; one thread per ENTRY marks the entries
 // holding an M or D run, a scan lists them; the host cuts the list into slices of whole entries; per slice
 //   k_cns_call    one thread per position: m and dl by two binary searches each over the sorted interval arrays, the position's
@@ -24,168 +24,78 @@
 //                 what the write pass needs; the entry's counters are combined inside the wavefront (wave_add.h)
 //   a scan        places the bytes
 //   k_cns_write_seq   stores them, for the reported entries alone, where the host laid their sequences out
-// Bounds: as variants.hip -- a record is walked only after its whole CIGAR held inside the read, the entry and the pool; a
-// 16-byte load may run up to 15 bytes past the last base of the arrays, inside the slack every DevBuf has, and those bytes are
-// masked out; a load that would begin before the read array is done bytewise.  An I run's bytes lie inside the read (the check
-// covered them).  The call pass indexes positions of touched entries only, below g_off[n_entries].
+// Bounds: the walk's are stated in pileup_walk.h; an I run's bytes lie inside the read (the fit check covered them).  The call
+// pass indexes positions of touched entries only, below g_off[n_entries].
 #include "consensus.h"
+#include "pileup_walk.h"
 #include "wave_add.h"
 
 namespace kslam {
 
 namespace {
 
-constexpr int CNS_BLOCK = 256;
+constexpr int CNS_BLOCK = PILEUP_BLOCK;
 constexpr uint32_t NO_INS = 0xFFFFFFFFu;
 constexpr uint64_t NOT_REPORTED = ~0ull;
 
-struct __attribute__((packed, aligned(1))) Bytes16 {
-  uint32_t w[4];
-};
-__device__ inline uint32_t byte_of(const Bytes16 &v, uint32_t j) { return (v.w[j >> 2] >> (8 * (j & 3))) & 0xFFu; }
-
-// complement of reverseComplement: A<->T, C<->G, upper case only
-__device__ inline uint32_t complement(uint32_t c) {
-  const uint32_t at = (c == 'A' || c == 'T') ? (uint32_t)('A' ^ 'T') : 0u;
-  const uint32_t cg = (c == 'C' || c == 'G') ? (uint32_t)('C' ^ 'G') : 0u;
-  return c ^ at ^ cg;
-}
-// A 0, C 1, G 2, T 3 (upper case), anything else 4
-__device__ inline uint32_t acgt(uint32_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
-
-struct CountSink {
+// an I run is unanchored (no reference position consumed before it), stored, or unrepresentable (too long, or a base outside
+// ACGT).  (Counted with sums, not one increment per case: three branches that each add 1 to another counter are merged into
+// one add through a pointer, which takes the counters out of registers.)
+struct CountEmit {
   uint32_t n[CNS_KINDS] = {0, 0, 0, 0}, unanchored = 0, unrepresentable = 0;
   __device__ void event(uint64_t) { n[CNS_EV]++; }
-  __device__ void m_run(uint64_t, uint64_t) { n[CNS_M]++; }
-  __device__ void d_run(uint64_t, uint64_t) { n[CNS_D]++; }
-  __device__ void insertion(uint64_t, uint64_t) { n[CNS_INS]++; }
-  __device__ void ins_unanchored() { unanchored++; }
-  __device__ void ins_unrepresentable() { unrepresentable++; }
+  __device__ void m(uint64_t, uint64_t) { n[CNS_M]++; }
+  __device__ void d(uint64_t, uint64_t) { n[CNS_D]++; }
+  __device__ void insertion(bool anchored, bool stored, uint64_t, uint64_t) {
+    n[CNS_INS] += stored ? 1u : 0u;
+    unanchored += anchored ? 0u : 1u;
+    unrepresentable += anchored && !stored ? 1u : 0u;
+  }
 };
-struct WriteSink {
+struct WriteEmit {
   ConsensusKeys at;
   __device__ void event(uint64_t key) { *at.ev++ = key; }
-  __device__ void m_run(uint64_t b, uint64_t e) { *at.mb++ = b; *at.me++ = e; }
-  __device__ void d_run(uint64_t b, uint64_t e) { *at.db++ = b; *at.de++ = e; }
-  __device__ void insertion(uint64_t key, uint64_t bases) { at.ins[0] = bases; at.ins[1] = key; at.ins += 2; }
-  __device__ void ins_unanchored() {}
-  __device__ void ins_unrepresentable() {}
+  __device__ void m(uint64_t b, uint64_t e) { *at.mb++ = b; *at.me++ = e; }
+  __device__ void d(uint64_t b, uint64_t e) { *at.db++ = b; *at.de++ = e; }
+  __device__ void insertion(bool, bool stored, uint64_t key, uint64_t bases) {
+    if (!stored) return;
+    at.ins[0] = bases;
+    at.ins[1] = key;
+    at.ins += 2;
+  }
 };
 
-// false: the record is skipped (nothing was handed to the sink)
-template <class Sink>
-__device__ inline bool cns_walk(const kslam_overlap &o, const VariantInputs &in, Sink &sink) {
-  if (o.entry >= in.n_entries || o.cigar_len == 0 || o.ref_begin < 0) return false;
-  // (kslam_consensus_add refuses these before anything is launched, and a lane's records do not have them)
-  if (o.read >= in.n_reads || o.cigar_off > in.n_cig || o.cigar_len > in.n_cig - o.cigar_off) return false;
-  const uint64_t rb = in.roff[o.read];
-  const int64_t L = (int64_t)(in.roff[o.read + 1] - rb);
-  const uint64_t gb = in.goff[o.entry];
-  const int64_t ref_len = (int64_t)(in.goff[o.entry + 1] - gb);
-  const uint32_t *__restrict__ cig = in.pool + o.cigar_off;
-  const int64_t q0 = o.query_begin > 0 ? o.query_begin : 0;
-  {   // the whole CIGAR against the read and the entry, before anything is emitted
-    int64_t rp = o.ref_begin, qp = q0;
-    for (uint32_t k = 0; k < o.cigar_len; k++) {
-      const uint32_t c = cig[k], op = c & 15u;
-      const int64_t len = c >> 4;
-      if (op == 0) {
-        if (rp + len > ref_len || qp + len > L) return false;
-        rp += len;
-        qp += len;
-      } else if (op == 1) {
-        if (qp + len > L) return false;
-        qp += len;
-      } else if (op == 2) {
-        if (rp + len > ref_len) return false;
-        rp += len;
-      }
-    }
+// the oriented bases of the I run at query positions qp .. qp + len - 1 (inside the read: the fit check covered them), bytewise,
+// at 2 bits each, the first one highest; false: one of them is not ACGT.  len <= 32.
+__device__ inline bool insertion_bases(const kslam_overlap &o, const VariantInputs &in, const RecordFrame &f, int64_t qp, uint32_t len, uint64_t *bases) {
+  uint64_t w = 0;
+  bool ok = true;
+  for (uint32_t j = 0; j < len; j++) {
+    const int64_t q = qp + (int64_t)j;
+    const uint32_t b = o.revcomp ? complement(in.rbases[f.rb + (uint64_t)(f.L - 1 - q)]) : (uint32_t)in.rbases[f.rb + (uint64_t)q];
+    const uint32_t code = acgt(b);
+    ok = ok && code < 4u;
+    w = (w << 2) | (code & 3u);
   }
-  const uint8_t *__restrict__ ref = in.gbases + gb;
-  const bool rc = o.revcomp != 0;
-  int64_t rp = o.ref_begin, qp = q0;
-  uint32_t k = 0, m_len = 0, i0 = 0;
-  for (;;) {
-    if (i0 >= m_len) {   // the M run is used up: operations until the next one (I and D on the way)
-      bool got = false;
-      while (k < o.cigar_len) {
-        const uint32_t c = cig[k], len = c >> 4, op = c & 15u;
-        k++;
-        if (op == 0) {
-          if (len) {
-            sink.m_run(gb + (uint64_t)rp, gb + (uint64_t)rp + len - 1);
-            m_len = len;
-            i0 = 0;
-            got = true;
-            break;
-          }
-        } else if (op == 1) {
-          if (len) {
-            if (rp <= (int64_t)o.ref_begin) {   // no reference position consumed yet
-              sink.ins_unanchored();
-            } else if (len > KSLAM_CONSENSUS_MAX_INS) {
-              sink.ins_unrepresentable();
-            } else {   // query positions qp .. qp + len - 1, inside the read (checked above)
-              uint64_t w = 0;
-              bool ok = true;
-              for (uint32_t j = 0; j < len; j++) {
-                const int64_t q = qp + (int64_t)j;
-                const uint32_t b = rc ? complement(in.rbases[rb + (uint64_t)(L - 1 - q)]) : (uint32_t)in.rbases[rb + (uint64_t)q];
-                const uint32_t code = acgt(b);
-                ok = ok && code < 4u;
-                w = (w << 2) | (code & 3u);
-              }
-              if (ok) sink.insertion(((gb + (uint64_t)rp - 1) << 6) | (uint64_t)(len - 1), w);
-              else sink.ins_unrepresentable();
-            }
-          }
-          qp += len;
-        } else if (op == 2) {
-          if (len) sink.d_run(gb + (uint64_t)rp, gb + (uint64_t)rp + len - 1);
-          rp += len;
-        }
-      }
-      if (!got) break;
-    }
-    const uint32_t nn = min(16u, m_len - i0);
-    const Bytes16 R = *reinterpret_cast<const Bytes16 *>(ref + rp + i0);
-    // forward: the bytes from query position qp + i0 on; reverse: the 16 bytes ENDING at read index L - 1 - qp - i0, back to front
-    const int64_t first = rc ? (int64_t)rb + (L - 1 - qp) - (int64_t)i0 - 15 : (int64_t)rb + qp + (int64_t)i0;
-    Bytes16 B;
-    if (first >= 0) {
-      B = *reinterpret_cast<const Bytes16 *>(in.rbases + first);
-    } else {   // (reverse strand at the very start of the batch's first read: stay inside the array)
-#pragma unroll
-      for (int x = 0; x < 4; x++) B.w[x] = 0;
-      for (int j = 0; j < 16; j++)
-        if (first + j >= 0) B.w[j >> 2] |= (uint32_t)in.rbases[first + j] << (8 * (j & 3));
-    }
-    if (rc) {   // byte j of the chunk is byte 15 - j of what was loaded
-      const uint32_t b0 = __builtin_bswap32(B.w[3]), b1 = __builtin_bswap32(B.w[2]), b2 = __builtin_bswap32(B.w[1]), b3 = __builtin_bswap32(B.w[0]);
-      B.w[0] = b0; B.w[1] = b1; B.w[2] = b2; B.w[3] = b3;
-    }
-    // the columns that differ, without a branch; the alphabet is looked at once per difference
-    uint32_t miss = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < 16; j++) {
-      const uint32_t b = byte_of(B, j), q = rc ? complement(b) : b;
-      miss |= (j < nn && byte_of(R, j) != q ? 1u : 0u) << j;
-    }
-    while (miss) {
-      const uint32_t j = (uint32_t)__builtin_ctz(miss);
-      miss &= miss - 1;
-      const uint32_t b = byte_of(B, j);
-      sink.event(((gb + (uint64_t)rp + i0 + j) << 3) | (uint64_t)acgt(rc ? complement(b) : b));
-    }
-    i0 += 16;
-    if (i0 >= m_len) {   // the run is done
-      rp += m_len;
-      qp += m_len;
-    }
-  }
-  return true;
+  *bases = w;
+  return ok;
 }
+
+// the walk's sink (pileup_walk.h): M and D runs as closed intervals, every differing column with its code 0 .. 4, and the I runs
+// -- the only sink that reads an I run's bases
+template <class Emit>
+struct CnsSink : Emit {
+  static constexpr bool COLUMNS = true, INSERTIONS = true;
+  __device__ void m_run(const kslam_overlap &, const RecordFrame &f, int64_t rp, uint32_t len) { Emit::m(f.gb + (uint64_t)rp, f.gb + (uint64_t)rp + len - 1); }
+  __device__ void d_run(const kslam_overlap &, const RecordFrame &f, int64_t rp, uint32_t len) { Emit::d(f.gb + (uint64_t)rp, f.gb + (uint64_t)rp + len - 1); }
+  __device__ void column(uint64_t g, uint32_t q, uint32_t, bool) { Emit::event((g << 3) | (uint64_t)acgt(q)); }
+  __device__ void i_run(const kslam_overlap &o, const VariantInputs &in, const RecordFrame &f, int64_t rp, int64_t qp, uint32_t len) {
+    const bool anchored = rp > (int64_t)o.ref_begin;
+    uint64_t w = 0;
+    const bool stored = anchored && len <= KSLAM_CONSENSUS_MAX_INS && insertion_bases(o, in, f, qp, len, &w);
+    Emit::insertion(anchored, stored, ((f.gb + (uint64_t)rp - 1) << 6) | (uint64_t)(len - 1), w);
+  }
+};
 
 __global__ __launch_bounds__(CNS_BLOCK) void k_cns_count(VariantInputs in, const uint32_t *__restrict__ list, uint64_t n_list,
                                                          uint32_t *__restrict__ cnt, unsigned long long *__restrict__ tallies) {
@@ -193,8 +103,8 @@ __global__ __launch_bounds__(CNS_BLOCK) void k_cns_count(VariantInputs in, const
   uint64_t skip = 0, unanchored = 0, unrepresentable = 0;
   if (x < n_list) {
     const kslam_overlap o = in.ov[list[x]];
-    CountSink sink;
-    if (!cns_walk(o, in, sink)) skip = 1;
+    CnsSink<CountEmit> sink;
+    if (!walk_record(o, in, sink)) skip = 1;
 #pragma unroll
     for (int kind = 0; kind < CNS_KINDS; kind++) cnt[(uint64_t)kind * n_list + x] = sink.n[kind];
     unanchored = sink.unanchored;
@@ -217,22 +127,11 @@ __global__ __launch_bounds__(CNS_BLOCK) void k_cns_write(VariantInputs in, const
   if ((cnt[x] | cnt[n_list + x] | cnt[2 * n_list + x] | cnt[3 * n_list + x]) == 0) return;   // (a skipped record counted nothing)
   const kslam_overlap o = in.ov[list[x]];
   const uint64_t o_ev = off[x], o_m = off[n_list + x], o_d = off[2 * n_list + x], o_ins = off[3 * n_list + x];
-  WriteSink sink{ConsensusKeys{at.ev + o_ev, at.mb + o_m, at.me + o_m, at.db + o_d, at.de + o_d, at.ins + 2 * o_ins}};
-  (void)cns_walk(o, in, sink);
+  CnsSink<WriteEmit> sink{{ConsensusKeys{at.ev + o_ev, at.mb + o_m, at.me + o_m, at.db + o_d, at.de + o_d, at.ins + 2 * o_ins}}};
+  (void)walk_record(o, in, sink);
 }
 
 // ---- take ----
-
-// the first i in [lo, hi) with a[i * stride] >= v (hi when there is none)
-template <int STRIDE = 1>
-__device__ inline uint64_t lower_bound(const uint64_t *__restrict__ a, uint64_t lo, uint64_t hi, uint64_t v) {
-  while (lo < hi) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (a[mid * STRIDE] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // touched: the entry holds at least one M or D run (a run lies inside one entry, so its first column decides)
 __global__ __launch_bounds__(CNS_BLOCK) void k_cns_touched(const uint64_t *__restrict__ goff, uint64_t n_entries, const uint64_t *__restrict__ mb,
@@ -250,12 +149,6 @@ __global__ __launch_bounds__(CNS_BLOCK) void k_cns_touched(const uint64_t *__res
     }
   }
   flag[e] = t ? 1u : 0u;
-}
-
-__global__ __launch_bounds__(CNS_BLOCK) void k_cns_list(const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos, uint64_t n,
-                                                        uint32_t *__restrict__ list) {
-  const uint64_t i = (uint64_t)blockIdx.x * CNS_BLOCK + threadIdx.x;
-  if (i < n && flag[i]) list[pos[i]] = (uint32_t)i;
 }
 
 struct SliceView {                 // touched entries [t0, t1) and their npos positions
@@ -382,8 +275,6 @@ __global__ __launch_bounds__(CNS_BLOCK) void k_cns_write_seq(SliceView S, const 
   for (uint32_t i = 0; i < il; i++) dst[i] = (uint8_t)((0x54474341u >> (8u * (uint32_t)((w >> (2u * (il - 1u - i))) & 3u))) & 0xFFu);
 }
 
-inline unsigned blocks(uint64_t n) { return (unsigned)((n + CNS_BLOCK - 1) / CNS_BLOCK); }
-
 // sorts n insertion records of `buf` by (key, bases): two stable runs of the radix sort, the less significant word first
 void sort_insertions(DevBuf &buf, DevBuf &alt, uint64_t n, uint64_t max_key, SortWorkspace &ws, hipStream_t s) {
   if (n < 2) return;
@@ -401,45 +292,9 @@ void sort_insertions(DevBuf &buf, DevBuf &alt, uint64_t n, uint64_t max_key, Sor
 
 }  // namespace
 
-void consensus_count_device(const VariantInputs &in, ConsensusEmitWork &W, hipStream_t s) {
-  W.ms = 0;
-  W.n_list = W.n_skipped = W.n_unanchored = W.n_unrepresentable = 0;
-  for (auto &v : W.n) v = 0;
-  if (!W.ev[0])
-    for (auto &e : W.ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(W.ev[0], s));
-  if (!in.n_groups || !in.n_pairs || !in.n_ov) return;
-  const uint64_t n_list = contributing_list_device(in, W.flag, W.pos, W.list, W.scan_tmp, W.list_tot, s);
-  W.n_list = n_list;
-  if (!n_list) return;
-  W.totals.ensure(8 * sizeof(uint64_t));
-  uint64_t *d_tot = W.totals.as<uint64_t>();
-  HIPCHK(hipMemsetAsync(d_tot, 0, 8 * sizeof(uint64_t), s));
-  W.cnt.ensure(CNS_KINDS * n_list * sizeof(uint32_t));
-  W.off.ensure(CNS_KINDS * n_list * sizeof(uint64_t));
-  W.scan_tmp.ensure(scan_tmp_bytes(n_list));
-  hipLaunchKernelGGL(k_cns_count, dim3(blocks(n_list)), dim3(CNS_BLOCK), 0, s, in, W.list.as<uint32_t>(), n_list, W.cnt.as<uint32_t>(),
-                     reinterpret_cast<unsigned long long *>(d_tot + 4));
-  HIPCHK(hipGetLastError());
-  for (int kind = 0; kind < CNS_KINDS; kind++)
-    exclusive_scan_u32_to_u64(W.cnt.as<uint32_t>() + kind * n_list, W.off.as<uint64_t>() + kind * n_list, n_list, d_tot + kind, W.scan_tmp.p, s);
-  uint64_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  read_back(h, d_tot, sizeof h, s);
-  for (int kind = 0; kind < CNS_KINDS; kind++) W.n[kind] = h[kind];
-  W.n_skipped = h[4];
-  W.n_unanchored = h[5];
-  W.n_unrepresentable = h[6];
-}
+void consensus_count_device(const VariantInputs &in, EmitWork &W, hipStream_t s) { emit_count_device(in, W, CNS_KINDS, k_cns_count, s); }
 
-void consensus_write_device(const VariantInputs &in, ConsensusEmitWork &W, const ConsensusKeys &at, hipStream_t s) {
-  if (W.n_list && (W.n[CNS_EV] || W.n[CNS_M] || W.n[CNS_D] || W.n[CNS_INS]))
-    hipLaunchKernelGGL(k_cns_write, dim3(blocks(W.n_list)), dim3(CNS_BLOCK), 0, s, in, W.list.as<uint32_t>(), W.n_list, W.cnt.as<uint32_t>(),
-                       W.off.as<uint64_t>(), at);
-  HIPCHK(hipEventRecord(W.ev[1], s));
-  HIPCHK(hipGetLastError());
-  HIPCHK(stream_wait(s));
-  HIPCHK(hipEventElapsedTime(&W.ms, W.ev[0], W.ev[1]));
-}
+void consensus_write_device(const VariantInputs &in, EmitWork &W, const ConsensusKeys &at, hipStream_t s) { emit_write_device(in, W, k_cns_write, at, s); }
 
 void consensus_sort_device(ConsensusTakeWork &T, DevBuf &ev, DevBuf &mb, DevBuf &me, DevBuf &db, DevBuf &de, DevBuf &ins, const uint64_t n[CNS_KINDS],
                            uint64_t total_bases, hipStream_t s) {
@@ -474,7 +329,7 @@ void consensus_take_device(ConsensusTakeWork &T, const ConsensusKeys &K, const u
   T.scan_tmp.ensure(scan_tmp_bytes(n_entries));
   T.totals.ensure(2 * sizeof(uint64_t));
   uint64_t *d_tot = T.totals.as<uint64_t>();
-  hipLaunchKernelGGL(k_cns_touched, dim3(blocks(n_entries)), dim3(CNS_BLOCK), 0, s, d_goff, n_entries, K.mb, n[CNS_M], K.db, n[CNS_D], T.tflag.as<uint32_t>());
+  hipLaunchKernelGGL(k_cns_touched, dim3(pileup_blocks(n_entries)), dim3(CNS_BLOCK), 0, s, d_goff, n_entries, K.mb, n[CNS_M], K.db, n[CNS_D], T.tflag.as<uint32_t>());
   HIPCHK(hipGetLastError());
   exclusive_scan_u32(T.tflag.as<uint32_t>(), T.tpos.as<uint32_t>(), n_entries, d_tot, T.scan_tmp.p, s);
   uint64_t n_touched = 0;
@@ -482,8 +337,7 @@ void consensus_take_device(ConsensusTakeWork &T, const ConsensusKeys &K, const u
   out.n_touched = n_touched;
   if (!n_touched) return;
   T.tlist.ensure(n_touched * sizeof(uint32_t));
-  hipLaunchKernelGGL(k_cns_list, dim3(blocks(n_entries)), dim3(CNS_BLOCK), 0, s, T.tflag.as<uint32_t>(), T.tpos.as<uint32_t>(), n_entries, T.tlist.as<uint32_t>());
-  HIPCHK(hipGetLastError());
+  scatter_list_device(T.tflag.as<uint32_t>(), T.tpos.as<uint32_t>(), n_entries, T.tlist.as<uint32_t>(), s);
   std::vector<uint32_t> tlist(n_touched);
   HIPCHK(hipMemcpyAsync(tlist.data(), T.tlist.p, n_touched * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIPCHK(stream_wait(s));
@@ -507,7 +361,7 @@ void consensus_take_device(ConsensusTakeWork &T, const ConsensusKeys &K, const u
     T.counters.ensure(8 * nt * sizeof(uint64_t));
     T.scan_tmp.ensure(scan_tmp_bytes(npos));
     HIPCHK(hipMemsetAsync(T.counters.p, 0, 8 * nt * sizeof(uint64_t), s));
-    hipLaunchKernelGGL(k_cns_call, dim3(blocks(npos)), dim3(CNS_BLOCK), 0, s, S, K, n[CNS_EV], n[CNS_M], n[CNS_D], n[CNS_INS], d_goff, d_gbases, P,
+    hipLaunchKernelGGL(k_cns_call, dim3(pileup_blocks(npos)), dim3(CNS_BLOCK), 0, s, S, K, n[CNS_EV], n[CNS_M], n[CNS_D], n[CNS_INS], d_goff, d_gbases, P,
                        T.len.as<uint32_t>(), T.call.as<uint8_t>(), T.insidx.as<uint32_t>(), T.counters.as<unsigned long long>());
     HIPCHK(hipGetLastError());
     exclusive_scan_u32_to_u64(T.len.as<uint32_t>(), T.off.as<uint64_t>(), npos, d_tot + 1, T.scan_tmp.p, s);
@@ -546,7 +400,7 @@ void consensus_take_device(ConsensusTakeWork &T, const ConsensusKeys &K, const u
       }
       T.obase.ensure(nt * sizeof(uint64_t));
       HIPCHK(hipMemcpyAsync(T.obase.p, obase.data(), nt * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(k_cns_write_seq, dim3(blocks(npos)), dim3(CNS_BLOCK), 0, s, S, K.ins, T.len.as<uint32_t>(), T.off.as<uint64_t>(),
+      hipLaunchKernelGGL(k_cns_write_seq, dim3(pileup_blocks(npos)), dim3(CNS_BLOCK), 0, s, S, K.ins, T.len.as<uint32_t>(), T.off.as<uint64_t>(),
                          T.call.as<uint8_t>(), T.insidx.as<uint32_t>(), T.obase.as<uint64_t>(), T.seq.as<uint8_t>());
       HIPCHK(hipGetLastError());
       HIPCHK(stream_wait(s));   // (obase is the host's vector, reused by the next slice)

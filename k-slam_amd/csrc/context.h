@@ -231,7 +231,7 @@ struct kslam_ctx {
     uint32_t stream_min_alt = 2, stream_min_depth = 1;
     std::mutex mu;                // append / take / reset / the switch: one at a time
   } var;
-  VariantEmitWork varw;           // this context's own emit passes (a lane's batches; on the primary: kslam_variants_add)
+  EmitWork varw;                  // this context's own emit passes (a lane's batches; on the primary: kslam_variants_add)
 
   // ---- the consensus caller (consensus.hip, include/kslam_consensus.h) ----
   struct Consensus {              // on the context the switch was set on; its lanes append to it (lane_main)
@@ -249,7 +249,7 @@ struct kslam_ctx {
     kslam_consensus_params stream_params{1, 500, KSLAM_CONSENSUS_FILL_N, 1};
     std::mutex mu;                // append / take / reset / the switch: one at a time
   } cns;
-  ConsensusEmitWork cnsw;         // this context's own emit passes (a lane's batches; on the primary: kslam_consensus_add)
+  EmitWork cnsw;                  // this context's own emit passes (a lane's batches; on the primary: kslam_consensus_add)
 
   // ---- the depth track (depth.hip, include/kslam_depth.h) ----
   struct Depth {                  // on the context the switch was set on; its lanes append to it (lane_main)
@@ -267,7 +267,7 @@ struct kslam_ctx {
     uint32_t stream_min_depth = 1;
     std::mutex mu;                // append / compact / take / reset / the switch: one at a time
   } dep;
-  DepthEmitWork depw;             // this context's own emit passes (a lane's batches; on the primary: kslam_depth_add)
+  EmitWork depw;                  // this context's own emit passes (a lane's batches; on the primary: kslam_depth_add)
 
   // ---- the Kraken-style report's counts (kreport.hip, include/kslam_kreport.h) ----
   struct Kreport {                // on the context the switch was set on; its lanes count into it (lane_main)

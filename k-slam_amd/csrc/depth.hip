@@ -8,14 +8,14 @@
 // continue into the next entry.
 // Per batch (depth_count_device, depth_write_device):
 //   1-2. variants.hip's flag / scan / list passes (contributing_list_device): the overlap records a live pair names, once each
-//   3. k_dep_count   one thread per listed record: depth_walk<CountSink> checks the whole CIGAR against the read's and the
-//                    entry's length and counts the M runs
+//   3. k_dep_count   one thread per listed record: walk_record (pileup_walk.h) checks the whole CIGAR against the read's and
+//                    the entry's length and hands the M runs to a DepSink<CountEmit>, which counts them
 //   4. one scan      lays out the slots
 //   5. the caller makes room (api_depth.hip, under the state's lock)
-//   6. k_dep_write   depth_walk<WriteSink>, the same function: per M run (begin << 1) and ((end + 1) << 1) | 1 into the pending keys
+//   6. k_dep_write   the same walk into a DepSink<WriteEmit>: per M run (begin << 1) and ((end + 1) << 1) | 1 into the pending keys
 // Compaction (depth_compact_device), when the pending keys pass the threshold and at every take:
 //   a. radix_sort of the pending keys, passes from the largest possible key
-//   b. run heads ignoring the low bit, a scan that numbers the runs, one thread per RUN: the begins sort before the ends, so a
+//   b. run heads ignoring the low bit (run_heads_device, run_starts_device: variants.hip's), a scan that numbers the runs, one thread per RUN: the begins sort before the ends, so a
 //      binary search for the split gives both counts whatever the run's length (70 001 equal intervals cost ~17 steps); the run
 //      becomes ONE record (key, begins - ends) with a 64-bit change
 //   c. merge with the compacted list: both lists are sorted and distinct, so a record's place is its own index plus its rank in
@@ -26,29 +26,22 @@
 // k_dep_scan_tiles, k_dep_depth), k_dep_flag marks the boundaries that start a row and combines rows, covered bases and the
 // largest depth per wavefront and then per block before one atomic each, a scan of the flags, and k_dep_rows resolves entry and
 // start by binary search in the entry offsets and takes the end from the next boundary.
-// Bounds: a record is walked only after entry < n_entries, read < n_reads and its CIGAR slice inside the pool held; the walk reads
-// nothing but the record, its CIGAR words and four offsets.  Every other kernel indexes arrays by thread number below their
-// length, by a scanned slot below the scan's total, or by a binary search's result inside [0, n).
-#include "common.h"
+// Bounds: the walk's are stated in pileup_walk.h; with a sink that wants no columns it reads nothing but the record, its CIGAR
+// words and four offsets.  Every other kernel indexes arrays by thread number below their length, by a scanned slot below the
+// scan's total, or by a binary search's result inside [0, n).
+#include "pileup_walk.h"
+#include "wave_add.h"
 #include "../../include/kslam_depth.h"
 
 namespace kslam {
 
 namespace {
 
-constexpr int DEP_BLOCK = 256;
+constexpr int DEP_BLOCK = PILEUP_BLOCK;
 constexpr int DEP_ITEMS = 4;
 constexpr int DEP_TILE = DEP_BLOCK * DEP_ITEMS;   // of the 64-bit scan
 constexpr int DEP_FLAG_ITEMS = 16;                // boundaries per thread of the flag pass
 
-__device__ inline uint64_t wave_sum64(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, o), hi = __shfl_xor((uint32_t)(v >> 32), o);
-    v += ((uint64_t)hi << 32) | lo;
-  }
-  return v;
-}
 __device__ inline uint32_t wave_max32(uint32_t v) {
 #pragma unroll
   for (int o = 32; o; o >>= 1) v = max(v, (uint32_t)__shfl_xor(v, o));
@@ -82,106 +75,54 @@ __device__ inline int64_t block_scan64(int64_t v, int64_t *lds, int64_t *total) 
   return v + before;
 }
 
-struct CountSink {
+struct CountEmit {
   uint32_t n = 0;
   __device__ void run(uint64_t, uint64_t) { n++; }
 };
-struct WriteSink {
+struct WriteEmit {
   uint64_t *out;
   __device__ void run(uint64_t begin, uint64_t end1) {
     *out++ = begin << 1;
     *out++ = (end1 << 1) | 1u;
   }
 };
-
-// false: the record is skipped (nothing was handed to the sink)
-template <class Sink>
-__device__ inline bool depth_walk(const kslam_overlap &o, const VariantInputs &in, Sink &sink) {
-  if (o.entry >= in.n_entries || o.cigar_len == 0 || o.ref_begin < 0) return false;
-  // (kslam_depth_add refuses these before anything is launched, and a lane's records do not have them)
-  if (o.read >= in.n_reads || o.cigar_off > in.n_cig || o.cigar_len > in.n_cig - o.cigar_off) return false;
-  const int64_t L = (int64_t)(in.roff[o.read + 1] - in.roff[o.read]);
-  const uint64_t gb = in.goff[o.entry];
-  const int64_t ref_len = (int64_t)(in.goff[o.entry + 1] - gb);
-  const uint32_t *__restrict__ cig = in.pool + o.cigar_off;
-  {   // the whole CIGAR against the read and the entry, before anything is emitted
-    int64_t rp = o.ref_begin, qp = o.query_begin > 0 ? o.query_begin : 0;
-    for (uint32_t k = 0; k < o.cigar_len; k++) {
-      const uint32_t c = cig[k], op = c & 15u;
-      const int64_t len = c >> 4;
-      if (op == 0) {
-        if (rp + len > ref_len || qp + len > L) return false;
-        rp += len;
-        qp += len;
-      } else if (op == 1) {
-        if (qp + len > L) return false;
-        qp += len;
-      } else if (op == 2) {
-        if (rp + len > ref_len) return false;
-        rp += len;
-      }
-    }
+// the walk's sink (pileup_walk.h): the M runs alone, no columns -- the walk reads nothing but the record, its CIGAR words and four
+// offsets.  A run's keys: the entry's first key is g_off[entry] + entry; the end is exclusive.
+template <class Emit>
+struct DepSink : Emit {
+  static constexpr bool COLUMNS = false, INSERTIONS = false;
+  __device__ void m_run(const kslam_overlap &o, const RecordFrame &f, int64_t rp, uint32_t len) {
+    const uint64_t begin = f.gb + o.entry + (uint64_t)rp;
+    Emit::run(begin, begin + len);
   }
-  const uint64_t base = gb + o.entry;   // the entry's first key
-  uint64_t rp = (uint64_t)o.ref_begin;
-  for (uint32_t k = 0; k < o.cigar_len; k++) {
-    const uint32_t c = cig[k], op = c & 15u, len = c >> 4;
-    if (op == 0) {
-      if (len) sink.run(base + rp, base + rp + len);
-      rp += len;
-    } else if (op == 2) {
-      rp += len;
-    }
-  }
-  return true;
-}
+  __device__ void d_run(const kslam_overlap &, const RecordFrame &, int64_t, uint32_t) {}
+};
 
 __global__ __launch_bounds__(DEP_BLOCK) void k_dep_count(VariantInputs in, const uint32_t *__restrict__ list, uint64_t n_list,
-                                                         uint32_t *__restrict__ cnt, unsigned long long *__restrict__ skipped) {
+                                                         uint32_t *__restrict__ cnt, unsigned long long *__restrict__ tallies) {
   const uint64_t x = (uint64_t)blockIdx.x * DEP_BLOCK + threadIdx.x;
   uint64_t skip = 0;
   if (x < n_list) {
     const kslam_overlap o = in.ov[list[x]];
-    CountSink sink;
-    if (!depth_walk(o, in, sink)) skip = 1;
+    DepSink<CountEmit> sink;
+    if (!walk_record(o, in, sink)) skip = 1;
     cnt[x] = sink.n;
   }
-  skip = wave_sum64(skip);
-  if ((threadIdx.x & 63) == 0 && skip) atomicAdd(skipped, (unsigned long long)skip);
+  skip = wave_sum(skip);
+  if ((threadIdx.x & 63) == 0 && skip) atomicAdd(tallies, (unsigned long long)skip);
 }
 
 __global__ __launch_bounds__(DEP_BLOCK) void k_dep_write(VariantInputs in, const uint32_t *__restrict__ list, uint64_t n_list,
                                                          const uint32_t *__restrict__ cnt, const uint64_t *__restrict__ off,
-                                                         uint64_t *__restrict__ pending) {
+                                                         uint64_t *pending) {
   const uint64_t x = (uint64_t)blockIdx.x * DEP_BLOCK + threadIdx.x;
   if (x >= n_list || cnt[x] == 0) return;   // (a skipped record counted nothing)
   const kslam_overlap o = in.ov[list[x]];
-  WriteSink sink{pending + 2 * off[x]};
-  (void)depth_walk(o, in, sink);
+  DepSink<WriteEmit> sink{{pending + 2 * off[x]}};
+  (void)walk_record(o, in, sink);
 }
 
 // ---- compaction ----
-
-// the first i in [lo, hi) with a[i] >= v (hi when there is none)
-__device__ inline uint64_t lower_bound(const uint64_t *__restrict__ a, uint64_t lo, uint64_t hi, uint64_t v) {
-  while (lo < hi) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (a[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-__global__ __launch_bounds__(DEP_BLOCK) void k_dep_heads(const uint64_t *__restrict__ key, uint64_t n, uint32_t *__restrict__ head) {
-  const uint64_t i = (uint64_t)blockIdx.x * DEP_BLOCK + threadIdx.x;
-  if (i < n) head[i] = (i == 0 || (key[i] >> 1) != (key[i - 1] >> 1)) ? 1u : 0u;
-}
-
-__global__ __launch_bounds__(DEP_BLOCK) void k_dep_starts(const uint32_t *__restrict__ head, const uint32_t *__restrict__ run, uint64_t n,
-                                                          uint32_t *__restrict__ starts) {
-  const uint64_t i = (uint64_t)blockIdx.x * DEP_BLOCK + threadIdx.x;
-  if (i < n && head[i]) starts[run[i]] = (uint32_t)i;
-}
 
 __global__ __launch_bounds__(DEP_BLOCK) void k_dep_reduce(const uint64_t *__restrict__ key, uint64_t n, const uint32_t *__restrict__ starts,
                                                           uint64_t n_runs, uint64_t *__restrict__ pkey, int64_t *__restrict__ pnet) {
@@ -322,8 +263,8 @@ __global__ __launch_bounds__(DEP_BLOCK) void k_dep_flag(const uint64_t *__restri
     }
     keep[i] = starts && d >= min_depth ? 1u : 0u;
   }
-  row = wave_sum64(row);
-  covered = wave_sum64(covered);
+  row = wave_sum(row);
+  covered = wave_sum(covered);
   deepest = wave_max32(deepest);
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
@@ -361,41 +302,11 @@ __global__ __launch_bounds__(DEP_BLOCK) void k_dep_rows(const uint64_t *__restri
   rows[at[i]] = out;
 }
 
-inline unsigned blocks(uint64_t n) { return (unsigned)((n + DEP_BLOCK - 1) / DEP_BLOCK); }
-
 }  // namespace
 
-void depth_count_device(const VariantInputs &in, DepthEmitWork &W, hipStream_t s) {
-  W.ms = 0;
-  W.n_list = W.n_iv = W.n_skipped = 0;
-  if (!W.ev[0])
-    for (auto &e : W.ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(W.ev[0], s));
-  const uint64_t n_list = contributing_list_device(in, W.flag, W.pos, W.list, W.scan_tmp, W.totals, s);
-  W.n_list = n_list;
-  if (!n_list) return;
-  uint64_t *d_tot = W.totals.as<uint64_t>();
-  W.cnt.ensure(n_list * sizeof(uint32_t));
-  W.off.ensure(n_list * sizeof(uint64_t));
-  hipLaunchKernelGGL(k_dep_count, dim3(blocks(n_list)), dim3(DEP_BLOCK), 0, s, in, W.list.as<uint32_t>(), n_list, W.cnt.as<uint32_t>(),
-                     reinterpret_cast<unsigned long long *>(d_tot + 3));
-  HIPCHK(hipGetLastError());
-  exclusive_scan_u32_to_u64(W.cnt.as<uint32_t>(), W.off.as<uint64_t>(), n_list, d_tot + 1, W.scan_tmp.p, s);
-  uint64_t h[4] = {0, 0, 0, 0};
-  read_back(h, d_tot, sizeof h, s);
-  W.n_iv = h[1];
-  W.n_skipped = h[3];
-}
+void depth_count_device(const VariantInputs &in, EmitWork &W, hipStream_t s) { emit_count_device(in, W, 1, k_dep_count, s); }
 
-void depth_write_device(const VariantInputs &in, DepthEmitWork &W, uint64_t *d_pending, hipStream_t s) {
-  if (W.n_list && W.n_iv)
-    hipLaunchKernelGGL(k_dep_write, dim3(blocks(W.n_list)), dim3(DEP_BLOCK), 0, s, in, W.list.as<uint32_t>(), W.n_list, W.cnt.as<uint32_t>(),
-                       W.off.as<uint64_t>(), d_pending);
-  HIPCHK(hipEventRecord(W.ev[1], s));
-  HIPCHK(hipGetLastError());
-  HIPCHK(stream_wait(s));
-  HIPCHK(hipEventElapsedTime(&W.ms, W.ev[0], W.ev[1]));
-}
+void depth_write_device(const VariantInputs &in, EmitWork &W, uint64_t *d_pending, hipStream_t s) { emit_write_device(in, W, k_dep_write, d_pending, s); }
 
 void depth_compact_device(DepthWork &T, DevBuf &pending, uint64_t n_pend, DevBuf &ckey, DevBuf &cnet, uint64_t *n_keys, uint64_t max_key, hipStream_t s) {
   if (!n_pend) return;
@@ -409,8 +320,7 @@ void depth_compact_device(DepthWork &T, DevBuf &pending, uint64_t n_pend, DevBuf
   T.scan_tmp.ensure(scan_tmp_bytes(std::max(n_pend, n_c + n_pend)));
   T.totals.ensure(4 * sizeof(uint64_t));
   uint64_t *d_tot = T.totals.as<uint64_t>();
-  hipLaunchKernelGGL(k_dep_heads, dim3(blocks(n_pend)), dim3(DEP_BLOCK), 0, s, key, n_pend, T.head.as<uint32_t>());
-  HIPCHK(hipGetLastError());
+  run_heads_device(key, n_pend, T.head.as<uint32_t>(), s);
   exclusive_scan_u32(T.head.as<uint32_t>(), T.run.as<uint32_t>(), n_pend, d_tot, T.scan_tmp.p, s);
   uint64_t n_p = 0;
   read_back(&n_p, d_tot, sizeof n_p, s);
@@ -424,13 +334,12 @@ void depth_compact_device(DepthWork &T, DevBuf &pending, uint64_t n_pend, DevBuf
   T.mnet.ensure(n_m * sizeof(int64_t));
   T.keep.ensure(n_m * sizeof(uint32_t));
   T.at.ensure(n_m * sizeof(uint32_t));
-  hipLaunchKernelGGL(k_dep_starts, dim3(blocks(n_pend)), dim3(DEP_BLOCK), 0, s, T.head.as<uint32_t>(), T.run.as<uint32_t>(), n_pend,
-                     T.starts.as<uint32_t>());
-  hipLaunchKernelGGL(k_dep_reduce, dim3(blocks(n_p)), dim3(DEP_BLOCK), 0, s, key, n_pend, T.starts.as<uint32_t>(), n_p, T.pkey.as<uint64_t>(),
+  run_starts_device(T.head.as<uint32_t>(), T.run.as<uint32_t>(), n_pend, T.starts.as<uint32_t>(), s);
+  hipLaunchKernelGGL(k_dep_reduce, dim3(pileup_blocks(n_p)), dim3(DEP_BLOCK), 0, s, key, n_pend, T.starts.as<uint32_t>(), n_p, T.pkey.as<uint64_t>(),
                      T.pnet.as<int64_t>());
-  hipLaunchKernelGGL(k_dep_merge, dim3(blocks(n_m)), dim3(DEP_BLOCK), 0, s, ckey.as<uint64_t>(), cnet.as<int64_t>(), n_c, T.pkey.as<uint64_t>(),
+  hipLaunchKernelGGL(k_dep_merge, dim3(pileup_blocks(n_m)), dim3(DEP_BLOCK), 0, s, ckey.as<uint64_t>(), cnet.as<int64_t>(), n_c, T.pkey.as<uint64_t>(),
                      T.pnet.as<int64_t>(), n_p, T.mkey.as<uint64_t>(), T.mnet.as<int64_t>());
-  hipLaunchKernelGGL(k_dep_keep, dim3(blocks(n_m)), dim3(DEP_BLOCK), 0, s, T.mkey.as<uint64_t>(), T.mnet.as<int64_t>(), n_m, T.keep.as<uint32_t>());
+  hipLaunchKernelGGL(k_dep_keep, dim3(pileup_blocks(n_m)), dim3(DEP_BLOCK), 0, s, T.mkey.as<uint64_t>(), T.mnet.as<int64_t>(), n_m, T.keep.as<uint32_t>());
   HIPCHK(hipGetLastError());
   exclusive_scan_u32(T.keep.as<uint32_t>(), T.at.as<uint32_t>(), n_m, d_tot + 1, T.scan_tmp.p, s);
   uint64_t n_new = 0;
@@ -438,7 +347,7 @@ void depth_compact_device(DepthWork &T, DevBuf &pending, uint64_t n_pend, DevBuf
   T.nkey.ensure((n_new + 1) * sizeof(uint64_t));
   T.nnet.ensure((n_new + 1) * sizeof(int64_t));
   if (n_new)
-    hipLaunchKernelGGL(k_dep_scatter, dim3(blocks(n_m)), dim3(DEP_BLOCK), 0, s, T.mkey.as<uint64_t>(), T.mnet.as<int64_t>(), n_m, T.keep.as<uint32_t>(),
+    hipLaunchKernelGGL(k_dep_scatter, dim3(pileup_blocks(n_m)), dim3(DEP_BLOCK), 0, s, T.mkey.as<uint64_t>(), T.mnet.as<int64_t>(), n_m, T.keep.as<uint32_t>(),
                        T.at.as<uint32_t>(), T.nkey.as<uint64_t>(), T.nnet.as<int64_t>());
   HIPCHK(hipGetLastError());
   HIPCHK(stream_wait(s));
@@ -470,7 +379,7 @@ void depth_take_device(DepthWork &T, const uint64_t *d_ckey, const int64_t *d_cn
   read_back(out, d_tot, 4 * sizeof(uint64_t), s);
   if (!out[3]) return;
   T.rows.ensure(out[3] * sizeof(kslam_depth_row));
-  hipLaunchKernelGGL(k_dep_rows, dim3(blocks(n)), dim3(DEP_BLOCK), 0, s, d_ckey, T.depth.as<uint32_t>(), n, T.keep.as<uint32_t>(), T.at.as<uint32_t>(),
+  hipLaunchKernelGGL(k_dep_rows, dim3(pileup_blocks(n)), dim3(DEP_BLOCK), 0, s, d_ckey, T.depth.as<uint32_t>(), n, T.keep.as<uint32_t>(), T.at.as<uint32_t>(),
                      d_goff, n_entries, T.rows.as<kslam_depth_row>());
   HIPCHK(hipGetLastError());
 }

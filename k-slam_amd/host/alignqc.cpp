@@ -9,11 +9,12 @@
 #include <vector>
 
 #include "../../include/kslam_alignqc.h"
-#include "batch_check.hpp"
+#include "pileup_walk.hpp"
 #include "workers.hpp"
 
 namespace {
 using namespace kslam_host;
+using namespace kslam_pileup;
 constexpr uint64_t NQ = KSLAM_ALIGN_QC_QUAL_COLS, NC = KSLAM_ALIGN_QC_CYCLE_COLS, NL = KSLAM_ALIGN_QC_LEN_BINS, NN = KSLAM_ALIGN_QC_NM_BINS,
                    NI = KSLAM_ALIGN_QC_IDENTITY_BINS, NS = KSLAM_ALIGN_QC_INSERT_BINS, NSC = KSLAM_ALIGN_QC_SCALARS;
 
@@ -74,38 +75,7 @@ void point_into(kslam_align_qc_tables *t) {
   }
 }
 
-inline int acgt(uint8_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
-inline uint8_t complement(uint8_t c) {
-  switch (c) {
-    case 'A': return 'T';
-    case 'C': return 'G';
-    case 'G': return 'C';
-    case 'T': return 'A';
-    default: return c;   // N, lower case, anything else: as it is
-  }
-}
 inline uint64_t qual_col(uint8_t q) { return q >= 33 && q <= 126 ? (uint64_t)(q - 33) : 94; }
-
-// does the record's CIGAR stay inside its read and its entry?  (the whole CIGAR, before anything is counted)
-bool fits(const kslam_overlap &o, const uint32_t *pool, int64_t read_len, int64_t ref_len) {
-  int64_t rp = o.ref_begin, qp = o.query_begin > 0 ? o.query_begin : 0;
-  for (uint32_t k = 0; k < o.cigar_len; k++) {
-    const uint32_t c = pool[o.cigar_off + k], op = c & 15u;
-    const int64_t len = c >> 4;
-    if (op == 0) {
-      if (rp + len > ref_len || qp + len > read_len) return false;
-      rp += len;
-      qp += len;
-    } else if (op == 1) {
-      if (qp + len > read_len) return false;
-      qp += len;
-    } else if (op == 2) {
-      if (rp + len > ref_len) return false;
-      rp += len;
-    }
-  }
-  return true;
-}
 
 std::string ratio(uint64_t num, uint64_t den) {
   char buf[64];
@@ -230,46 +200,20 @@ extern "C" kslam_status kslam_tail_align_qc(const char *entry_bases, const uint6
     if (paired && (n_reads & 1)) fail(KSLAM_ERR_ARG, "a paired batch holds an even number of reads");
     if (n_reads && read_offsets[n_reads] && !read_bases) fail(KSLAM_ERR_ARG, "null argument");
     if (n_entries && entry_offsets[n_entries] && !entry_bases) fail(KSLAM_ERR_ARG, "null argument");
-    // ---- the contributing set, and the pairs ----
-    std::vector<uint8_t> named(n_overlaps < (1ull << 32) ? n_overlaps : 0, 0);   // (2^32 or more: refused before anything is named)
-    const std::string fault = kslam_batch::check({overlaps, n_overlaps, n_cigar, read_offsets, n_reads, read_pairs, n_read_pairs, pairs, n_pairs},
-                                                 kslam_batch::Level::records, nullptr, [&](uint32_t idx) { named[idx] = 1; });
-    if (!fault.empty()) fail(KSLAM_ERR_ARG, fault);
     const uint64_t nw = KSLAM_ALIGN_QC_WORDS(C);
     block = (uint64_t *)calloc(nw, sizeof(uint64_t));
     if (!block) fail(KSLAM_ERR_OOM, "out of host memory");
-    uint64_t *insert = block + 6;
-    for (uint64_t g = 0; g < n_read_pairs; g++) {
-      const kslam_read_pair &rp = read_pairs[g];
-      if (rp.count) block[0]++;
-      for (uint64_t k = rp.first; k < rp.first + rp.count; k++) {
-        const bool h1 = pairs[k].r1 != KSLAM_NO_OVERLAP, h2 = pairs[k].r2 != KSLAM_NO_OVERLAP;
-        if (h1 && h2) {
-          block[1]++;
-          block[4] += pairs[k].insert_size;
-          insert[pairs[k].insert_size < NS - 1 ? pairs[k].insert_size : NS - 1]++;
-        } else if (h1) {
-          block[2]++;
-        } else if (h2) {
-          block[3]++;
-        }
-      }
-    }
-    // ---- the walk ----
+    // ---- the walk of the contributing set ----
     const uint64_t half = n_reads / 2;
-    for (uint64_t i = 0; i < n_overlaps; i++) {
-      if (!named[i]) continue;
-      const kslam_overlap &o = overlaps[i];
+    const std::string fault = for_each_named_record({overlaps, n_overlaps, n_cigar, read_offsets, n_reads, read_pairs, n_read_pairs, pairs, n_pairs}, cigar_pool,
+                                                    entry_offsets, n_entries, [&](const kslam_overlap &o, int64_t L, int64_t, bool holds) {
       const StreamWords S(block, C, paired && o.read >= half ? 1 : 0);
       S.w[0]++;
       if (!read_quality) S.w[3]++;
-      if (o.entry >= n_entries || o.cigar_len == 0 || o.ref_begin < 0) { S.w[2]++; continue; }
+      if (!holds) { S.w[2]++; return; }
       const uint8_t *ref = (const uint8_t *)entry_bases + entry_offsets[o.entry];
-      const int64_t ref_len = (int64_t)(entry_offsets[o.entry + 1] - entry_offsets[o.entry]);
       const uint8_t *read = (const uint8_t *)read_bases + read_offsets[o.read];
       const uint8_t *qual = read_quality ? (const uint8_t *)read_quality + read_offsets[o.read] : nullptr;
-      const int64_t L = (int64_t)(read_offsets[o.read + 1] - read_offsets[o.read]);
-      if (!fits(o, cigar_pool, L, ref_len)) { S.w[2]++; continue; }
       const bool rc = o.revcomp != 0;
       if (rc) S.w[1]++;
       auto cycle_of = [&](int64_t q) { return rc ? L - 1 - q : q; };
@@ -326,6 +270,25 @@ extern "C" kslam_status kslam_tail_align_qc(const char *entry_bases, const uint6
       const uint64_t edits = miss + ins + del, den = compared + ins + del;
       S.nm[edits < NN - 1 ? edits : NN - 1]++;
       if (den) S.identity[100 * (compared - miss) / den]++;
+    });
+    if (!fault.empty()) fail(KSLAM_ERR_ARG, fault);
+    // ---- the pairs (the check has passed: every live pair lies inside the arrays) ----
+    uint64_t *insert = block + 6;
+    for (uint64_t g = 0; g < n_read_pairs; g++) {
+      const kslam_read_pair &rp = read_pairs[g];
+      if (rp.count) block[0]++;
+      for (uint64_t k = rp.first; k < rp.first + rp.count; k++) {
+        const bool h1 = pairs[k].r1 != KSLAM_NO_OVERLAP, h2 = pairs[k].r2 != KSLAM_NO_OVERLAP;
+        if (h1 && h2) {
+          block[1]++;
+          block[4] += pairs[k].insert_size;
+          insert[pairs[k].insert_size < NS - 1 ? pairs[k].insert_size : NS - 1]++;
+        } else if (h1) {
+          block[2]++;
+        } else if (h2) {
+          block[3]++;
+        }
+      }
     }
     tables->max_cycles = (uint32_t)C;
     tables->paired = paired ? 1 : 0;

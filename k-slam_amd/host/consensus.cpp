@@ -12,43 +12,12 @@
 #include <vector>
 
 #include "../../include/kslam_consensus.h"
-#include "batch_check.hpp"
+#include "pileup_walk.hpp"
 #include "workers.hpp"
 
 namespace {
 using namespace kslam_host;
-
-inline int acgt(uint8_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
-inline uint8_t complement(uint8_t c) {
-  switch (c) {
-    case 'A': return 'T';
-    case 'C': return 'G';
-    case 'G': return 'C';
-    case 'T': return 'A';
-    default: return c;   // N, lower case, anything else: as it is
-  }
-}
-
-// does the record's CIGAR stay inside its read and its entry?  (the whole CIGAR, before anything is emitted)
-bool fits(const kslam_overlap &o, const uint32_t *pool, int64_t read_len, int64_t ref_len) {
-  int64_t rp = o.ref_begin, qp = o.query_begin > 0 ? o.query_begin : 0;
-  for (uint32_t k = 0; k < o.cigar_len; k++) {
-    const uint32_t c = pool[o.cigar_off + k], op = c & 15u;
-    const int64_t len = c >> 4;
-    if (op == 0) {
-      if (rp + len > ref_len || qp + len > read_len) return false;
-      rp += len;
-      qp += len;
-    } else if (op == 1) {
-      if (qp + len > read_len) return false;
-      qp += len;
-    } else if (op == 2) {
-      if (rp + len > ref_len) return false;
-      rp += len;
-    }
-  }
-  return true;
-}
+using namespace kslam_pileup;
 
 struct Column { uint32_t m = 0, dl = 0, ev[5] = {0, 0, 0, 0, 0}; };
 
@@ -78,28 +47,15 @@ extern "C" kslam_status kslam_tail_consensus(const char *entry_bases, const uint
     check_params(params);
     if (n_reads && read_offsets[n_reads] && !read_bases) fail(KSLAM_ERR_ARG, "null argument");
     if (n_entries && entry_offsets[n_entries] && !entry_bases) fail(KSLAM_ERR_ARG, "null argument");
-    // ---- the contributing set: every overlap record a live alignment pair names, once ----
-    std::vector<uint8_t> named(n_overlaps < (1ull << 32) ? n_overlaps : 0, 0);   // (2^32 or more: refused before anything is named)
-    const std::string fault = kslam_batch::check({overlaps, n_overlaps, n_cigar, read_offsets, n_reads, read_pairs, n_read_pairs, pairs, n_pairs},
-                                                 kslam_batch::Level::records, nullptr, [&](uint32_t idx) { named[idx] = 1; });
-    if (!fault.empty()) fail(KSLAM_ERR_ARG, fault);
-    // ---- the walk: dense counters for the entries it touches ----
+    // ---- the walk of the contributing set: dense counters for the entries it touches ----
     std::vector<std::vector<Column>> cols(n_entries);
     std::map<std::tuple<uint32_t, uint32_t, uint32_t, std::string>, uint64_t> ins;   // (entry, anchor, len, bases): ascending as the device's keys
     std::string query;
-    for (uint64_t i = 0; i < n_overlaps; i++) {
-      if (!named[i]) continue;
-      stats->n_records++;
-      const kslam_overlap &o = overlaps[i];
-      if (o.entry >= n_entries || o.cigar_len == 0 || o.ref_begin < 0) { stats->n_skipped++; continue; }
-      const int64_t ref_len = (int64_t)(entry_offsets[o.entry + 1] - entry_offsets[o.entry]);
+    const std::string fault = for_each_contributing_record({overlaps, n_overlaps, n_cigar, read_offsets, n_reads, read_pairs, n_read_pairs, pairs, n_pairs},
+                                                           cigar_pool, entry_offsets, n_entries, stats->n_records, stats->n_skipped,
+                                                           [&](const kslam_overlap &o, int64_t L, int64_t ref_len) {
       const uint8_t *ref = (const uint8_t *)entry_bases + entry_offsets[o.entry];
-      const uint8_t *read = (const uint8_t *)read_bases + read_offsets[o.read];
-      const int64_t L = (int64_t)(read_offsets[o.read + 1] - read_offsets[o.read]);
-      if (!fits(o, cigar_pool, L, ref_len)) { stats->n_skipped++; continue; }
-      query.assign((const char *)read, (size_t)L);
-      if (o.revcomp)
-        for (int64_t j = 0; j < L; j++) query[(size_t)j] = (char)complement(read[L - 1 - j]);
+      oriented_query(query, (const uint8_t *)read_bases + read_offsets[o.read], L, o.revcomp != 0);
       std::vector<Column> &col = cols[o.entry];
       int64_t rp = o.ref_begin, qp = o.query_begin > 0 ? o.query_begin : 0;
       for (uint32_t k = 0; k < o.cigar_len; k++) {
@@ -142,7 +98,8 @@ extern "C" kslam_status kslam_tail_consensus(const char *entry_bases, const uint
           rp += len;
         }
       }
-    }
+    });
+    if (!fault.empty()) fail(KSLAM_ERR_ARG, fault);
     // ---- the call ----
     const uint64_t min_covered = params->min_covered ? params->min_covered : 1;
     std::vector<kslam_consensus_row> out;

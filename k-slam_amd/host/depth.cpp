@@ -10,33 +10,12 @@
 #include <vector>
 
 #include "../../include/kslam_depth.h"
-#include "batch_check.hpp"
+#include "pileup_walk.hpp"
 #include "workers.hpp"
 
 namespace {
 using namespace kslam_host;
-
-// does the record's CIGAR stay inside its read and its entry?  (the whole CIGAR, before anything is emitted)
-bool fits(const kslam_overlap &o, const uint32_t *pool, int64_t read_len, int64_t ref_len) {
-  int64_t rp = o.ref_begin, qp = o.query_begin > 0 ? o.query_begin : 0;
-  for (uint32_t k = 0; k < o.cigar_len; k++) {
-    const uint32_t c = pool[o.cigar_off + k], op = c & 15u;
-    const int64_t len = c >> 4;
-    if (op == 0) {
-      if (rp + len > ref_len || qp + len > read_len) return false;
-      rp += len;
-      qp += len;
-    } else if (op == 1) {
-      if (qp + len > read_len) return false;
-      qp += len;
-    } else if (op == 2) {
-      if (rp + len > ref_len) return false;
-      rp += len;
-    }
-  }
-  return true;
-}
-
+using namespace kslam_pileup;
 }  // namespace
 
 extern "C" kslam_status kslam_tail_depth(const uint64_t *entry_offsets, uint64_t n_entries, const kslam_overlap *overlaps, uint64_t n_overlaps,
@@ -51,21 +30,12 @@ extern "C" kslam_status kslam_tail_depth(const uint64_t *entry_offsets, uint64_t
         (n_reads && !read_offsets) || (n_read_pairs && !read_pairs) || (n_pairs && !pairs))
       fail(KSLAM_ERR_ARG, "null argument");
     memset(stats, 0, sizeof *stats);
-    // ---- the contributing set: every overlap record a live alignment pair names, once ----
-    std::vector<uint8_t> named(n_overlaps < (1ull << 32) ? n_overlaps : 0, 0);   // (2^32 or more: refused before anything is named)
-    const std::string fault = kslam_batch::check({overlaps, n_overlaps, n_cigar, read_offsets, n_reads, read_pairs, n_read_pairs, pairs, n_pairs},
-                                                 kslam_batch::Level::records, nullptr, [&](uint32_t idx) { named[idx] = 1; });
-    if (!fault.empty()) fail(KSLAM_ERR_ARG, fault);
-    // ---- the walk: per entry, the change of depth at each position (position `length` closes what reaches the last base) ----
+    // ---- the walk of the contributing set: per entry, the change of depth at each position (position `length` closes what
+    // reaches the last base) ----
     std::vector<std::map<uint64_t, int64_t>> change(n_entries);
-    for (uint64_t i = 0; i < n_overlaps; i++) {
-      if (!named[i]) continue;
-      stats->n_records++;
-      const kslam_overlap &o = overlaps[i];
-      if (o.entry >= n_entries || o.cigar_len == 0 || o.ref_begin < 0) { stats->n_skipped++; continue; }
-      const int64_t ref_len = (int64_t)(entry_offsets[o.entry + 1] - entry_offsets[o.entry]);
-      const int64_t L = (int64_t)(read_offsets[o.read + 1] - read_offsets[o.read]);
-      if (!fits(o, cigar_pool, L, ref_len)) { stats->n_skipped++; continue; }
+    const std::string fault = for_each_contributing_record({overlaps, n_overlaps, n_cigar, read_offsets, n_reads, read_pairs, n_read_pairs, pairs, n_pairs},
+                                                           cigar_pool, entry_offsets, n_entries, stats->n_records, stats->n_skipped,
+                                                           [&](const kslam_overlap &o, int64_t, int64_t) {
       uint64_t rp = (uint64_t)o.ref_begin;
       for (uint32_t k = 0; k < o.cigar_len; k++) {
         const uint32_t c = cigar_pool[o.cigar_off + k], op = c & 15u, len = c >> 4;
@@ -80,7 +50,8 @@ extern "C" kslam_status kslam_tail_depth(const uint64_t *entry_offsets, uint64_t
           rp += len;
         }
       }
-    }
+    });
+    if (!fault.empty()) fail(KSLAM_ERR_ARG, fault);
     const uint64_t floor = min_depth ? min_depth : 1;
     std::vector<kslam_depth_row> out;
     for (uint64_t e = 0; e < n_entries; e++) {

@@ -11,45 +11,14 @@
 #include <vector>
 
 #include "../../include/kslam_variants.h"
-#include "batch_check.hpp"
+#include "pileup_walk.hpp"
 #include "workers.hpp"
 
 namespace {
 using namespace kslam_host;
-
-inline bool is_acgt(uint8_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
-inline uint8_t complement(uint8_t c) {
-  switch (c) {
-    case 'A': return 'T';
-    case 'C': return 'G';
-    case 'G': return 'C';
-    case 'T': return 'A';
-    default: return c;   // N, lower case, anything else: as it is
-  }
-}
+using namespace kslam_pileup;
 
 struct Counts { uint32_t fwd = 0, rev = 0; };
-
-// does the record's CIGAR stay inside its read and its entry?  (the whole CIGAR, before anything is emitted)
-bool fits(const kslam_overlap &o, const uint32_t *pool, int64_t read_len, int64_t ref_len) {
-  int64_t rp = o.ref_begin, qp = o.query_begin > 0 ? o.query_begin : 0;
-  for (uint32_t k = 0; k < o.cigar_len; k++) {
-    const uint32_t c = pool[o.cigar_off + k], op = c & 15u;
-    const int64_t len = c >> 4;
-    if (op == 0) {
-      if (rp + len > ref_len || qp + len > read_len) return false;
-      rp += len;
-      qp += len;
-    } else if (op == 1) {
-      if (qp + len > read_len) return false;
-      qp += len;
-    } else if (op == 2) {
-      if (rp + len > ref_len) return false;
-      rp += len;
-    }
-  }
-  return true;
-}
 
 }  // namespace
 
@@ -68,28 +37,15 @@ extern "C" kslam_status kslam_tail_variants(const char *entry_bases, const uint6
     memset(stats, 0, sizeof *stats);
     if (n_reads && read_offsets[n_reads] && !read_bases) fail(KSLAM_ERR_ARG, "null argument");
     if (n_entries && entry_offsets[n_entries] && !entry_bases) fail(KSLAM_ERR_ARG, "null argument");
-    // ---- the contributing set: every overlap record a live alignment pair names, once ----
-    std::vector<uint8_t> named(n_overlaps < (1ull << 32) ? n_overlaps : 0, 0);   // (2^32 or more: refused before anything is named)
-    const std::string fault = kslam_batch::check({overlaps, n_overlaps, n_cigar, read_offsets, n_reads, read_pairs, n_read_pairs, pairs, n_pairs},
-                                                 kslam_batch::Level::records, nullptr, [&](uint32_t idx) { named[idx] = 1; });
-    if (!fault.empty()) fail(KSLAM_ERR_ARG, fault);
-    // ---- the walk ----
+    // ---- the walk of the contributing set ----
     std::map<std::tuple<uint32_t, uint32_t, uint8_t>, Counts> sites;          // (entry, pos, alt): ascending as the rows do
     std::vector<std::vector<uint32_t>> begins(n_entries), ends(n_entries);     // per entry: the closed M intervals
     std::string query;
-    for (uint64_t i = 0; i < n_overlaps; i++) {
-      if (!named[i]) continue;
-      stats->n_records++;
-      const kslam_overlap &o = overlaps[i];
-      if (o.entry >= n_entries || o.cigar_len == 0 || o.ref_begin < 0) { stats->n_skipped++; continue; }
+    const std::string fault = for_each_contributing_record({overlaps, n_overlaps, n_cigar, read_offsets, n_reads, read_pairs, n_read_pairs, pairs, n_pairs},
+                                                           cigar_pool, entry_offsets, n_entries, stats->n_records, stats->n_skipped,
+                                                           [&](const kslam_overlap &o, int64_t L, int64_t) {
       const uint8_t *ref = (const uint8_t *)entry_bases + entry_offsets[o.entry];
-      const int64_t ref_len = (int64_t)(entry_offsets[o.entry + 1] - entry_offsets[o.entry]);
-      const uint8_t *read = (const uint8_t *)read_bases + read_offsets[o.read];
-      const int64_t L = (int64_t)(read_offsets[o.read + 1] - read_offsets[o.read]);
-      if (!fits(o, cigar_pool, L, ref_len)) { stats->n_skipped++; continue; }
-      query.assign((const char *)read, (size_t)L);
-      if (o.revcomp)
-        for (int64_t j = 0; j < L; j++) query[(size_t)j] = (char)complement(read[L - 1 - j]);
+      oriented_query(query, (const uint8_t *)read_bases + read_offsets[o.read], L, o.revcomp != 0);
       int64_t rp = o.ref_begin, qp = o.query_begin > 0 ? o.query_begin : 0;
       for (uint32_t k = 0; k < o.cigar_len; k++) {
         const uint32_t c = cigar_pool[o.cigar_off + k], op = c & 15u;
@@ -102,7 +58,7 @@ extern "C" kslam_status kslam_tail_variants(const char *entry_bases, const uint6
           }
           for (int64_t j = 0; j < len; j++) {
             const uint8_t r = ref[rp + j], q = (uint8_t)query[(size_t)(qp + j)];
-            if (is_acgt(r) && is_acgt(q) && r != q) {
+            if (acgt(r) < 4 && acgt(q) < 4 && r != q) {
               Counts &s = sites[std::make_tuple(o.entry, (uint32_t)(rp + j), q)];
               (o.revcomp ? s.rev : s.fwd)++;
               stats->n_events++;
@@ -116,7 +72,8 @@ extern "C" kslam_status kslam_tail_variants(const char *entry_bases, const uint6
           rp += len;
         }
       }
-    }
+    });
+    if (!fault.empty()) fail(KSLAM_ERR_ARG, fault);
     stats->n_sites = sites.size();
     for (auto &v : begins) std::sort(v.begin(), v.end());
     for (auto &v : ends) std::sort(v.begin(), v.end());
