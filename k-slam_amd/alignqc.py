@@ -3,7 +3,6 @@ spectrum, indel lengths, edit distance and identity per alignment, insert sizes)
 JSON writer and a parser for the file."""
 import ctypes as C
 import json
-import os
 
 import numpy as np
 
@@ -112,7 +111,7 @@ def pack(tables):
 
 
 def _tables_out(t):
-    block = np.frombuffer(C.string_at(t.block, 8 * int(t.n_words)), dtype=np.uint64)
+    block = _T.rows_at(t.block, int(t.n_words), np.dtype(np.uint64))
     return unpack(block, int(t.max_cycles), t.paired)
 
 
@@ -197,18 +196,7 @@ def write(tables, fd):
 
 def report_bytes(tables):
     """the file as bytes (through a temporary descriptor)"""
-    fd = os.memfd_create("kslam_align_qc")
-    try:
-        write(tables, fd)
-        os.lseek(fd, 0, os.SEEK_SET)
-        out = b""
-        while True:
-            piece = os.read(fd, 1 << 20)
-            if not piece:
-                return out
-            out += piece
-    finally:
-        os.close(fd)
+    return _T.fd_bytes("kslam_align_qc", lambda fd: write(tables, fd))
 
 
 def stream_set_align_qc(ctx, fd, max_cycles=0):

@@ -2,7 +2,6 @@
 from the pile-up of each batch (one row and one sequence per reported entry), its host twin, the FASTA writer and a parser for
 the file."""
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -100,7 +99,7 @@ def set_slice(ctx, slice_positions=0):
 
 
 def _result(rows, n, seq, st):
-    out = np.frombuffer(C.string_at(rows.value, n.value * ROW_DT.itemsize), dtype=ROW_DT).copy() if n.value else np.zeros(0, dtype=ROW_DT)
+    out = _T.rows_at(rows.value, n.value, ROW_DT)
     total = int(out["seq_off"][-1] + out["seq_len"][-1]) if n.value else 0
     # (ctypes.string_at takes its size as a C int: the sequences of a large database are longer)
     return out, (bytes((C.c_char * total).from_address(seq.value)) if total else b""), st.as_dict()
@@ -157,18 +156,7 @@ def write(index, rows, seq, fd):
 
 def report_bytes(index, rows, seq):
     """the FASTA file as bytes (through a pipe-free temporary descriptor)"""
-    fd = os.memfd_create("kslam_consensus")
-    try:
-        write(index, rows, seq, fd)
-        os.lseek(fd, 0, os.SEEK_SET)
-        out = b""
-        while True:
-            piece = os.read(fd, 1 << 20)
-            if not piece:
-                return out
-            out += piece
-    finally:
-        os.close(fd)
+    return _T.fd_bytes("kslam_consensus", lambda fd: write(index, rows, seq, fd))
 
 
 def stream_set_consensus(ctx, fd, min_depth=1, call_permille=500, fill=FILL_N, min_covered=1):

@@ -1,7 +1,6 @@
 """ctypes plumbing for include/kslam_coverage.h: the per-entry coverage table accumulated on the GPU (alignments, unique read
 pairs, aligned and covered bases), its host twin, the report writer and a parser for the report."""
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -73,7 +72,7 @@ def take(ctx):
     L = lib()
     rows, n, skipped = C.c_void_p(), C.c_uint64(), C.c_uint64()
     ctx._chk(L.kslam_coverage_take(ctx._h, C.byref(rows), C.byref(n), C.byref(skipped)))
-    out = np.frombuffer(C.string_at(rows.value, n.value * ROW_DT.itemsize), dtype=ROW_DT).copy() if n.value else np.zeros(0, dtype=ROW_DT)
+    out = _T.rows_at(rows.value, n.value, ROW_DT)
     L.kslam_free_pinned(ctx._h, rows)
     return out, int(skipped.value)
 
@@ -111,18 +110,7 @@ def write_report(index, rows, fd):
 
 def report_bytes(index, rows):
     """the report as bytes (through a pipe-free temporary descriptor)"""
-    fd = os.memfd_create("kslam_coverage")
-    try:
-        write_report(index, rows, fd)
-        os.lseek(fd, 0, os.SEEK_SET)
-        out = b""
-        while True:
-            piece = os.read(fd, 1 << 20)
-            if not piece:
-                return out
-            out += piece
-    finally:
-        os.close(fd)
+    return _T.fd_bytes("kslam_coverage", lambda fd: write_report(index, rows, fd))
 
 
 def stream_set_coverage(ctx, fd):

@@ -1,7 +1,6 @@
 """ctypes plumbing for include/kslam_depth.h: the depth along every entry accumulated on the GPU (one row per maximal run of equal
 depth), its host twin, the bedGraph writer and a parser for the file."""
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -59,13 +58,6 @@ def _arrays(overlaps, cigar_pool, read_offsets, read_pairs, pairs):
     return (ov, cg, ro, rp, pr), (ptr(ov), len(ov), ptr(cg), len(cg), ro.ctypes.data if n_reads else None, n_reads, ptr(rp), len(rp), ptr(pr), len(pr))
 
 
-def _rows_at(address, n):
-    """a copy of the n rows at `address` (ctypes.string_at takes its size as a C int: not enough for 2^27 rows and more)"""
-    if not n:
-        return np.zeros(0, dtype=ROW_DT)
-    return np.frombuffer((C.c_char * (n * ROW_DT.itemsize)).from_address(address), dtype=ROW_DT).copy()
-
-
 def set_depth(ctx, on=True):
     """kslam_set_depth: needs an index, ctx.set_pairing and a context with report_cigar; off frees the state"""
     ctx._chk(lib().kslam_set_depth(ctx._h, int(on)))
@@ -98,7 +90,7 @@ def take(ctx, min_depth=1):
     L = lib()
     rows, n, st = C.c_void_p(), C.c_uint64(), Stats()
     ctx._chk(L.kslam_depth_take(ctx._h, int(min_depth), C.byref(rows), C.byref(n), C.byref(st)))
-    out = _rows_at(rows.value, n.value)
+    out = _T.rows_at(rows.value, n.value, ROW_DT)
     L.kslam_free_pinned(ctx._h, rows)
     return out, st.as_dict()
 
@@ -118,7 +110,7 @@ def tail_depth(entry_offsets, overlaps, cigar_pool, read_offsets, read_pairs, pa
     rows, n, st = C.c_void_p(), C.c_uint64(), Stats()
     n_entries = max(len(go) - 1, 0)
     _T._chk(L.kslam_tail_depth(go.ctypes.data if n_entries else None, n_entries, *args, int(min_depth), C.byref(rows), C.byref(n), C.byref(st)))
-    out = _rows_at(rows.value, n.value)
+    out = _T.rows_at(rows.value, n.value, ROW_DT)
     L.kslam_free(rows)
     return out, st.as_dict()
 
@@ -131,18 +123,7 @@ def write(index, rows, fd):
 
 def report_bytes(index, rows):
     """the bedGraph file as bytes (through a pipe-free temporary descriptor)"""
-    fd = os.memfd_create("kslam_depth")
-    try:
-        write(index, rows, fd)
-        os.lseek(fd, 0, os.SEEK_SET)
-        out = b""
-        while True:
-            piece = os.read(fd, 1 << 20)
-            if not piece:
-                return out
-            out += piece
-    finally:
-        os.close(fd)
+    return _T.fd_bytes("kslam_depth", lambda fd: write(index, rows, fd))
 
 
 def stream_set_depth(ctx, fd, min_depth=1):

@@ -1,7 +1,6 @@
 """ctypes plumbing for include/kslam_genes.h: the per-gene abundance table counted on the GPU (alignments, unique read pairs and
 overlapping bases per annotated gene), its host twin, the table writer and a parser for the file."""
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -112,7 +111,7 @@ def take(ctx):
     L = lib()
     rows, n, st = C.c_void_p(), C.c_uint64(), Stats()
     ctx._chk(L.kslam_genes_take(ctx._h, C.byref(rows), C.byref(n), C.byref(st)))
-    out = np.frombuffer(C.string_at(rows.value, n.value * ROW_DT.itemsize), dtype=ROW_DT).copy() if n.value else np.zeros(0, dtype=ROW_DT)
+    out = _T.rows_at(rows.value, n.value, ROW_DT)
     L.kslam_free_pinned(ctx._h, rows)
     return out, st.as_dict()
 
@@ -152,18 +151,7 @@ def write(index, rows, fd):
 
 def table_bytes(index, rows):
     """the file as bytes (through a pipe-free temporary descriptor)"""
-    fd = os.memfd_create("kslam_genes")
-    try:
-        write(index, rows, fd)
-        os.lseek(fd, 0, os.SEEK_SET)
-        out = b""
-        while True:
-            piece = os.read(fd, 1 << 20)
-            if not piece:
-                return out
-            out += piece
-    finally:
-        os.close(fd)
+    return _T.fd_bytes("kslam_genes", lambda fd: write(index, rows, fd))
 
 
 def stream_set_genes(ctx, fd):

@@ -1,7 +1,6 @@
 """ctypes plumbing for include/kslam_kreport.h: the Kraken-style report (percent, clade reads, direct reads, rank code, taxonomy
 id, indented name) counted per taxon on the GPU, its host twin, the report writer and a parser for the report."""
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -50,7 +49,7 @@ def lib():
 
 
 def _rows(ptr, n):
-    return np.frombuffer(C.string_at(ptr.value, n.value * ROW_DT.itemsize), dtype=ROW_DT).copy() if n.value else np.zeros(0, dtype=ROW_DT)
+    return _T.rows_at(ptr.value, n.value, ROW_DT)
 
 
 def set_kreport(ctx, on=True):
@@ -110,18 +109,7 @@ def write(taxdb, rows, total_read_pairs, fd):
 
 def report_bytes(taxdb, rows, total_read_pairs):
     """the report as bytes (through a pipe-free temporary descriptor)"""
-    fd = os.memfd_create("kslam_kreport")
-    try:
-        write(taxdb, rows, total_read_pairs, fd)
-        os.lseek(fd, 0, os.SEEK_SET)
-        out = b""
-        while True:
-            piece = os.read(fd, 1 << 20)
-            if not piece:
-                return out
-            out += piece
-    finally:
-        os.close(fd)
+    return _T.fd_bytes("kslam_kreport", lambda fd: write(taxdb, rows, total_read_pairs, fd))
 
 
 def stream_set_kreport(ctx, fd):

@@ -3,7 +3,6 @@ per cycle, mean quality per read, GC content) tallied per cycle on the GPU, its 
 file."""
 import ctypes as C
 import json
-import os
 
 import numpy as np
 
@@ -92,7 +91,7 @@ def pack(tables):
 
 def _tables_out(t):
     n = 2 * int(t.words_per_stream)
-    block = np.frombuffer(C.string_at(t.block, 8 * n), dtype=np.uint64)
+    block = _T.rows_at(t.block, n, np.dtype(np.uint64))
     return unpack(block, int(t.max_cycles), t.paired)
 
 
@@ -181,18 +180,7 @@ def write(tables, fd):
 
 def report_bytes(tables):
     """the file as bytes (through a temporary descriptor)"""
-    fd = os.memfd_create("kslam_read_qc")
-    try:
-        write(tables, fd)
-        os.lseek(fd, 0, os.SEEK_SET)
-        out = b""
-        while True:
-            piece = os.read(fd, 1 << 20)
-            if not piece:
-                return out
-            out += piece
-    finally:
-        os.close(fd)
+    return _T.fd_bytes("kslam_read_qc", lambda fd: write(tables, fd))
 
 
 def stream_set_read_qc(ctx, fd, max_cycles=0):

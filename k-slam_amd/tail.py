@@ -5,6 +5,7 @@ i.e. what the reference runs between alignToDatabase and the taxonomy step
 (reference src/SLAM.h:101-133).  Host-only calls: they work without a GPU.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -211,6 +212,30 @@ def _take(ptr, n, dtype):
     if ptr.value:
         L.kslam_free(ptr)
     return out
+
+
+def rows_at(address, n, dtype):
+    """a copy of the n items of `dtype` at `address` (not through ctypes.string_at: it takes its size as a C int, which 2^31 bytes
+    of rows and more do not fit)"""
+    if not n:
+        return np.zeros(0, dtype=dtype)
+    return np.frombuffer((C.c_char * (int(n) * dtype.itemsize)).from_address(address), dtype=dtype).copy()
+
+
+def fd_bytes(name, write_to_fd):
+    """what write_to_fd(fd) writes, as bytes (through a pipe-free temporary descriptor called `name`)"""
+    fd = os.memfd_create(name)
+    try:
+        write_to_fd(fd)
+        os.lseek(fd, 0, os.SEEK_SET)
+        out = b""
+        while True:
+            piece = os.read(fd, 1 << 20)
+            if not piece:
+                return out
+            out += piece
+    finally:
+        os.close(fd)
 
 
 def _ov(overlaps):

@@ -54,7 +54,7 @@ def get_taxon_reads(ctx):
     L = lib()
     p, n, mode = C.c_void_p(), C.c_uint64(), C.c_uint32()
     ctx._chk(L.kslam_get_taxon_reads(ctx._h, C.byref(p), C.byref(n), C.byref(mode)))
-    out = np.frombuffer(C.string_at(p.value, 4 * n.value), dtype=np.uint32).copy() if n.value else np.zeros(0, dtype=np.uint32)
+    out = _T.rows_at(p.value, n.value, np.dtype(np.uint32))
     L.kslam_free(p)
     return out, int(mode.value)
 
@@ -100,8 +100,8 @@ def mask(ctx):
     L = lib()
     m, n, u, nu, a = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64(), C.c_int()
     ctx._chk(L.kslam_taxon_reads_mask(ctx._h, C.byref(m), C.byref(n), C.byref(u), C.byref(nu), C.byref(a)))
-    hm = np.frombuffer(C.string_at(m.value, n.value), dtype=np.uint8).copy() if n.value else np.zeros(0, dtype=np.uint8)
-    hu = np.frombuffer(C.string_at(u.value, 4 * nu.value), dtype=np.uint32).copy() if nu.value else np.zeros(0, dtype=np.uint32)
+    hm = _T.rows_at(m.value, n.value, np.dtype(np.uint8))
+    hu = _T.rows_at(u.value, nu.value, np.dtype(np.uint32))
     L.kslam_free(m)
     L.kslam_free(u)
     return hm, hu, bool(a.value)

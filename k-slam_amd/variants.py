@@ -1,7 +1,6 @@
 """ctypes plumbing for include/kslam_variants.h: the SNV table piled up on the GPU (one row per entry, position and alternate
 base with its observations by strand and the depth), its host twin, the VCF writer and a parser for the file."""
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -89,7 +88,7 @@ def take(ctx, min_alt=2, min_depth=1):
     L = lib()
     rows, n, st = C.c_void_p(), C.c_uint64(), Stats()
     ctx._chk(L.kslam_variants_take(ctx._h, int(min_alt), int(min_depth), C.byref(rows), C.byref(n), C.byref(st)))
-    out = np.frombuffer(C.string_at(rows.value, n.value * ROW_DT.itemsize), dtype=ROW_DT).copy() if n.value else np.zeros(0, dtype=ROW_DT)
+    out = _T.rows_at(rows.value, n.value, ROW_DT)
     L.kslam_free_pinned(ctx._h, rows)
     return out, st.as_dict()
 
@@ -111,7 +110,7 @@ def tail_variants(entry_bases, entry_offsets, overlaps, cigar_pool, read_bases, 
     n_entries = max(len(go) - 1, 0)
     _T._chk(L.kslam_tail_variants(gb.ctypes.data if len(gb) else None, go.ctypes.data if n_entries else None, n_entries, *args, int(min_alt),
                                   int(min_depth), C.byref(rows), C.byref(n), C.byref(st)))
-    out = np.frombuffer(C.string_at(rows.value, n.value * ROW_DT.itemsize), dtype=ROW_DT).copy() if n.value else np.zeros(0, dtype=ROW_DT)
+    out = _T.rows_at(rows.value, n.value, ROW_DT)
     L.kslam_free(rows)
     return out, st.as_dict()
 
@@ -127,18 +126,7 @@ def write(index, rows, fd, stats=None):
 
 def report_bytes(index, rows, stats=None):
     """the VCF file as bytes (through a pipe-free temporary descriptor)"""
-    fd = os.memfd_create("kslam_variants")
-    try:
-        write(index, rows, fd, stats)
-        os.lseek(fd, 0, os.SEEK_SET)
-        out = b""
-        while True:
-            piece = os.read(fd, 1 << 20)
-            if not piece:
-                return out
-            out += piece
-    finally:
-        os.close(fd)
+    return _T.fd_bytes("kslam_variants", lambda fd: write(index, rows, fd, stats))
 
 
 def stream_set_variants(ctx, fd, min_alt=2, min_depth=1):

@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fcntl.h>
+#include <functional>
 #include <getopt.h>
 #include <string>
 #include <sys/stat.h>
@@ -629,53 +630,27 @@ int run(const Options &o, const std::string &command_line) {
     }
     if (kslam_stream_set_taxon_reads(ctx, extract_fds) != KSLAM_OK) die(std::string("extract: ") + kslam_last_error(ctx));
   }
-  int coverage_fd = -1;
-  if (!o.coverage_out.empty()) {
-    coverage_fd = open(o.coverage_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (coverage_fd < 0) die("unable to open " + o.coverage_out);
-    if (kslam_stream_set_coverage(ctx, coverage_fd) != KSLAM_OK) die(std::string("coverage: ") + kslam_last_error(ctx));
-  }
-  int kreport_fd = -1;
-  if (!o.kraken_report.empty()) {
-    kreport_fd = open(o.kraken_report.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (kreport_fd < 0) die("unable to open " + o.kraken_report);
-    if (kslam_stream_set_kreport(ctx, kreport_fd) != KSLAM_OK) die(std::string("Kraken-style report: ") + kslam_last_error(ctx));
-  }
-  int consensus_fd = -1;
-  if (!o.consensus_out.empty()) {
-    consensus_fd = open(o.consensus_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (consensus_fd < 0) die("unable to open " + o.consensus_out);
-    if (kslam_stream_set_consensus(ctx, consensus_fd, &o.consensus) != KSLAM_OK) die(std::string("consensus: ") + kslam_last_error(ctx));
-  }
-  int variants_fd = -1;
-  if (!o.variants_out.empty()) {
-    variants_fd = open(o.variants_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (variants_fd < 0) die("unable to open " + o.variants_out);
-    if (kslam_stream_set_variants(ctx, variants_fd, o.variants_min_alt, o.variants_min_depth) != KSLAM_OK) die(std::string("variants: ") + kslam_last_error(ctx));
-  }
-  int depth_fd = -1;
-  if (!o.depth_out.empty()) {
-    depth_fd = open(o.depth_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (depth_fd < 0) die("unable to open " + o.depth_out);
-    if (kslam_stream_set_depth(ctx, depth_fd, o.depth_min) != KSLAM_OK) die(std::string("depth: ") + kslam_last_error(ctx));
-  }
-  int genes_fd = -1;
-  if (!o.genes_out.empty()) {
-    genes_fd = open(o.genes_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (genes_fd < 0) die("unable to open " + o.genes_out);
-    if (kslam_stream_set_genes(ctx, genes_fd) != KSLAM_OK) die(std::string("genes: ") + kslam_last_error(ctx));
-  }
-  int qc_fd = -1;
-  if (!o.qc_out.empty()) {
-    qc_fd = open(o.qc_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (qc_fd < 0) die("unable to open " + o.qc_out);
-    if (kslam_stream_set_read_qc(ctx, qc_fd, o.qc_max_cycles) != KSLAM_OK) die(std::string("read QC: ") + kslam_last_error(ctx));
-  }
-  int align_qc_fd = -1;
-  if (!o.align_qc_out.empty()) {
-    align_qc_fd = open(o.align_qc_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (align_qc_fd < 0) die("unable to open " + o.align_qc_out);
-    if (kslam_stream_set_align_qc(ctx, align_qc_fd, o.align_qc_max_cycles) != KSLAM_OK) die(std::string("alignment QC: ") + kslam_last_error(ctx));
+  // the file reports, in the order they are opened and set: the path, "<what>: " of a refusal, "closing <noun> failed", the setter
+  struct OutputFile {
+    const std::string &path;
+    const char *what, *noun;
+    std::function<kslam_status(int)> set;
+    int fd = -1;
+  } output_files[] = {
+      {o.coverage_out, "coverage", "the coverage file", [ctx, &o](int fd) { return kslam_stream_set_coverage(ctx, fd); }},
+      {o.kraken_report, "Kraken-style report", "the Kraken-style report", [ctx, &o](int fd) { return kslam_stream_set_kreport(ctx, fd); }},
+      {o.consensus_out, "consensus", "the consensus file", [ctx, &o](int fd) { return kslam_stream_set_consensus(ctx, fd, &o.consensus); }},
+      {o.variants_out, "variants", "the variants file", [ctx, &o](int fd) { return kslam_stream_set_variants(ctx, fd, o.variants_min_alt, o.variants_min_depth); }},
+      {o.depth_out, "depth", "the depth file", [ctx, &o](int fd) { return kslam_stream_set_depth(ctx, fd, o.depth_min); }},
+      {o.genes_out, "genes", "the gene table", [ctx, &o](int fd) { return kslam_stream_set_genes(ctx, fd); }},
+      {o.qc_out, "read QC", "the read QC report", [ctx, &o](int fd) { return kslam_stream_set_read_qc(ctx, fd, o.qc_max_cycles); }},
+      {o.align_qc_out, "alignment QC", "the alignment QC report", [ctx, &o](int fd) { return kslam_stream_set_align_qc(ctx, fd, o.align_qc_max_cycles); }},
+  };
+  for (OutputFile &f : output_files) {
+    if (f.path.empty()) continue;
+    f.fd = open(f.path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (f.fd < 0) die("unable to open " + f.path);
+    if (f.set(f.fd) != KSLAM_OK) die(std::string(f.what) + ": " + kslam_last_error(ctx));
   }
   kslam_stream_params sp;
   memset(&sp, 0, sizeof sp);
@@ -721,14 +696,8 @@ int run(const Options &o, const std::string &command_line) {
     if (fd >= 0 && close(fd) != 0) die("closing a reads-out file failed");
   for (int fd : extract_fds)
     if (fd >= 0 && close(fd) != 0) die("closing a file of extracted reads failed");
-  if (coverage_fd >= 0 && close(coverage_fd) != 0) die("closing the coverage file failed");
-  if (variants_fd >= 0 && close(variants_fd) != 0) die("closing the variants file failed");
-  if (consensus_fd >= 0 && close(consensus_fd) != 0) die("closing the consensus file failed");
-  if (depth_fd >= 0 && close(depth_fd) != 0) die("closing the depth file failed");
-  if (genes_fd >= 0 && close(genes_fd) != 0) die("closing the gene table failed");
-  if (kreport_fd >= 0 && close(kreport_fd) != 0) die("closing the Kraken-style report failed");
-  if (qc_fd >= 0 && close(qc_fd) != 0) die("closing the read QC report failed");
-  if (align_qc_fd >= 0 && close(align_qc_fd) != 0) die("closing the alignment QC report failed");
+  for (const OutputFile &f : output_files)
+    if (f.fd >= 0 && close(f.fd) != 0) die(std::string("closing ") + f.noun + " failed");
   logl(cat("Found ", st.n_overlaps, " k-mer overlaps"));
   logl(cat("", st.n_read_pairs_aligned, " entries have k-mer overlaps"));
   if (paired && st.n_batches) logl(cat("Screening all alignment pairs with insert size >= ", st.first_max_insert_size, ""));
