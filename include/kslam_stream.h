@@ -77,7 +77,19 @@ typedef struct {
 
 /* tax_ids: one taxonomy id per aligned read pair over all batches, in order (malloc'ed, kslam_free; NULL when taxdb
  * is NULL = --just-align).  report may be NULL.  Errors: those of the calls above; the message is in
- * kslam_last_error(ctx) or kslam_tail_last_error(), whichever stage failed (both are tried by the Python plumbing). */
+ * kslam_last_error(ctx) or kslam_tail_last_error(), whichever stage failed (both are tried by the Python plumbing).
+ *
+ * The files of a call that fails.  A batch that is refused (a FASTQ record that does not hold together, R1 and R2 of different
+ * lengths -- also when R2 ends exactly where a batch ends --, a read id a BAM record cannot hold) ends the call: per_read_fd and the
+ * descriptors of kslam_stream_set_reads_out / kslam_stream_set_taxon_reads hold the batches in front of it, whole and in order,
+ * and a plain-text SAM file its header and their rows; a compressed SAM file has no EOF marker.  The report files of the other
+ * kslam_stream_set_* are written behind the last batch only, in the order coverage, genes, Kraken-style report, variants,
+ * consensus, read QC, alignment QC, depth: a call that fails in a batch writes none of them, and one that fails writing a report
+ * leaves the reports in front of it whole and those behind it untouched.  A descriptor that stops taking bytes (EPIPE, a full disk)
+ * fails the call with that file's message; what the other files hold then is a prefix, batch by batch, of what the call would have
+ * written (a failing SAM descriptor may be noticed only when the file is closed, behind the reports).  However the call ends, it
+ * leaves every switch it set off and every kslam_stream_set_* descriptor and parameter at its default, and it keeps nothing: the
+ * next call on ctx starts every report from nothing, whatever an earlier call or the caller's own batches left in it. */
 kslam_status kslam_stream_classify(kslam_ctx *ctx, const kslam_index_view *index, const kslam_taxdb *taxdb,
                                    kslam_taxreport *report, const char *r1, uint64_t len1, const char *r2,
                                    uint64_t len2, const kslam_stream_params *params, uint32_t **tax_ids,

@@ -475,7 +475,10 @@ struct Run {
     done_pairs += want;
     p1 += e1;
     p2 += e2;
-    if (p1 >= len1 || (paired && p2 >= len2)) exhausted = true;
+    // R1 decides when the stream is over (src/FASTQsequence.h:114-116: no read from R1, no batch).  R2 running out first does not:
+    // the next window then holds R1's records and nothing of R2, and the batch is refused as the reference refuses it (:118-122)
+    // -- also when R2 ends exactly where a batch ends.
+    if (p1 >= len1) exhausted = true;
     return true;
   }
 

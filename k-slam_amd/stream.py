@@ -171,7 +171,7 @@ def cut_batches(r1_ptr, len1, r2_ptr, len2, pairs_per_batch, max_pairs_total=0, 
         e2 = 0 if single else F.batch_end(r2_ptr + p2, len2 - p2, want, True, threads)[0]
         e1 += p1
         e2 += p2
-        last = e1 >= len1 or (not single and e2 >= len2)
+        last = e1 >= len1      # R1 decides (src/FASTQsequence.h:114-116); an R2 that ran out first makes the next batch a mismatch (:118-122)
         yield p1, e1, p2, e2, last
         done_pairs += want
         p1, p2 = e1, e2

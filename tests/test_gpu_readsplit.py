@@ -113,9 +113,9 @@ def world(kslam, synth, tmp_path_factory):
     return {"case": case, "db": db, "tmp": tmp, "n": n}
 
 
-def _indexed_context(kslam, world):
+def _indexed_context(kslam, world, **params):
     import ctypes as C
-    c = kslam.Context()
+    c = kslam.Context(**params)
     bases_pp, lens_p = world["db"].entry_pointers()
     c._chk(c._L.kslam_set_index(c._h, world["db"].n_entries, C.cast(bases_pp, C.c_void_p), C.cast(lens_p, C.c_void_p)))
     return c

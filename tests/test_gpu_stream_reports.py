@@ -29,12 +29,17 @@ def _modules():
                                                                   "kreport", "variants", "consensus", "readqc", "alignqc", "depth")}
 
 
-def _call(M, c, world, texts, tax, tmp, tag, wanted, chosen, with_tree=True):
-    """one kslam_stream_classify with the outputs in `wanted` -> ({file: bytes}, statistics)"""
+def _call(M, c, world, texts, tax, tmp, tag, wanted, chosen, with_tree=True, per_batch=300, params=None, header=b"@HD\tVN:1.0\n", report=None,
+          instead=None):
+    """one kslam_stream_classify with the outputs in `wanted` -> ({file: bytes}, statistics).  texts: ((R1 buffer, bytes), (R2
+    buffer or None for single-end data, bytes)); params: the tail's parameters (default: paired, everything else as SLAM's);
+    instead: {file: descriptor} the caller opened itself (and closes), used in place of the file of that name"""
     (h1, n1), (h2, n2) = texts
-    names = {f: str(tmp / (tag + "." + f)) for o in wanted for f in OUTPUTS[o]}
+    single = h2 is None
+    names = {f: str(tmp / (tag + "." + f)) for o in wanted for f in OUTPUTS[o] if not (single and f[-1] == "2")}
     names.update({f: str(tmp / (tag + "." + f)) for f in ALWAYS})
-    fds = {f: os.open(p, os.O_RDWR | os.O_CREAT | os.O_TRUNC) for f, p in names.items()}
+    own = {f: os.open(p, os.O_RDWR | os.O_CREAT | os.O_TRUNC) for f, p in names.items()}
+    fds = dict(own, **(instead or {}))
     fd = lambda o: fds[OUTPUTS[o][0]] if o in wanted else -1   # noqa: E731
     if "taxon_reads" in wanted:   # the chosen ids hold for one call
         M["samtext"].set_annotations(c, world["db"], tax)
@@ -42,14 +47,15 @@ def _call(M, c, world, texts, tax, tmp, tag, wanted, chosen, with_tree=True):
         M["taxreads"].set_taxon_reads(c, chosen, M["taxreads"].CHILDREN)
     try:
         st = M["stream"].classify_stream_native(
-            c, world["db"], h1.ptr, n1, h2.ptr, n2, 300, M["tail"].TailParams.default(paired=True), taxdb=tax if with_tree else None,
-            sam_fd=fds["sam"], per_read_fd=fds["per_read"] if with_tree else -1, sam_header=b"@HD\tVN:1.0\n", depth=3,
+            c, world["db"], h1.ptr, n1, None if single else h2.ptr, n2, per_batch, params if params is not None else M["tail"].TailParams.default(paired=True),
+            taxdb=tax if with_tree else None, report=report,
+            sam_fd=fds["sam"], per_read_fd=fds["per_read"] if with_tree else -1, sam_header=header, depth=3,
             coverage_fd=fd("coverage"), genes_fd=fd("genes"), kreport_fd=fd("kreport"), variants_fd=fd("variants"), consensus_fd=fd("consensus"),
             read_qc_fd=fd("read_qc"), align_qc_fd=fd("align_qc"), depth_fd=fd("depth"),
-            reads_out_fds=[fds[f] for f in OUTPUTS["reads_out"]] if "reads_out" in wanted else None,
-            taxon_reads_fds=[fds[f] for f in OUTPUTS["taxon_reads"]] if "taxon_reads" in wanted else None, **PARAMS)
+            reads_out_fds=[fds.get(f, -1) for f in OUTPUTS["reads_out"]] if "reads_out" in wanted else None,
+            taxon_reads_fds=[fds.get(f, -1) for f in OUTPUTS["taxon_reads"]] if "taxon_reads" in wanted else None, **PARAMS)
     finally:
-        for f in fds.values():
+        for f in own.values():
             os.close(f)
     return {f: open(p, "rb").read() for f, p in names.items()}, st
 
