@@ -179,14 +179,23 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
     if (sam_planned) {
       sam_stage_mapq(sam);   // pow / log10 / ceil with the host's libm
       // (kslam_set_sam_bgzf) compressed before the copy; (kslam_set_sam_bam) BAM records, which are always compressed
-      const bool bam = primary->samtext.sam && primary->samtext.bam;
-      const bool bgzf = primary->samtext.sam && (primary->samtext.bgzf || bam);
+      // (kslam_set_bam_sort) BAM records that stay on the device: neither compressed nor fetched, held for the sort at the end
+      const bool held = primary->samtext.sam && primary->bsort_on.load(std::memory_order_acquire);
+      const bool bam = primary->samtext.sam && (primary->samtext.bam || held);
+      const bool bgzf = primary->samtext.sam && (primary->samtext.bgzf || bam) && !held;
       sam.bam = bam;
       sam.seq = primary->samtext.sam && primary->samtext.seq;   // (kslam_set_sam_seq) SEQ and QUAL on the primary rows
       sam.unmapped = primary->samtext.sam && primary->samtext.unmapped;   // (kslam_set_sam_unmapped) rows for the reads without alignment
       st = guarded(c, [&] {
         sam_stage_kernels(c, primary, sam, primary->samtext.sam, primary->samtext.per_read);
-        if (bgzf) {
+        if (held) {
+          // into the owner's store on this lane's stream, outside the compute token like the reports below; the unmapped rows lie
+          // behind the mapped ones (sam_stage_kernels), c->sumw.bytes of them
+          const uint64_t behind = sam.unmapped ? c->sumw.bytes : 0;
+          const uint64_t n_records = primary->pairing.paired ? c->n_reads / 2 : c->n_reads;
+          bamsort_append_resident(primary, c, job->ticket, sam.n_groups, sam.text_bytes - behind, sam.unmapped ? n_records : 0, sam.text_bytes);
+          sam.text_bytes = 0;   // nothing travels
+        } else if (bgzf) {
           bgzf_compress_device(c->samw.text.as<char>(), sam.text_bytes, primary->samtext.deflate, c->bgzfw, c->bgzf_out, &sam.text_bytes, c->stream);
           sam.d_sam = c->bgzf_out.p;
         }
@@ -199,7 +208,7 @@ void lane_main(kslam_ctx *primary, kslam_ctx::AsyncLane *lane) {
         });
       if (st == KSLAM_OK)
         job->text_flags = (primary->samtext.sam ? (KSLAM_TEXT_PAIRS_SORTED | KSLAM_TEXT_SAM) : 0u) | (primary->samtext.per_read ? KSLAM_TEXT_PER_READ : 0u) |
-                          (bgzf ? KSLAM_TEXT_SAM_BGZF : 0u) | (bam ? KSLAM_TEXT_SAM_BAM : 0u) | (sam.seq ? KSLAM_TEXT_SAM_SEQ : 0u) |
+                          (bgzf ? KSLAM_TEXT_SAM_BGZF : 0u) | (bam ? KSLAM_TEXT_SAM_BAM : 0u) | (held ? KSLAM_TEXT_SAM_HELD : 0u) | (sam.seq ? KSLAM_TEXT_SAM_SEQ : 0u) |
                           (sam.unmapped ? KSLAM_TEXT_SAM_UNMAPPED : 0u);
       if (st == KSLAM_OK && sam.unmapped) unmapped_note(primary, c);
       // (kslam_set_kreport) this lane has just made the batch's taxonomy ids: they go into the owner's per-taxon counters from

@@ -1,5 +1,5 @@
 // api_reports.h -- what the opt-in reports behind the C ABI share (api_coverage.hip, api_variants.hip, api_depth.hip,
-// api_kreport.hip, api_genes.hip, api_readqc.hip, api_alignqc.hip, api_consensus.hip; the reads of chosen taxa, api_taxreads.hip, are released with
+// api_kreport.hip, api_genes.hip, api_readqc.hip, api_alignqc.hip, api_consensus.hip, api_bamsort.hip; the reads of chosen taxa, api_taxreads.hip, are released with
 // them): their entry points for the lanes, the lists of what an index or a tree takes with it, and the shell of their ABI
 // functions.  Each file keeps what is its own: its table layout, its switch-on preconditions, its zeroing, its take.
 // Included from context.h, behind the context.
@@ -59,6 +59,16 @@ void consensus_release(kslam_ctx *c);
 // the batch `lane` has just finished (as variants_emit_resident sees it) into owner's state, on lane's stream
 void consensus_emit_resident(kslam_ctx *owner, kslam_ctx *lane);
 
+// ---- api_bamsort.hip
+// frees the held records of c and switches the sort off (kslam_set_bam_sort(c, 0), kslam_set_index)
+void bamsort_release(kslam_ctx *c);
+// ... and the state itself (kslam_destroy)
+void bamsort_destroy(kslam_ctx *c);
+// the BAM records `lane` has just written (lane->samw.text[0 .. total_bytes): the mapped rows of n_groups read pairs in front of
+// mapped_bytes, the rows of the reads without alignment behind it) into owner's store as batch `ticket`, on lane's stream
+void bamsort_append_resident(kslam_ctx *owner, kslam_ctx *lane, uint64_t ticket, uint64_t n_groups, uint64_t mapped_bytes, uint64_t n_unmapped_rows,
+                             uint64_t total_bytes);
+
 // ---- api_taxreads.hip
 // frees the selection of c and switches it off (kslam_set_taxon_reads(c, NULL, 0, 0), kslam_set_sam_annotations, kslam_set_index)
 void taxreads_release(kslam_ctx *c);
@@ -84,6 +94,7 @@ inline void release_index_bound_reports(kslam_ctx *c) {
   genes_release(c);      // (include/kslam_genes.h) likewise: the gene columns belong to the old index's entries
   alignqc_release(c);    // (include/kslam_alignqc.h) its counts are of alignments to the old index's entries
   consensus_release(c);  // (include/kslam_consensus.h) the keys hold the old index's base positions
+  bamsort_release(c);    // (include/kslam_bamsort.h) the held records name the old index's entries
 }
 
 // ---- the batch a lane has just finished, as the reports' kernels see it ----

@@ -10,7 +10,7 @@
 //   api_readsplit.hip  the reads split by outcome, cut out of the uploaded text
 //   api_taxreads.hip   the reads of chosen taxa, likewise
 //   api_coverage.hip, api_variants.hip, api_depth.hip, api_kreport.hip, api_genes.hip, api_readqc.hip, api_alignqc.hip,
-//   api_consensus.hip
+//   api_consensus.hip, api_bamsort.hip
 //                  the opt-in reports the lanes feed, one file each; what they share is in api_reports.h (included below)
 #pragma once
 #include <sys/mman.h>
@@ -35,6 +35,7 @@
 #include "../../include/kslam_taxreads.h"
 #include "../../include/kslam_genes.h"
 #include "../../include/kslam_alignqc.h"
+#include "../../include/kslam_bamsort.h"
 #include "../host/workers.hpp"
 #include "../host/inflate.hpp"
 #include "../host/batch_check.hpp"
@@ -52,6 +53,11 @@
 #include <thread>
 
 using namespace kslam;
+
+namespace kslam {
+struct BamSortState;   // bamsort.h
+struct BamSortWork;
+}  // namespace kslam
 
 // The resident genome index (const GenbankIndex&): what build_index makes, never changed after.  The context that built it,
 // its worker lanes and its siblings share it; kslam_set_index builds a new one and leaves the old one to whoever still holds it.
@@ -183,6 +189,13 @@ struct kslam_ctx {
   SamWork samw;
   struct { bool sam = false, per_read = false, bgzf = false, bam = false, seq = false, unmapped = false; uint32_t num_alignments = 10; int sam_xa = 0;
            int deflate = KSLAM_BGZF_DEFLATE_FIXED; } samtext;   // for the lanes; deflate: kslam_set_bgzf_deflate, also for kslam_bgzf_compress
+  // ---- the coordinate-sorted BAM (bamsort.hip, include/kslam_bamsort.h): the state behind a pointer (bamsort.h), made by the
+  // switch on the context it was set on; its lanes append their batches' records to it instead of compressing them
+  std::atomic<bool> bsort_on{false};
+  kslam::BamSortState *bsort = nullptr;
+  kslam::BamSortWork *bsort_w = nullptr;   // this context's own record-index passes (a lane's batches); made by the thread that uses it
+  struct { int on = 0, bai_fd = -1; } bsort_stream;   // kslam_stream_set_bam_sort
+
   // the rows of the reads without alignment (samunmapped.hip, include/kslam_samunmapped.h): this context's own passes, and what
   // kslam_sam_unmapped_kernel_ms reports -- the last batch formatted here or on one of this context's lanes (under as_mu)
   SamUnmappedWork sumw;

@@ -38,6 +38,7 @@
 #include "../../include/kslam_taxreads.h"
 #include "../../include/kslam_variants.h"
 #include "../../include/kslam_consensus.h"
+#include "../../include/kslam_bamsort.h"
 #include "../../include/kslam_depth.h"
 #include "workers.hpp"
 
@@ -275,8 +276,9 @@ struct Batch {
   kslam_batch_result res{};
   kslam_reads_out ro{}, tro{};
   Window win{};
+  uint64_t seq = 0;   // the batch's place in submission order (the sorted BAM's ordinal)
   explicit Batch(kslam_ctx *c) : ctx(c) {}
-  Batch(Batch &&o) noexcept : ctx(o.ctx), res(o.res), ro(o.ro), tro(o.tro), win(o.win) { o.ctx = nullptr; }
+  Batch(Batch &&o) noexcept : ctx(o.ctx), res(o.res), ro(o.ro), tro(o.tro), win(o.win), seq(o.seq) { o.ctx = nullptr; }
   ~Batch() {
     if (!ctx) return;
     kslam_release_reads_out(ctx, &tro);
@@ -334,6 +336,11 @@ struct Run {
   uint32_t tr_mode = 0;
   int tr_bgzf = 0;
   int bgzf = 0, bam = 0, seq = 0, unmapped = 0;
+  // kslam_stream_set_bam_sort (include/kslam_bamsort.h): the SAM file as a coordinate-sorted BAM, written whole behind the last batch
+  int sorted = 0, bai_fd = -1;
+  bool sort_armed = false;
+  uint64_t first_ticket = 0;
+  bool any_ticket = false;
   kslam_tail_params host_all, host_write, host_sorted;   // what the host stage still has to run
   // batch boundaries, found ahead of the submission (src/SLAM.h:193, 201-206)
   uint64_t p1 = 0, p2 = 0, done_pairs = 0;
@@ -392,6 +399,14 @@ struct Run {
       if (tr_ids.empty()) fail(KSLAM_ERR_STATE, "kslam_stream_set_taxon_reads without chosen ids: call kslam_set_taxon_reads first");
       if (kslam_get_reads_out_bgzf(ctx, &tr_bgzf) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
     }
+    // the sorted BAM: switched on (and emptied) ahead of the first ticket, which becomes ordinal 0
+    if (kslam_stream_get_bam_sort(ctx, &sorted, &bai_fd) != KSLAM_OK) fail(KSLAM_ERR_ARG, "null context");
+    if (sorted) {
+      if (P->sam_fd < 0) fail(KSLAM_ERR_ARG, "kslam_stream_set_bam_sort needs a SAM file (sam_fd)");
+      if (kslam_set_bam_sort(ctx, 1) != KSLAM_OK) fail(KSLAM_ERR_UNSUPPORTED, kslam_last_error(ctx));
+      sort_armed = true;
+      if (kslam_bam_sort_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+    }
     Report *const ahead_of_the_annotations[] = {&coverage, &variants, &consensus, &depth_track, &read_qc, &align_qc};
     for (Report *r : ahead_of_the_annotations) {
       r->want(ctx);
@@ -436,9 +451,11 @@ struct Run {
     if (kslam_get_sam_bgzf(ctx, &bgzf) != KSLAM_OK || kslam_get_sam_bam(ctx, &bam) != KSLAM_OK || kslam_get_sam_seq(ctx, &seq) != KSLAM_OK ||
         kslam_get_sam_unmapped(ctx, &unmapped) != KSLAM_OK)
       fail(KSLAM_ERR_ARG, "null context");
+    if (sorted) bam = 1;
     if (bam) bgzf = 1;
     if (P->sam_fd < 0) return;
     if (kslam_sam_writer_open(P->sam_fd, &writer) != KSLAM_OK) fail(KSLAM_ERR_ARG, "could not start the SAM writer");
+    if (sorted) return;   // (the header goes out with the records, behind the last batch: finish)
     if (bam) {
       char *h = nullptr;
       uint64_t hlen = 0;
@@ -494,6 +511,8 @@ struct Run {
       if (kslam_submit_batch_fastq_text(ctx, r1 + w.p1, w.e1 - w.p1, paired ? r2 + w.p2 : nullptr, paired ? w.e2 - w.p2 : 0, 0, 1, &tk) != KSLAM_OK)
         fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
       st.seconds_submitting += (now_ms() - tsub) * 1e-3;
+      if (!any_ticket) first_ticket = tk;
+      any_ticket = true;
       tickets.push_back(tk);
       windows.push_back(w);
     }
@@ -506,6 +525,7 @@ struct Run {
     const uint64_t tk = tickets.front();
     tickets.pop_front();
     b.win = windows.front();
+    b.seq = tk - first_ticket;
     windows.pop_front();
     const kslam_status cs = kslam_collect_batch(ctx, tk, &b.res);
     const double tb = now_ms();
@@ -599,6 +619,11 @@ struct Run {
       fail(KSLAM_ERR_STATE, "kslam_set_sam_seq was changed while kslam_stream_classify was running");
     if ((unmapped != 0) != ((res.text_flags & KSLAM_TEXT_SAM_UNMAPPED) != 0))   // (host-formatted batches follow `unmapped`)
       fail(KSLAM_ERR_STATE, "kslam_set_sam_unmapped was changed while kslam_stream_classify was running");
+    if (sorted) {   // the lane holds the records in the sort's store: nothing travels, nothing is written yet
+      if (!(res.text_flags & KSLAM_TEXT_SAM_HELD)) fail(KSLAM_ERR_STATE, "kslam_set_bam_sort was switched off while kslam_stream_classify was running");
+      st.seconds_sam_text += (now_ms() - t0) * 1e-3;
+      return;
+    }
     if (bgzf && !(res.text_flags & KSLAM_TEXT_SAM_BGZF)) {   // (the switch went on after the batch was formatted)
       st.sam_bytes += enqueue_compressed(res.sam_text, res.sam_text_len);
     } else {
@@ -612,7 +637,7 @@ struct Run {
   }
 
   // The batch's SAM text formatted here, by the host twins of what the lanes run.
-  void host_text_route(const kslam_batch_result &res, const kslam_reads_view &reads, Columns &columns) {
+  void host_text_route(const kslam_batch_result &res, const kslam_reads_view &reads, Columns &columns, uint64_t ordinal) {
     kslam_tail_stats ts;
     memset(&ts, 0, sizeof ts);
     const double t0 = now_ms();
@@ -653,7 +678,10 @@ struct Run {
       if (rows_len && wr(wu, rows, rows_len) != 0) fail(KSLAM_ERR_ARG, "writing the SAM rows of the unaligned reads failed");
       if (!bgzf) ts.sam_bytes += rows_len;
     }
-    st.sam_bytes += bgzf ? enqueue_compressed(text.data(), text.size()) : ts.sam_bytes;
+    if (sorted) {   // the batch's records join the lanes' in the sort's store, under the batch's ordinal
+      if (kslam_bam_sort_add(ctx, ordinal, text.data(), text.size()) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+    } else
+      st.sam_bytes += bgzf ? enqueue_compressed(text.data(), text.size()) : ts.sam_bytes;
     st.seconds_sam_text += (now_ms() - t0) * 1e-3;
   }
 
@@ -719,7 +747,7 @@ struct Run {
     // the reports that count final alignment pairs: this stage has just finished the batch's, where no lane did
     for (Report *r : reports) main.run(r->armed && pseudo_left, [this, r, &res, &columns] { r->add(ctx, res, columns); });
     if (writer && (res.text_flags & KSLAM_TEXT_SAM)) main.run(true, [this, &res] { device_text_route(res); });
-    else main.run(writer != nullptr, [this, &res, &reads, &columns] { host_text_route(res, reads, columns); });
+    else main.run(writer != nullptr, [this, &b, &res, &reads, &columns] { host_text_route(res, reads, columns, b.seq); });
     if (tax_thread.joinable()) tax_thread.join();
     else if (taxdb && main.s == KSLAM_OK) tax_part();
     if (main.s == KSLAM_OK && tax.s != KSLAM_OK) main = tax;
@@ -737,7 +765,15 @@ struct Run {
   void finish() {
     if (worker.joinable()) worker.join();
     if (worker_status != KSLAM_OK) fail(worker_status, worker_error);
-    if (writer && bgzf && kslam_write_queued(writer, KSLAM_BGZF_EOF, KSLAM_BGZF_EOF_LEN) != 0) fail(KSLAM_ERR_ARG, "writing the BGZF EOF marker failed");
+    if (writer && sorted) {   // every batch is in: the whole sorted file and its index, in front of the other report files
+      kslam_bam_sort_stats bs;
+      int fd = bai_fd;
+      if (kslam_bam_sort_take(ctx, P->sam_header, P->sam_header ? P->sam_header_len : 0, kslam_write_queued, writer, bai_fd >= 0 ? kslam_write_fd : nullptr,
+                              &fd, &bs) != KSLAM_OK)
+        fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
+      st.sam_bytes = bs.compressed_bytes;
+    } else if (writer && bgzf && kslam_write_queued(writer, KSLAM_BGZF_EOF, KSLAM_BGZF_EOF_LEN) != 0)
+      fail(KSLAM_ERR_ARG, "writing the BGZF EOF marker failed");
     if (ro_which && ro_bgzf)
       for (int k = 0; k < 4; k++)
         if (ro_fds[k] >= 0 && !write_all(ro_fds[k], KSLAM_BGZF_EOF, KSLAM_BGZF_EOF_LEN)) fail(KSLAM_ERR_ARG, "writing a reads-out file's BGZF EOF marker failed");
@@ -769,6 +805,8 @@ struct Run {
     if (text_set) kslam_set_sam_text(ctx, 0, 0, 10, 0);
     if (reads_out_set) kslam_set_reads_out(ctx, 0);
     for (Report *r : reports) r->disarm(ctx);
+    if (sort_armed) kslam_set_bam_sort(ctx, 0);
+    if (ctx) kslam_stream_set_bam_sort(ctx, 0, -1);
     if (taxreads_set) kslam_set_taxon_reads(ctx, nullptr, 0, 0);
     if (ctx) kslam_stream_set_taxon_reads(ctx, nullptr);
     if (ctx) kslam_stream_set_reads_out(ctx, nullptr);

@@ -58,7 +58,7 @@ def classify_stream_native(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_bat
                            sam_fd=-1, per_read_fd=-1, sam_header=None, max_pairs_total=0, depth=0, passes=1, host_threads=0, pool_threads=0,
                            reads_out_fds=None, coverage_fd=-1, variants_fd=None, variants_min_alt=2, variants_min_depth=1, kreport_fd=-1, consensus_fd=None, consensus_params=None,
                            taxon_reads_fds=None, depth_fd=None, depth_min=1, read_qc_fd=-1, read_qc_max_cycles=0, genes_fd=-1,
-                           align_qc_fd=-1, align_qc_max_cycles=0):
+                           align_qc_fd=-1, align_qc_max_cycles=0, sam_sorted=False, sam_index_fd=None):
     """kslam_stream_classify: the same loop as classify_stream below, inside the library (no Python between the batches).
     Single-end data: params.paired = 0, r2_ptr = None, len2 = 0.
     reads_out_fds: four descriptors for the classified R1 / R2 and unclassified R1 / R2 records (kslam_amd.readsplit; -1 = not wanted).
@@ -77,6 +77,8 @@ def classify_stream_native(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_bat
     genes_fd: an open descriptor for the per-gene abundance table (kslam_amd.genes; -1 = none).
     align_qc_fd: an open descriptor for the alignment QC report (kslam_amd.alignqc; -1 = none) with its number of per-cycle
     rows (0 = 512); the context needs report_cigar.
+    sam_sorted: the file on sam_fd becomes a coordinate-sorted BAM, written behind the last batch (kslam_amd.bamsort), and
+    sam_index_fd, an open descriptor, receives its BAI index (None = no index).
     -> dict of the statistics + tax_ids (uint32 array, empty without a taxdb)"""
     L = T.lib()
     L.kslam_stream_classify.argtypes = [C.c_void_p, C.POINTER(T.IndexView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
@@ -115,6 +117,9 @@ def classify_stream_native(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_bat
     if align_qc_fd is not None and align_qc_fd >= 0:
         from . import alignqc as AQ
         AQ.stream_set_align_qc(ctx, align_qc_fd, align_qc_max_cycles)
+    if sam_sorted:
+        from . import bamsort as BS
+        BS.stream_set_bam_sort(ctx, True, sam_index_fd)
     rc =L.kslam_stream_classify(ctx._h, C.byref(index.view), taxdb._h if taxdb is not None else None,
                                  report._h if report is not None else None, r1_ptr, len1, r2_ptr, len2, C.byref(P),
                                  C.byref(ids), C.byref(n_ids), C.byref(st))

@@ -12,6 +12,11 @@
 // dead code path, out of the hot path's scope).
 //
 //   SLAM [option] --db=DATABASE R1FILE [R2FILE]
+//
+// Two options that `SLAM --help` does not list yet (its text is pinned by tests/golden/slam_help.txt):
+//   --sam-sorted        write --sam-file as a coordinate-sorted BAM (include/kslam_bamsort.h): implies --sam-bam, needs --sam-file;
+//                       the records stay on the GPU until the last batch, the file is written behind it
+//   --sam-index arg     where its BAI index goes (needs --sam-sorted); default: <sam-file>.bai
 #include <algorithm>
 #include <cerrno>
 #include <chrono>
@@ -43,6 +48,7 @@
 #include "../include/kslam_taxreads.h"
 #include "../include/kslam_variants.h"
 #include "../include/kslam_consensus.h"
+#include "../include/kslam_bamsort.h"
 #include "../include/kslam_depth.h"
 #include "../include/kslam_genes.h"
 #include "../include/kslam_alignqc.h"
@@ -81,6 +87,8 @@ struct Options {
   std::string db, out, sam, classified_out, unclassified_out, coverage_out, variants_out, kraken_report;
   uint32_t variants_min_alt = 2, variants_min_depth = 1;
   bool variants_min_alt_given = false, variants_min_depth_given = false;
+  bool sam_sorted = false;                 // --sam-sorted (include/kslam_bamsort.h)
+  std::string sam_index;                   // --sam-index
   std::string consensus_out;               // --consensus-out (include/kslam_consensus.h)
   kslam_consensus_params consensus{1, 500, KSLAM_CONSENSUS_FILL_N, 1};
   const char *consensus_dependent = nullptr;   // the first of --consensus-min-depth / -call-permille / -fill / -min-covered given
@@ -193,7 +201,7 @@ void usage(FILE *o) {
 Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
-         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT,
+         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SORTED, SAM_INDEX, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT,
          VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, CONSENSUS_OUT, CONSENSUS_MIN_DEPTH, CONSENSUS_PERMILLE, CONSENSUS_FILL, CONSENSUS_MIN_COVERED, DEPTH_OUT, DEPTH_MIN, GENES_OUT, QC_OUT, QC_MAX_CYCLES, ALIGN_QC_OUT, ALIGN_QC_MAX_CYCLES, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
@@ -210,6 +218,8 @@ Options parse(int argc, char **argv) {
       {"device", required_argument, nullptr, DEVICE},   // not in the reference: the HIP device ordinal (default 0)
       {"sam-bgzf", no_argument, nullptr, SAM_BGZF},     // not in the reference: the SAM file as BGZF (include/kslam_bgzf.h)
       {"sam-bam", no_argument, nullptr, SAM_BAM},       // not in the reference: the SAM file as BAM (include/kslam_bam.h)
+      // not in the reference: the SAM file as a coordinate-sorted BAM with its BAI index (include/kslam_bamsort.h)
+      {"sam-sorted", no_argument, nullptr, SAM_SORTED}, {"sam-index", required_argument, nullptr, SAM_INDEX},
       {"sam-deflate", required_argument, nullptr, SAM_DEFLATE},   // not in the reference: kslam_set_bgzf_deflate (include/kslam_bgzf.h)
       {"sam-seq", no_argument, nullptr, SAM_SEQ},       // not in the reference: SEQ and QUAL in the SAM file (include/kslam_samseq.h)
       {"sam-unmapped", no_argument, nullptr, SAM_UNMAPPED},   // not in the reference: rows for the reads without alignment (include/kslam_samunmapped.h)
@@ -262,6 +272,8 @@ Options parse(int argc, char **argv) {
       case XA: o.sam_xa = true; break;
       case SAM_BGZF: o.sam_bgzf = true; break;
       case SAM_BAM: o.sam_bam = true; break;
+      case SAM_SORTED: o.sam_sorted = true; break;
+      case SAM_INDEX: o.sam_index = optarg; break;
       case SAM_SEQ: o.sam_seq = true; break;
       case SAM_UNMAPPED: o.sam_unmapped = true; break;
       case CLASSIFIED_OUT: o.classified_out = optarg; break;
@@ -346,8 +358,12 @@ Options parse(int argc, char **argv) {
       default: die(std::string("unrecognised option '") + (optind > 0 && optind <= argc ? argv[optind - 1] : "?") + "'");
     }
   }
-  if (o.sam_deflate_given && !o.sam_bgzf && !o.sam_bam && !o.reads_out_bgzf) die("option '--sam-deflate' needs '--sam-bgzf' or '--sam-bam'");
+  if (o.sam_deflate_given && !o.sam_bgzf && !o.sam_bam && !o.sam_sorted && !o.reads_out_bgzf) die("option '--sam-deflate' needs '--sam-bgzf' or '--sam-bam'");
   if (o.sam_unmapped && o.sam.empty()) die("option '--sam-unmapped' needs '--sam-file'");
+  if (o.sam_sorted && o.sam.empty()) die("option '--sam-sorted' needs '--sam-file'");
+  if (!o.sam_index.empty() && !o.sam_sorted) die("option '--sam-index' needs '--sam-sorted'");
+  if (o.sam_sorted) o.sam_bam = true;                                   // --sam-sorted implies --sam-bam
+  if (o.sam_sorted && o.sam_index.empty()) o.sam_index = o.sam + ".bai";
   if (!o.kraken_report.empty() && o.just_align) die("option '--kraken-report' cannot be combined with '--just-align': the report counts taxonomy ids");
   if (o.just_align && (!o.extract_taxids.empty() || !o.extract_out.empty()))
     die(std::string("option '--") + (o.extract_taxids.empty() ? "extract-out" : "extract-taxid") + "' cannot be combined with '--just-align': the reads are chosen by taxonomy id");
@@ -652,6 +668,12 @@ int run(const Options &o, const std::string &command_line) {
     if (f.fd < 0) die("unable to open " + f.path);
     if (f.set(f.fd) != KSLAM_OK) die(std::string(f.what) + ": " + kslam_last_error(ctx));
   }
+  int sam_index_fd = -1;
+  if (o.sam_sorted) {
+    sam_index_fd = open(o.sam_index.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (sam_index_fd < 0) die("unable to open " + o.sam_index);
+    if (kslam_stream_set_bam_sort(ctx, 1, sam_index_fd) != KSLAM_OK) die(std::string("sorted BAM: ") + kslam_last_error(ctx));
+  }
   kslam_stream_params sp;
   memset(&sp, 0, sizeof sp);
   sp.pairs_per_batch = o.num_reads_at_once;
@@ -691,6 +713,7 @@ int run(const Options &o, const std::string &command_line) {
   struct stat sam_stat;
   if (sam_fd >= 0 && (o.sam_bgzf || o.sam_bam) && fstat(sam_fd, &sam_stat) == 0) sam_file_bytes = (uint64_t)sam_stat.st_size;   // compressed
   if (sam_fd >= 0) close(sam_fd);
+  if (sam_index_fd >= 0 && close(sam_index_fd) != 0) die("closing the BAM index failed");
   if (per_read_fd >= 0) close(per_read_fd);
   for (int fd : reads_out_fds)
     if (fd >= 0 && close(fd) != 0) die("closing a reads-out file failed");
