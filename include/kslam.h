@@ -672,6 +672,12 @@ typedef struct {
 } kslam_index_export;
 kslam_status kslam_debug_index_export(kslam_ctx *ctx, kslam_index_export *x);
 
+/* ---- test hook for the page-locked pools (tests/test_gpu_lane_batches.py) ----
+ * *n_blocks = the page-locked blocks marked in use on the context and on each of its lanes' contexts: what pipelined batches
+ * hold between kslam_collect_batch and kslam_release_batch, and 0 once everything was handed back.  Read-only; it takes each
+ * pool's lock in turn, so call it while no batch is in flight.  KSLAM_ERR_ARG for a null pointer. */
+kslam_status kslam_debug_pinned_in_use(kslam_ctx *ctx, uint64_t *n_blocks);
+
 #ifdef __cplusplus
 }
 #endif

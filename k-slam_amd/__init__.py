@@ -49,7 +49,7 @@ EXPORTS = ["kslam_abi_version", "kslam_index_build_stats", "kslam_version", "ksl
            "kslam_load_reads", "kslam_load_reads_device", "kslam_align_resident",
            "kslam_fetch_results", "kslam_take_results", "kslam_copy_results_device", "kslam_get_timings",
            "kslam_extract_kmers", "kslam_sort_kmers", "kslam_find_overlaps", "kslam_free",
-           "kslam_selftest_sort", "kslam_debug_radix_sort", "kslam_debug_scan", "kslam_debug_partition_bins", "kslam_debug_bgzf_code_lengths", "kslam_debug_join", "kslam_debug_overlap_unique", "kslam_debug_index_export",
+           "kslam_selftest_sort", "kslam_debug_radix_sort", "kslam_debug_scan", "kslam_debug_partition_bins", "kslam_debug_bgzf_code_lengths", "kslam_debug_join", "kslam_debug_overlap_unique", "kslam_debug_index_export", "kslam_debug_pinned_in_use",
            "kslam_merge_shards_device", "kslam_shard_counts_device",
            "kslam_export_shard_device", "kslam_multi_create", "kslam_multi_destroy",
            "kslam_multi_last_error", "kslam_multi_set_index", "kslam_multi_align_batch", "kslam_multi_free_batch"]
@@ -217,6 +217,7 @@ def lib():
         L.kslam_debug_overlap_unique.argtypes = [vp, vp, u64, C.POINTER(OverlapLayout), u32, C.c_int, vp, vp, vp, C.POINTER(u32),
                                                  C.POINTER(u64), vp]
         L.kslam_debug_index_export.argtypes = [vp, C.POINTER(IndexExport)]
+        L.kslam_debug_pinned_in_use.argtypes = [vp, C.POINTER(u64)]
         L.kslam_merge_shards_device.argtypes = [vp, u32, vp, u64, vp, vp, vp, vp]
         L.kslam_shard_counts_device.argtypes = [vp, u64, vp]
         L.kslam_export_shard_device.argtypes = [vp, u64, u64, u64, u64, u64, vp, vp, vp, vp]
@@ -758,6 +759,12 @@ class Context:
                 "meta": mo[:, 0].copy(), "offset": mo[:, 1].copy(),
                 "bucket": buf["bucket"][:need["bucket"]].view(np.uint32).copy(),
                 "filter": buf["filter"][:need["filter"]].view(np.uint32).copy()}
+
+    def debug_pinned_in_use(self):
+        """kslam_debug_pinned_in_use -> the page-locked blocks marked in use on this context and its lanes' contexts"""
+        n = C.c_uint64()
+        self._chk(self._L.kslam_debug_pinned_in_use(self._h, C.byref(n)))
+        return int(n.value)
 
     def find_overlaps(self):
         out = C.c_void_p()

@@ -454,6 +454,17 @@ void kslam_free_pinned(kslam_ctx *c, void *p) {
     if (pinned_put(l->c, p)) return;
 }
 
+kslam_status kslam_debug_pinned_in_use(kslam_ctx *c, uint64_t *n_blocks) {
+  if (!c || !n_blocks) return KSLAM_ERR_ARG;
+  auto in_use = [](kslam_ctx *x) {
+    std::lock_guard<std::mutex> lk(x->pin_mu);
+    return (uint64_t)std::count_if(x->pinned.begin(), x->pinned.end(), [](const kslam_ctx::Pinned &b) { return b.in_use; });
+  };
+  *n_blocks = in_use(c);
+  for (auto *l : c->lanes) *n_blocks += in_use(l->c);
+  return KSLAM_OK;
+}
+
 void kslam_free(void *p) { free(p); }
 void *kslam_host_alloc(uint64_t bytes) { return pinned_alloc((size_t)bytes); }
 void kslam_host_free(void *p, uint64_t bytes) { pinned_free(p, (size_t)bytes); }

@@ -375,7 +375,7 @@ struct kslam_ctx {
 
   // ---- pipelined entry (kslam_align_batch_async): worker lanes, each a sibling context that shares this context's index ----
   bool holds_hook = false;       // this context counts towards the page-locked column allocator being installed
-  struct AsyncJob {
+  struct AsyncJob {                   // what was submitted ...
     uint64_t ticket = 0;
     uint64_t n_reads = 0;
     char *cat = nullptr;              // pinned, from the lane context's pool
@@ -386,20 +386,14 @@ struct kslam_ctx {
     bool fastq = false, fastq_text = false;   // fastq_text: the index is built on the device too
     bool single = false;                      // fastq_text with ONE stream (r2 == NULL): single-end reads
     uint64_t max_pairs = 0; int at_eof = 1;
-    uint64_t r_n = 0, *r_off = nullptr, *r_ids_off = nullptr; char *r_ids = nullptr; uint64_t consumed[2] = {0, 0};
     uint64_t len1 = 0, len2 = 0;
     const uint64_t *bases_at = nullptr, *quality_at = nullptr;
     std::vector<uint64_t> off;
+    // ... and what became of it: the lane writes the result where kslam_collect_batch hands it out from
     bool done = false;
     kslam_status st = KSLAM_OK;
     std::string err;
-    kslam_overlap *out = nullptr; uint64_t n_out = 0;
-    uint32_t *pool = nullptr; uint64_t n_cig = 0;
-    kslam_row_detail *det = nullptr; char *md = nullptr; uint64_t n_md = 0;
-    kslam_read_pair *rp = nullptr; uint64_t n_rp = 0; kslam_paired_overlap *pr = nullptr; uint64_t n_pr = 0;
-    kslam_pair_stats pstats{};
-    char *sam_text = nullptr; uint64_t sam_len = 0; char *pr_text = nullptr; uint64_t pr_len = 0; uint32_t *tax = nullptr;
-    uint32_t text_flags = 0;
+    kslam_batch_result res{};
     bool ro_on = false, ro_supported = false;   // kslam_set_reads_out was on when the lane ran the batch; it came as FASTQ text
     kslam_reads_out ro{};
     bool tr_on = false, tr_supported = false;   // the same for kslam_set_taxon_reads
@@ -408,12 +402,12 @@ struct kslam_ctx {
   struct AsyncLane {
     kslam_ctx *c = nullptr;
     std::thread th;
-    std::deque<AsyncJob *> q;
+    std::deque<AsyncJob *> q;     // of the jobs `jobs` owns: a job leaves the map only when it is done
   };
   std::vector<AsyncLane *> lanes;
   std::mutex as_mu, as_compute;
   std::condition_variable as_cv;
-  std::map<uint64_t, AsyncJob *> jobs;   // submitted, not yet waited for
+  std::map<uint64_t, std::unique_ptr<AsyncJob>> jobs;   // submitted, not yet waited for
   uint64_t next_ticket = 0;
   bool as_stop = false;
 
