@@ -271,9 +271,12 @@ __device__ inline int32_t banded_attempt_reg(Seq &m, uint32_t *DW, uint32_t NL, 
 // One candidate per lane.  LDS ([element][lane]): translated spans + the three row arrays.  The
 // directions go to a global slab per block ([cell][lane], coalesced, L2 resident), written
 // fire-and-forget during the DP.
-template <int REG_BW>   // 0: rows in LDS, any band; 1 / 2 / 4: bands up to that width in registers
-__global__ __launch_bounds__(64) void k_banded_lds(CigJob J, SwInputs in, SwParams p, LdsLayout Y) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+// Row: what a cell of h_b / e_b / h_c is kept as.  int16_t wherever match x longest read <= 32767 bounds every H (every chunk of
+// short reads, and most long ones); int32_t, the reference's own type, for the chunks in which a span's score can pass that
+// (k_banded_lds_wide: a span that ends where the word pass first saturated scores up to 32767 + match - 1).
+template <int REG_BW, typename Row>   // 0: rows in LDS, any band; 1 / 2 / 4: bands up to that width in registers
+__device__ __forceinline__ void banded_lds_body(const CigJob &J, const SwInputs &in, const SwParams &p, const LdsLayout &Y,
+                                                uint8_t *lds_raw) {
   if (J.variant == 3) return;   // ablation: launch floor
   const uint32_t lane = threadIdx.x;
   const uint32_t NL = Y.nl;
@@ -282,7 +285,7 @@ __global__ __launch_bounds__(64) void k_banded_lds(CigJob J, SwInputs in, SwPara
   const uint32_t half = Y.nch * NL * 8u;   // bytes per packed sequence buffer
   uint8_t *SQ = lds_raw;
   uint8_t *SR = SQ + half;
-  int16_t *S = reinterpret_cast<int16_t *>(lds_raw + (size_t)2 * half);
+  Row *S = reinterpret_cast<Row *>(lds_raw + (size_t)2 * half);
   uint8_t *D = J.scratch + (uint64_t)blockIdx.x * J.wave_slab;
 
   uint32_t ci = 0;
@@ -335,11 +338,11 @@ __global__ __launch_bounds__(64) void k_banded_lds(CigJob J, SwInputs in, SwPara
   if (skip || J.variant == 2) return;
   const int32_t score = o.score;
   struct Acc {
-    int16_t *S; uint8_t *SQ, *SR, *D;   // row arrays as int16: |values| < 2^13 (14-bit score field)
+    Row *S; uint8_t *SQ, *SR, *D;       // row arrays: int16 holds them while match x longest read <= 32767 (cigar_traceback)
     uint32_t NL, lane, W1, width_d;
-    __device__ int16_t &hb(int32_t k) { return S[(uint32_t)k * NL + lane]; }
-    __device__ int16_t &eb(int32_t k) { return S[(W1 + (uint32_t)k) * NL + lane]; }
-    __device__ int16_t &hc(int32_t k) { return S[(2 * W1 + (uint32_t)k) * NL + lane]; }
+    __device__ Row &hb(int32_t k) { return S[(uint32_t)k * NL + lane]; }
+    __device__ Row &eb(int32_t k) { return S[(W1 + (uint32_t)k) * NL + lane]; }
+    __device__ Row &hc(int32_t k) { return S[(2 * W1 + (uint32_t)k) * NL + lane]; }
     int32_t oq, orf;                    // where element 0 of each span sits in its column (stage_codes_wave)
     __device__ static uint32_t code(const uint8_t *B, uint32_t s, uint32_t NL, uint32_t lane) {
       return ((uint32_t)B[((s >> 4) * NL + lane) * 8u + ((s >> 1) & 7u)] >> (4u * (s & 1u))) & 15u;
@@ -411,6 +414,17 @@ __global__ __launch_bounds__(64) void k_banded_lds(CigJob J, SwInputs in, SwPara
   J.ov[ci] = o;
   J.bw[ci] = 0;
   J.needbig[ci] = J.big ? 2 : 0;  // 2: ops live in the big temp area
+}
+
+template <int REG_BW>
+__global__ __launch_bounds__(64) void k_banded_lds(CigJob J, SwInputs in, SwParams p, LdsLayout Y) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  banded_lds_body<REG_BW, int16_t>(J, in, p, Y, lds_raw);
+}
+// the literal banded_sw with the reference's int32 rows: chunks whose scores can pass what int16 holds
+__global__ __launch_bounds__(64) void k_banded_lds_wide(CigJob J, SwInputs in, SwParams p, LdsLayout Y) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw_wide[];
+  banded_lds_body<0, int32_t>(J, in, p, Y, lds_raw_wide);
 }
 
 // ---- systolic banded attempt ----------------------------------------------------------------------
@@ -802,6 +816,10 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
   uint32_t *d_err = reinterpret_cast<uint32_t *>(d_tot + 2);
   HIPCHK(hipMemsetAsync(d_tot, 0, 4 * sizeof(uint64_t), s));
   const uint32_t cap_big = 2 * lmax + 4;
+  // H of a span is at most match x its shorter side.  Where that can pass 32767 (long chunks only: match <= 31 inside the
+  // envelope, and outside it every chunk is a long one) the rows are the reference's int32 ones, on the one-lane kernel.
+  const bool wide_rows = (uint64_t)p.match * lmax > 32767;
+  if (tune.debug && wide_rows && p.report_cigar) fprintf(stderr, "[kslam] cigar: int32 rows (match %d x longest read %u)\n", p.match, lmax);
   if (p.report_cigar) {
     W.counters.ensure(16 * sizeof(uint32_t));
     uint32_t *cnt = W.counters.as<uint32_t>();   // [0..7] bin list sizes, [8] handed back, [9] long cigars, [10] tracebacks of a systolic launch, [11] classes present (generic loop)
@@ -848,7 +866,7 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
     // one attempt for the candidates of J.items with the systolic kernel; false when the band is too wide for it
     auto launch_systolic = [&](const CigJob &J, uint32_t slot_bw, uint32_t bin) -> bool {
       const uint32_t need = 2 * slot_bw + 1;
-      if (need > 256 || !((sys_mask >> std::min(bin, 7u)) & 1)) return false;
+      if (need > 256 || wide_rows || !((sys_mask >> std::min(bin, 7u)) & 1)) return false;
       const uint64_t m = J.items.cap;
       const int lm = lmax <= 160 ? 0 : (lmax <= 256 ? 1 : 2);
       const uint32_t LM = lm == 0 ? 160 : (lm == 1 ? 256 : 512);
@@ -901,19 +919,20 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
       // against 2.8 ms).
       Y.nch = ((lmax + 30) >> 4) + 1;   // 15 bytes of misalignment in front, up to 15 behind
       // narrow bands: the band in registers (KSLAM_CIGAR_REG=0 turns it off)
-      const bool use_reg = tune.cigar_reg && !no_reg;
+      const bool use_reg = tune.cigar_reg && !no_reg && !wide_rows;
       // (a class-0 candidate has band 1: three slots, not the five of the band-2 instantiation it used to share)
       const uint32_t reg_bw = (!use_reg || J.big) ? 0u : (slot_bw <= 1 ? 1u : (slot_bw <= 2 ? 2u : (slot_bw <= 4 ? 4u : (slot_bw <= 8 ? 8u : (slot_bw <= 16 ? 16u : 0u)))));
       // The register kernels keep no row arrays in LDS (round 6): a candidate they cannot hold -- a window no longer than its
       // band -- goes to the one-lane kernel through the same list the systolic kernels hand theirs over on.  3-5 KB less per
       // workgroup: 13 instead of 10 workgroups per CU for band 2.
       if (reg_bw) Y.W1 = 0;
-      const size_t per_lane = (size_t)2 * Y.nch * 8 + (size_t)3 * Y.W1 * sizeof(int16_t);
+      const size_t row_size = wide_rows ? sizeof(int32_t) : sizeof(int16_t);
+      const size_t per_lane = (size_t)2 * Y.nch * 8 + (size_t)3 * Y.W1 * row_size;
       uint32_t nl = 64;
       while (nl > 1 && per_lane * nl + 64 > 64 * 1024) nl >>= 1;   // <= 64 KB: at least two blocks per CU
       Y.nl = nl;
       const size_t half = (size_t)Y.nch * nl * 8;
-      const size_t rows_bytes = ((size_t)3 * Y.W1 * nl * sizeof(int16_t) + 15) & ~(size_t)15;
+      const size_t rows_bytes = ((size_t)3 * Y.W1 * nl * row_size + 15) & ~(size_t)15;
       const size_t lds = 2 * half + rows_bytes;
       if (lds > 160 * 1024) throw StatusError{KSLAM_ERR_UNSUPPORTED, "banded traceback band does not fit LDS"};
       if (lds > 64 * 1024)
@@ -922,7 +941,8 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
                               reinterpret_cast<const void *>(&k_banded_lds<2>),
                               reinterpret_cast<const void *>(&k_banded_lds<4>),
                               reinterpret_cast<const void *>(&k_banded_lds<8>),
-                              reinterpret_cast<const void *>(&k_banded_lds<16>)})
+                              reinterpret_cast<const void *>(&k_banded_lds<16>),
+                              reinterpret_cast<const void *>(&k_banded_lds_wide)})
           HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       uint64_t slab = (uint64_t)lmax * std::max<uint32_t>(Y.wd, reg_bw ? 8u : 0u) * nl;   // direction bytes per block; the
       slab = (slab + 255) & ~255ull;   // register variant stores <= 8 bytes per row and lane
@@ -936,7 +956,8 @@ void cigar_traceback(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, u
         Jl.items = part(J.items, b0 * nl, std::min<uint64_t>(nb_here * nl, m - b0 * nl));
         Jl.scratch = W.scratch.as<uint8_t>();
         Jl.wave_slab = slab;
-        if (reg_bw == 1) hipLaunchKernelGGL(k_banded_lds<1>, dim3((unsigned)nb_here), dim3(64), lds, s, Jl, in, p, Y);
+        if (wide_rows) hipLaunchKernelGGL(k_banded_lds_wide, dim3((unsigned)nb_here), dim3(64), lds, s, Jl, in, p, Y);
+        else if (reg_bw == 1) hipLaunchKernelGGL(k_banded_lds<1>, dim3((unsigned)nb_here), dim3(64), lds, s, Jl, in, p, Y);
         else if (reg_bw == 2) hipLaunchKernelGGL(k_banded_lds<2>, dim3((unsigned)nb_here), dim3(64), lds, s, Jl, in, p, Y);
         else if (reg_bw == 4) hipLaunchKernelGGL(k_banded_lds<4>, dim3((unsigned)nb_here), dim3(64), lds, s, Jl, in, p, Y);
         else if (reg_bw == 8) hipLaunchKernelGGL(k_banded_lds<8>, dim3((unsigned)nb_here), dim3(64), lds, s, Jl, in, p, Y);

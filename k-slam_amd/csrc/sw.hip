@@ -1018,7 +1018,9 @@ __global__ __launch_bounds__(64) void k_sw_long(kslam_overlap *__restrict__ ov, 
 
 // ---- scoring outside the envelope: the reference's striped kernels evaluated LITERALLY ------------------------------
 // Inside `1 <= gapE < gapO, mismatch <= gapO + gapE` the striped evaluation order of sw_sse2_byte / sw_sse2_word is not
-// observable and every kernel above computes a plain Gotoh recurrence.  Outside it the reference's answer depends on its
+// observable and every kernel above computes a plain Gotoh recurrence -- as long as no alignment of the batch can reach
+// 32 767, where the word pass saturates (adds_epi16): a chunk with match x longest read > 32 767 comes here too, whatever
+// its scoring (sw_scores), because the reference then reports the cell at which its lanes first saturated.  Outside it the reference's answer depends on its
 // layout: the Lazy-F loop only EXTENDS F and E is never refreshed after the correction (src/ssw.c:274-305, 512-526), so a
 // candidate's score is what 16 (byte) or 8 (word) SSE lanes of segLen = ceil(readLen / lanes) cells each produce in that
 // order.  `SLAM --gap-open / --gap-extend` takes any value (src/main.cpp:44-55), so this kernel plays the lanes: one
@@ -1026,7 +1028,8 @@ __global__ __launch_bounds__(64) void k_sw_long(kslam_overlap *__restrict__ ov, 
 // segLen x W cells, the query profile is computed on the fly.  It follows sw_sse2_byte (src/ssw.c:143-383) and sw_sse2_word
 // (:408-592) statement by statement -- the tests hold it to the real ssw.c on scorings outside the envelope -- and
 // ssw_align's sequence (:870-923): byte pass, word pass when the byte pass saturates, reverse pass over the reversed
-// prefixes with `terminate = score1`.  Slow (~20 us of one wavefront per candidate) and exact.
+// prefixes with `terminate = score1`.  Slow and exact: ~20 us of one wavefront per 120-base candidate, and by the square of the
+// length from there (measured: 3.4 s for a 6 500-base candidate, 6.5 s for one of 9 000 bases).
 struct StripedEnd { int32_t score, ref, read; };
 
 template <int W>
@@ -1224,11 +1227,19 @@ void sw_scores(kslam_overlap *d_ov, uint64_t n, SwInputs in, SwParams p, uint32_
   if (n == 0) return;
   if (long_reads) {   // a chunk of reads the packed kernels cannot hold: every candidate through the plain two-pass kernel
     const uint32_t lcap = (max_read_len + 15u) & ~15u;
+    // ... unless the reference's word pass could saturate (adds_epi16, src/ssw.c:487): a cell's true H is at most match x the
+    // read's length, and a saturated sum differs from the true one only above 32767 (at exactly 32767 both forms hold the same
+    // number).  From match x longest read >= 32768 on the reference's answer is what its saturated lanes give -- ends cut at
+    // the first column that reaches 32767 -- so such a chunk goes through the literal kernel, whatever the scoring.
+    if ((uint64_t)p.match * max_read_len > 32767) p.striped = 1;
+    if (tune.debug)
+      fprintf(stderr, "[kslam] SW long chunk: %llu candidates through %s (longest read %u)\n", (unsigned long long)n,
+              p.striped ? "k_sw_striped" : "k_sw_long", max_read_len);
     const size_t lds = (size_t)4 * (lcap + 2) * sizeof(int32_t) + 2 * ((size_t)lcap + 16);
     if (lds > 160 * 1024) throw StatusError{KSLAM_ERR_UNSUPPORTED, "reads longer than 9000 bases are not supported"};
     if (lds > 64 * 1024)
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sw_long), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (p.striped) {   // scoring outside the envelope: the reference's striped evaluation, literally
+    if (p.striped) {   // scoring outside the envelope, or scores that can saturate: the reference's striped evaluation, literally
       const size_t lds2 = (size_t)4 * (lcap + 16) * sizeof(uint16_t) + 2 * ((size_t)lcap + 16);
       if (lds2 > 64 * 1024)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sw_striped), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));

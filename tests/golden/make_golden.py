@@ -17,6 +17,8 @@
    (oracle/_ref/libjoin_ref.so, one OpenMP thread), plus the (read, entry, rel) keys whose revComp is a tie.
  * align_vectors.npz   : ASCII (query, ref, ref_len) triples with the answers of the reference's OWN
    Aligner::Align at three filter settings.
+ * ssw_saturation_vectors.npz : the vectors of tests/sw_literal_cases.py on which the reference's word pass saturates at
+   32 767 (and their neighbours just below), with the answers of the reference's own ssw_init + ssw_align.
  * slam_loop.npz       : two small FASTQ pairs + databases + taxDB with the files the reference's OWN batch
    loop metagenomicAnalysis_Low_Mem wrote for them (oracle/_ref/libslam_ref.so): SAM, XML report,
    _abbreviated, _PerRead.
@@ -240,6 +242,27 @@ def make_join_and_align_vectors():
     print("align_vectors.npz: %d scorings x 3 filter settings" % len(param_sets))
 
 
+def make_saturation_vectors():
+    """ssw_saturation_vectors.npz: the word-saturation vectors of tests/sw_literal_cases.py (families S6 and S9: every
+    candidate of the cases of up to 1200 bases, and two of 9000) as (read codes, window codes, scoring) with the answers of
+    the reference's own ssw_init + ssw_align (oracle/_ref/libssw_ref.so)."""
+    import oracle as O
+    import test_sw_literal_cases as T
+    assert O.have_ref_ssw(), "needs oracle/_ref (reference present)"
+    cases = []
+    for sc, rd, win in T.saturation_vectors(O, T.STORED_SHORT, T.STORED_LONG):
+        res, cig = O.ref_ssw_align(rd, win, O.build_matrix(sc[0], sc[1]), sc[2], sc[3])
+        cases.append((sc, rd, win, res, cig))
+    np.savez_compressed(
+        os.path.join(HERE, "ssw_saturation_vectors.npz"),
+        params=np.array([c[0] for c in cases], dtype=np.int32),
+        reads=np.concatenate([c[1] for c in cases]), read_len=np.array([len(c[1]) for c in cases]),
+        refs=np.concatenate([c[2] for c in cases]), ref_len=np.array([len(c[2]) for c in cases]),
+        results=np.array([c[3] for c in cases], dtype=np.int32),
+        cigars=np.concatenate([c[4] for c in cases]), cigar_len=np.array([len(c[4]) for c in cases]))
+    print("ssw_saturation_vectors.npz: %d vectors, %d saturated" % (len(cases), sum(c[3][0] == 32767 for c in cases)))
+
+
 def make_slam_loop():
     import importlib
     import tempfile
@@ -312,6 +335,9 @@ if __name__ == "__main__":
         make_slam_loop()
         make_c1_golden()
         sys.exit(0)
+    if "--saturation" in sys.argv:     # only ssw_saturation_vectors.npz
+        make_saturation_vectors()
+        sys.exit(0)
     if "--taxonomy" in sys.argv:
         make_taxonomy_cases()
         sys.exit(0)
@@ -320,5 +346,6 @@ if __name__ == "__main__":
     make_fastq_cases()
     make_taxonomy_cases()
     make_join_and_align_vectors()
+    make_saturation_vectors()
     make_slam_loop()
     make_c1_golden()

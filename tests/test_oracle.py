@@ -144,8 +144,9 @@ def _random_pair(rng):
 @pytest.mark.parametrize("params,n", [((2, 3, 5, 2), 3000), ((1, 4, 6, 1), 800), ((2, 6, 5, 1), 800),
                                       ((3, 2, 4, 3), 800)])
 def test_plain_spec_equals_striped(oracle, params, n):
-    """The plain-Gotoh spec the HIP kernel implements == the striped emulation, inside the
-    scoring envelope kslam_create accepts (gapE < gapO, mismatch <= gapO + gapE)."""
+    """The plain-Gotoh spec the HIP kernels implement == the striped emulation, inside the scoring envelope of the fast
+    kernels (gapE < gapO, mismatch <= gapO + gapE) -- and, the third condition, as long as no alignment can reach 32 767,
+    where the reference's word pass saturates: test_plain_spec_equals_striped_up_to_saturation below."""
     rng = np.random.default_rng(sum(params))
     mat = oracle.build_matrix(params[0], params[1])
     for i in range(n):
@@ -155,6 +156,34 @@ def test_plain_spec_equals_striped(oracle, params, n):
         assert (a.score1, a.ref_begin1, a.ref_end1, a.read_begin1, a.read_end1) == \
                (b.score1, b.ref_begin1, b.ref_end1, b.read_begin1, b.read_end1), i
         assert np.array_equal(ca, cb), i
+
+
+def test_plain_spec_equals_striped_up_to_saturation(oracle):
+    """The envelope's third condition, on the in-envelope saturation vectors of tests/sw_literal_cases.py (family S9, match x
+    length around 32 767): the plain spec equals the striped emulation on every candidate whose plain score is at most
+    32 766 and differs on every one above (adds_epi16 holds 32 767 at most, and the reference then reports the cell at
+    which its lanes first got there).  A plain score of exactly 32 767 is the same number in both forms: equal."""
+    import sw_literal_cases as C
+    from test_sw_literal_cases import rows_of, same_rows
+    below = above = 0
+    for name in C.names("S9"):
+        B, sc = C.build(name), C.CASES[name][1]
+        a, ca = rows_of(oracle, name)
+        b, cb = rows_of(oracle, name, plain=True)
+        same = same_rows(a, ca, b, cb)
+        for k in range(len(a)):
+            L = len(B.reads[int(b["read"][k])])
+            plain_score = int(b["score"][k])
+            if sc[0] * L > 65535:          # the uint16 field may have wrapped: the planted alignment bounds the score from below
+                assert sc[0] * (L - 12) - 9 * sc[1] - 3 * (sc[2] + 2 * sc[3]) > C.SAT
+                plain_score = C.SAT + 1
+            if plain_score <= C.SAT:
+                assert same[k], (name, k, plain_score)
+                below += 1
+            else:
+                assert not same[k] and int(a["score"][k]) == C.SAT, (name, k, plain_score)
+                above += 1
+    assert below >= 10 and above >= 20, (below, above)
 
 
 def test_against_real_ssw_when_present(oracle):
