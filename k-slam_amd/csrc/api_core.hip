@@ -243,6 +243,7 @@ void kslam_destroy(kslam_ctx *c) {
     for (auto &ev : c->evs1) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->cov.ev_count) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->var.ev_take) if (ev) (void)hipEventDestroy(ev);
+    for (auto &ev : c->ind.ev_take) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->cns.ev_take) if (ev) (void)hipEventDestroy(ev);
     bamsort_destroy(c);
     for (auto &ev : c->dep.ev) if (ev) (void)hipEventDestroy(ev);

@@ -291,6 +291,8 @@ struct LaneBatch {
     // (kslam_set_variants) the batch's mismatch events and covered intervals into the owner's state, on this lane's stream and
     // outside the compute token as well; the batches left to the host go in through kslam_variants_add after the host stage
     feed(primary->var.on, [&] { variants_emit_resident(primary, c); });
+    // (kslam_set_indels) the batch's normalised deletions and insertions and its covered intervals into the owner's state, likewise
+    feed(primary->ind.on, [&] { indels_emit_resident(primary, c); });
     // (kslam_set_consensus) the batch's intervals, events and insertions into the owner's state, likewise
     feed(primary->cns.on, [&] { consensus_emit_resident(primary, c); });
     // (kslam_set_depth) the batch's M runs as interval boundaries into the owner's state, likewise

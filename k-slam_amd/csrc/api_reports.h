@@ -1,4 +1,4 @@
-// api_reports.h -- what the opt-in reports behind the C ABI share (api_coverage.hip, api_variants.hip, api_depth.hip,
+// api_reports.h -- what the opt-in reports behind the C ABI share (api_coverage.hip, api_variants.hip, api_indels.hip, api_depth.hip,
 // api_kreport.hip, api_genes.hip, api_readqc.hip, api_alignqc.hip, api_consensus.hip, api_bamsort.hip; the reads of chosen taxa, api_taxreads.hip, are released with
 // them): their entry points for the lanes, the lists of what an index or a tree takes with it, and the shell of their ABI
 // functions.  Each file keeps what is its own: its table layout, its switch-on preconditions, its zeroing, its take.
@@ -18,6 +18,12 @@ void coverage_mark_resident(kslam_ctx *owner, kslam_ctx *lane);
 void variants_release(kslam_ctx *c);
 // the batch `lane` has just finished (lane->pres over lane->res_ov, lane->res_cig and lane's reads) into owner's state, on lane's stream
 void variants_emit_resident(kslam_ctx *owner, kslam_ctx *lane);
+
+// ---- api_indels.hip
+// frees the indel state of c and switches it off (kslam_set_indels(c, 0), kslam_set_index)
+void indels_release(kslam_ctx *c);
+// the batch `lane` has just finished (as variants_emit_resident sees it) into owner's state, on lane's stream
+void indels_emit_resident(kslam_ctx *owner, kslam_ctx *lane);
 
 // ---- api_depth.hip
 // frees the depth state of c and switches it off (kslam_set_depth(c, 0), kslam_set_index)
@@ -88,6 +94,7 @@ inline void release_tree_bound_reports(kslam_ctx *c) {
 inline void release_index_bound_reports(kslam_ctx *c) {
   coverage_release(c);   // (include/kslam_coverage.h) the table was laid out for the old index's entries
   variants_release(c);   // (include/kslam_variants.h) the keys hold the old index's base positions
+  indels_release(c);     // (include/kslam_indels.h) likewise
   depth_release(c);      // (include/kslam_depth.h) likewise, and the spare position per entry besides
   kreport_release(c);    // (include/kslam_kreport.h) the annotations, and the tree with them, belong to the old index's entries
   taxreads_release(c);   // (include/kslam_taxreads.h) likewise

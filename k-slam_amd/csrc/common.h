@@ -930,6 +930,28 @@ void run_heads_device(const uint64_t *key, uint64_t n, uint32_t *head, hipStream
 // starts[run[i]] = i for every i < n with head[i] (run: the exclusive scan of the heads)
 void run_starts_device(const uint32_t *head, const uint32_t *run, uint64_t n, uint32_t *starts, hipStream_t s);
 
+// ------------------------------------------------------------- indels.hip
+// The indel table (include/kslam_indels.h).  The state -- the interval arrays, 8-byte deletion keys and 16-byte insertion
+// records -- belongs to the context the switch was set on (context.h: kslam_ctx::Indels); the emit shell and the take's buffers
+// are the SNV table's.  INDEL_LONG is a kind for the shell's sake alone: the anchored D runs that are too long are summed by its
+// scan and nothing is written for them.
+enum { INDEL_IV = 0, INDEL_DEL = 1, INDEL_INS = 2, INDEL_LONG = 3, INDEL_KINDS = 4 };
+struct IndelKeys {                // where a batch's keys go
+  uint64_t *ib, *ie, *del, *ins;  // ins: two words per record
+};
+// the list, the counting walk and the scans; fills W.n_list / n[kind] / n_skipped / n_unanchored / n_unrepresentable (waits)
+void indels_count_device(const VariantInputs &in, EmitWork &W, hipStream_t s);
+// the writing walk of the batch counted last (the caller made room for W.n[kind] of each); waits for the stream and fills W.ms
+void indels_write_device(const VariantInputs &in, EmitWork &W, const IndelKeys &at, hipStream_t s);
+// sorts the four arrays in place: the rows' order
+void indels_sort_device(VariantTakeWork &T, DevBuf &begins, DevBuf &ends, uint64_t n_iv, DevBuf &dels, uint64_t n_del, DevBuf &ins, uint64_t n_ins,
+                        uint64_t total_bases, hipStream_t s);
+// the rows of ONE kind (KSLAM_INDEL_DEL: keys = the sorted deletion keys, KSLAM_INDEL_INS: the sorted insertion records) that
+// pass the filter into T.rows (device, kslam_indel_row); waits for the stream
+void indels_take_device(VariantTakeWork &T, int kind, const uint64_t *keys, uint64_t n_keys, const uint64_t *begins, const uint64_t *ends, uint64_t n_iv,
+                        const uint64_t *d_goff, uint64_t n_entries, uint32_t min_alt, uint32_t min_depth, uint64_t *n_sites_out, uint64_t *n_rows_out,
+                        hipStream_t s);
+
 // ------------------------------------------------------------ alignqc.hip
 // The alignment QC report (include/kslam_alignqc.h).  The state -- one block of 64-bit counters -- belongs to the context the
 // switch was set on (context.h: kslam_ctx::AlignQc); each lane counts its batch with an AlignQcWork of its own.

@@ -16,7 +16,7 @@
 //   5. the caller makes room (api_consensus.hip: under the state's lock)
 //   6. k_cns_write   the same walk writes the keys through a CnsSink<WriteEmit>
 // The walk is the SNV table's and the depth track's, with the widest sink: every differing column, the D runs, and the I runs,
-// whose bases (at most 32) are read bytewise by this sink alone.
+// whose bases (at most 32) are read bytewise (insertion_bases, shared with indels.hip).
 // On request (consensus_sort_device, consensus_take_device): radix_sort of the six arrays; one thread per ENTRY marks the entries
 // holding an M or D run, a scan lists them; the host cuts the list into slices of whole entries; per slice
 //   k_cns_call    one thread per position: m and dl by two binary searches each over the sorted interval arrays, the position's
@@ -65,24 +65,8 @@ struct WriteEmit {
   }
 };
 
-// the oriented bases of the I run at query positions qp .. qp + len - 1 (inside the read: the fit check covered them), bytewise,
-// at 2 bits each, the first one highest; false: one of them is not ACGT.  len <= 32.
-__device__ inline bool insertion_bases(const kslam_overlap &o, const VariantInputs &in, const RecordFrame &f, int64_t qp, uint32_t len, uint64_t *bases) {
-  uint64_t w = 0;
-  bool ok = true;
-  for (uint32_t j = 0; j < len; j++) {
-    const int64_t q = qp + (int64_t)j;
-    const uint32_t b = o.revcomp ? complement(in.rbases[f.rb + (uint64_t)(f.L - 1 - q)]) : (uint32_t)in.rbases[f.rb + (uint64_t)q];
-    const uint32_t code = acgt(b);
-    ok = ok && code < 4u;
-    w = (w << 2) | (code & 3u);
-  }
-  *bases = w;
-  return ok;
-}
-
-// the walk's sink (pileup_walk.h): M and D runs as closed intervals, every differing column with its code 0 .. 4, and the I runs
-// -- the only sink that reads an I run's bases
+// the walk's sink (pileup_walk.h): M and D runs as closed intervals, every differing column with its code 0 .. 4, and the I runs,
+// whose bases insertion_bases (pileup_walk.h) reads
 template <class Emit>
 struct CnsSink : Emit {
   static constexpr bool COLUMNS = true, INSERTIONS = true;

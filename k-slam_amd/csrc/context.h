@@ -9,7 +9,7 @@
 //   api_multi.hip  several devices: shard export / merge, kslam_multi_*
 //   api_readsplit.hip  the reads split by outcome, cut out of the uploaded text
 //   api_taxreads.hip   the reads of chosen taxa, likewise
-//   api_coverage.hip, api_variants.hip, api_depth.hip, api_kreport.hip, api_genes.hip, api_readqc.hip, api_alignqc.hip,
+//   api_coverage.hip, api_variants.hip, api_indels.hip, api_depth.hip, api_kreport.hip, api_genes.hip, api_readqc.hip, api_alignqc.hip,
 //   api_consensus.hip, api_bamsort.hip
 //                  the opt-in reports the lanes feed, one file each; what they share is in api_reports.h (included below)
 #pragma once
@@ -29,6 +29,7 @@
 #include "../../include/kslam_readsplit.h"
 #include "../../include/kslam_coverage.h"
 #include "../../include/kslam_variants.h"
+#include "../../include/kslam_indels.h"
 #include "../../include/kslam_depth.h"
 #include "../../include/kslam_kreport.h"
 #include "../../include/kslam_readqc.h"
@@ -245,6 +246,24 @@ struct kslam_ctx {
     std::mutex mu;                // append / take / reset / the switch: one at a time
   } var;
   EmitWork varw;                  // this context's own emit passes (a lane's batches; on the primary: kslam_variants_add)
+
+  // ---- the indel table (indels.hip, include/kslam_indels.h) ----
+  struct Indels {                 // on the context the switch was set on; its lanes append to it (lane_main)
+    std::atomic<bool> on{false};
+    uint64_t n_entries = 0, total_bases = 0;
+    DevBuf begins, ends, dels, ins;   // u64 keys (ins: two per record), append-only between two resets; n[kind] of them are in use
+    uint64_t n[INDEL_KINDS] = {0, 0, 0, 0};   // n[INDEL_LONG]: the D runs too long to be counted (nothing is stored for them)
+    uint64_t n_records = 0, n_skipped = 0, n_unanchored = 0, n_unrepresentable = 0;
+    bool sorted = false;          // nothing was appended since kslam_indels_take sorted the arrays
+    VariantTakeWork tw;
+    BatchUpload up;               // kslam_indels_add's
+    hipEvent_t ev_take[2]{};
+    double take_ms = 0;
+    int stream_fd = -1;           // kslam_stream_set_indels
+    uint32_t stream_min_alt = 2, stream_min_depth = 1;
+    std::mutex mu;                // append / take / reset / the switch: one at a time
+  } ind;
+  EmitWork indw;                  // this context's own emit passes (a lane's batches; on the primary: kslam_indels_add)
 
   // ---- the consensus caller (consensus.hip, include/kslam_consensus.h) ----
   struct Consensus {              // on the context the switch was set on; its lanes append to it (lane_main)

@@ -83,6 +83,22 @@ __device__ inline bool record_frame(const kslam_overlap &o, const VariantInputs 
   return true;
 }
 
+// the oriented bases of the I run at query positions qp .. qp + len - 1 (inside the read: the fit check covered them), bytewise,
+// at 2 bits each, the first one highest; false: one of them is not ACGT.  len <= 32.  (consensus.hip, indels.hip)
+__device__ inline bool insertion_bases(const kslam_overlap &o, const VariantInputs &in, const RecordFrame &f, int64_t qp, uint32_t len, uint64_t *bases) {
+  uint64_t w = 0;
+  bool ok = true;
+  for (uint32_t j = 0; j < len; j++) {
+    const int64_t q = qp + (int64_t)j;
+    const uint32_t b = o.revcomp ? complement(in.rbases[f.rb + (uint64_t)(f.L - 1 - q)]) : (uint32_t)in.rbases[f.rb + (uint64_t)q];
+    const uint32_t code = acgt(b);
+    ok = ok && code < 4u;
+    w = (w << 2) | (code & 3u);
+  }
+  *bases = w;
+  return ok;
+}
+
 // Walks a record into `sink`; false: the record is skipped (nothing was handed to the sink).  rp and qp are positions in the
 // entry and in the oriented query; the sink forms its keys from them and the frame.  Runs of length 0 are not handed over.
 //   sink.m_run(o, f, rp, len), sink.d_run(o, f, rp, len)      an M run, a D run

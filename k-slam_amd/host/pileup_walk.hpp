@@ -51,6 +51,20 @@ inline void oriented_query(std::string &query, const uint8_t *read, int64_t L, b
     for (int64_t j = 0; j < L; j++) query[(size_t)j] = (char)complement(read[L - 1 - j]);
 }
 
+// the bases query[qp .. qp + len) of an I run at 2 bits each, the first one highest (len <= 32); false: one of them is not
+// upper-case ACGT (csrc/pileup_walk.h: insertion_bases)
+inline bool insertion_bases(const std::string &query, int64_t qp, int64_t len, uint64_t *bases) {
+  uint64_t w = 0;
+  bool ok = true;
+  for (int64_t j = 0; j < len; j++) {
+    const int code = acgt((uint8_t)query[(size_t)(qp + j)]);
+    ok = ok && code < 4;
+    w = (w << 2) | (uint64_t)(code & 3);
+  }
+  *bases = w;
+  return ok;
+}
+
 // Every overlap record a live alignment pair names, once, ascending: fn(o, L, ref_len, holds) with the read's and the entry's
 // length.  holds == false: the record is skipped -- its entry is not of the index, its CIGAR is empty, ref_begin < 0, or the CIGAR
 // leaves the read or the entry (L and ref_len are 0 for the first three).  Returns kslam_batch::check's fault (Level::records),

@@ -37,6 +37,7 @@
 #include "../../include/kslam_readqc.h"
 #include "../../include/kslam_taxreads.h"
 #include "../../include/kslam_variants.h"
+#include "../../include/kslam_indels.h"
 #include "../../include/kslam_consensus.h"
 #include "../../include/kslam_bamsort.h"
 #include "../../include/kslam_depth.h"
@@ -184,6 +185,26 @@ struct VariantsReport : Report {
     kslam_variant_stats vs;
     taken(e.ctx, kslam_variants_take(e.ctx, min_alt, min_depth, &rows.p, &n_rows, &vs));
     written(kslam_variants_write(e.index, rows.p, n_rows, &vs, fd));
+  }
+};
+
+// the indel table (include/kslam_indels.h): as the SNV table
+struct IndelsReport : Report {
+  uint32_t min_alt = 2, min_depth = 1;
+  void want(kslam_ctx *ctx) override { got(kslam_stream_get_indels(ctx, &fd, &min_alt, &min_depth)); }
+  void arm(kslam_ctx *ctx) override { if (fd >= 0) started(ctx, kslam_set_indels(ctx, 1), kslam_indels_reset); }
+  void disarm(kslam_ctx *ctx) override { if (armed) kslam_set_indels(ctx, 0); if (ctx) kslam_stream_set_indels(ctx, -1, 2, 1); }
+  void add(kslam_ctx *ctx, const kslam_batch_result &res, Columns &columns) override {
+    const kslam_reads_columns &rc = columns.get();
+    taken(ctx, kslam_indels_add(ctx, res.overlaps, res.n_overlaps, res.cigar_pool, res.n_cigar, rc.bases, rc.bases_off, rc.n_reads,
+                                res.read_pairs, res.n_read_pairs, res.pairs, res.n_pairs));
+  }
+  void finish(const Ending &e) override {
+    Pinned<kslam_indel_row> rows{e.ctx};
+    uint64_t n_rows = 0;
+    kslam_indel_stats is;
+    taken(e.ctx, kslam_indels_take(e.ctx, min_alt, min_depth, &rows.p, &n_rows, &is));
+    written(kslam_indels_write(e.index, rows.p, n_rows, &is, fd));
   }
 };
 
@@ -346,10 +367,10 @@ struct Run {
   uint64_t p1 = 0, p2 = 0, done_pairs = 0;
   uint32_t passes_left = 0;
   bool exhausted = false;
-  CoverageReport coverage; VariantsReport variants; ConsensusReport consensus; DepthReport depth_track; ReadQcReport read_qc; AlignQcReport align_qc;
+  CoverageReport coverage; VariantsReport variants; IndelsReport indels; ConsensusReport consensus; DepthReport depth_track; ReadQcReport read_qc; AlignQcReport align_qc;
   GenesReport genes; KrakenReport kreport;   // armed behind the annotations, which drop them
   // in the order they are fed and finished: it decides which error is reported if two fail
-  Report *const reports[8] = {&coverage, &genes, &kreport, &variants, &consensus, &read_qc, &align_qc, &depth_track};
+  Report *const reports[9] = {&coverage, &genes, &kreport, &variants, &indels, &consensus, &read_qc, &align_qc, &depth_track};
 
   void check_arguments(const kslam_stream_stats *stats, uint32_t *const *tax_ids_out) {
     if (!ctx || !index || !P || !stats) fail(KSLAM_ERR_ARG, "null argument");
@@ -407,7 +428,7 @@ struct Run {
       sort_armed = true;
       if (kslam_bam_sort_reset(ctx) != KSLAM_OK) fail(KSLAM_ERR_STATE, kslam_last_error(ctx));
     }
-    Report *const ahead_of_the_annotations[] = {&coverage, &variants, &consensus, &depth_track, &read_qc, &align_qc};
+    Report *const ahead_of_the_annotations[] = {&coverage, &variants, &indels, &consensus, &depth_track, &read_qc, &align_qc};
     for (Report *r : ahead_of_the_annotations) {
       r->want(ctx);
       r->arm(ctx);

@@ -58,12 +58,14 @@ def classify_stream_native(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_bat
                            sam_fd=-1, per_read_fd=-1, sam_header=None, max_pairs_total=0, depth=0, passes=1, host_threads=0, pool_threads=0,
                            reads_out_fds=None, coverage_fd=-1, variants_fd=None, variants_min_alt=2, variants_min_depth=1, kreport_fd=-1, consensus_fd=None, consensus_params=None,
                            taxon_reads_fds=None, depth_fd=None, depth_min=1, read_qc_fd=-1, read_qc_max_cycles=0, genes_fd=-1,
-                           align_qc_fd=-1, align_qc_max_cycles=0, sam_sorted=False, sam_index_fd=None):
+                           align_qc_fd=-1, align_qc_max_cycles=0, sam_sorted=False, sam_index_fd=None, indels_fd=None, indels_min_alt=2, indels_min_depth=1):
     """kslam_stream_classify: the same loop as classify_stream below, inside the library (no Python between the batches).
     Single-end data: params.paired = 0, r2_ptr = None, len2 = 0.
     reads_out_fds: four descriptors for the classified R1 / R2 and unclassified R1 / R2 records (kslam_amd.readsplit; -1 = not wanted).
     coverage_fd: an open descriptor for the per-entry coverage report (kslam_amd.coverage; -1 = none).
     variants_fd: an open descriptor for the VCF file of the SNV table (kslam_amd.variants; None = none) with its two thresholds;
+    the context needs report_cigar.
+    indels_fd: an open descriptor for the VCF file of the indel table (kslam_amd.indels; None = none) with its two thresholds;
     the context needs report_cigar.
     consensus_fd: an open descriptor for the consensus FASTA (kslam_amd.consensus; None = none) with consensus_params =
     (min_depth, call_permille, fill, min_covered), None = (1, 500, N, 1); the context needs report_cigar.
@@ -99,6 +101,9 @@ def classify_stream_native(ctx, index, r1_ptr, len1, r2_ptr, len2, pairs_per_bat
     if variants_fd is not None and variants_fd >= 0:
         from . import variants as VR
         VR.stream_set_variants(ctx, variants_fd, variants_min_alt, variants_min_depth)
+    if indels_fd is not None and indels_fd >= 0:
+        from . import indels as ID
+        ID.stream_set_indels(ctx, indels_fd, indels_min_alt, indels_min_depth)
     if depth_fd is not None and depth_fd >= 0:
         from . import depth as DP
         DP.stream_set_depth(ctx, depth_fd, depth_min)

@@ -21,6 +21,7 @@ g++ $FLAGS -fsanitize=address,undefined tools/readqc_check.cpp k-slam_amd/host/r
 g++ $FLAGS -fsanitize=address,undefined tools/genes_check.cpp k-slam_amd/host/genes.cpp -o $T/gn_asan
 g++ $FLAGS -fsanitize=address,undefined tools/alignqc_check.cpp k-slam_amd/host/alignqc.cpp -o $T/aq_asan
 g++ $FLAGS -fsanitize=address,undefined tools/bamsort_check.cpp k-slam_amd/host/bamsort.cpp -o $T/bs_asan
+g++ $FLAGS -fsanitize=address,undefined tools/indels_check.cpp k-slam_amd/host/indels.cpp -o $T/id_asan
 export ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 TSAN_OPTIONS=halt_on_error=1
 for mode in 0 1 2; do $T/tail_asan 40000 6 2 $mode > /dev/null; $T/tail_tsan 20000 6 2 $mode > /dev/null; done   # mode 2: the batch loop's two-thread host stage
 $T/fq_asan 40000 5 2 > /dev/null
@@ -36,5 +37,6 @@ $T/rq_asan 4000 $T > /dev/null
 $T/gn_asan 20000 $T > /dev/null
 $T/aq_asan 20000 $T > /dev/null
 $T/bs_asan 20000 > /dev/null
+$T/id_asan $T > /dev/null
 rm -rf $T
-echo "sanitizers: clean (ASan+UBSan, TSan) on the host tail, the FASTQ ingest, the database load, the coverage table, the rows for unaligned reads, the Kraken-style report, the reads of chosen taxa, the read QC report, the per-gene table, the alignment QC report and the sorted BAM's twins"
+echo "sanitizers: clean (ASan+UBSan, TSan) on the host tail, the FASTQ ingest, the database load, the coverage table, the rows for unaligned reads, the Kraken-style report, the reads of chosen taxa, the read QC report, the per-gene table, the alignment QC report, the sorted BAM's twins and the indel table"

@@ -13,10 +13,13 @@
 //
 //   SLAM [option] --db=DATABASE R1FILE [R2FILE]
 //
-// Two options that `SLAM --help` does not list yet (its text is pinned by tests/golden/slam_help.txt):
+// Options that `SLAM --help` does not list yet (its text is pinned by tests/golden/slam_help.txt):
 //   --sam-sorted        write --sam-file as a coordinate-sorted BAM (include/kslam_bamsort.h): implies --sam-bam, needs --sam-file;
 //                       the records stay on the GPU until the last batch, the file is written behind it
 //   --sam-index arg     where its BAI index goes (needs --sam-sorted); default: <sam-file>.bai
+//   --indels-out arg    write the insertions and deletions the reads carry, left-normalised, to this file as VCF
+//                       (include/kslam_indels.h); implies what --variants-out implies
+//   --indels-min-alt arg (=2), --indels-min-depth arg (=1)   its filter (need --indels-out)
 #include <algorithm>
 #include <cerrno>
 #include <chrono>
@@ -47,6 +50,7 @@
 #include "../include/kslam_samtext.h"
 #include "../include/kslam_taxreads.h"
 #include "../include/kslam_variants.h"
+#include "../include/kslam_indels.h"
 #include "../include/kslam_consensus.h"
 #include "../include/kslam_bamsort.h"
 #include "../include/kslam_depth.h"
@@ -86,6 +90,9 @@ void logl(const std::string &s) { g_log.line(s); }
 struct Options {
   std::string db, out, sam, classified_out, unclassified_out, coverage_out, variants_out, kraken_report;
   uint32_t variants_min_alt = 2, variants_min_depth = 1;
+  std::string indels_out;                  // --indels-out (include/kslam_indels.h)
+  uint32_t indels_min_alt = 2, indels_min_depth = 1;
+  bool indels_min_alt_given = false, indels_min_depth_given = false;
   bool variants_min_alt_given = false, variants_min_depth_given = false;
   bool sam_sorted = false;                 // --sam-sorted (include/kslam_bamsort.h)
   std::string sam_index;                   // --sam-index
@@ -202,7 +209,7 @@ Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
          PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SORTED, SAM_INDEX, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT,
-         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, CONSENSUS_OUT, CONSENSUS_MIN_DEPTH, CONSENSUS_PERMILLE, CONSENSUS_FILL, CONSENSUS_MIN_COVERED, DEPTH_OUT, DEPTH_MIN, GENES_OUT, QC_OUT, QC_MAX_CYCLES, ALIGN_QC_OUT, ALIGN_QC_MAX_CYCLES, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
+         VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, INDELS_OUT, INDELS_MIN_ALT, INDELS_MIN_DEPTH, CONSENSUS_OUT, CONSENSUS_MIN_DEPTH, CONSENSUS_PERMILLE, CONSENSUS_FILL, CONSENSUS_MIN_COVERED, DEPTH_OUT, DEPTH_MIN, GENES_OUT, QC_OUT, QC_MAX_CYCLES, ALIGN_QC_OUT, ALIGN_QC_MAX_CYCLES, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
       {"score-fraction-threshold", required_argument, nullptr, FRACTION}, {"match-score", required_argument, nullptr, MATCH},
@@ -230,6 +237,9 @@ Options parse(int argc, char **argv) {
       // not in the reference: include/kslam_variants.h
       {"variants-out", required_argument, nullptr, VARIANTS_OUT}, {"variants-min-alt", required_argument, nullptr, VARIANTS_MIN_ALT},
       {"variants-min-depth", required_argument, nullptr, VARIANTS_MIN_DEPTH},
+      // not in the reference: include/kslam_indels.h
+      {"indels-out", required_argument, nullptr, INDELS_OUT}, {"indels-min-alt", required_argument, nullptr, INDELS_MIN_ALT},
+      {"indels-min-depth", required_argument, nullptr, INDELS_MIN_DEPTH},
       // not in the reference: include/kslam_consensus.h
       {"consensus-out", required_argument, nullptr, CONSENSUS_OUT}, {"consensus-min-depth", required_argument, nullptr, CONSENSUS_MIN_DEPTH},
       {"consensus-call-permille", required_argument, nullptr, CONSENSUS_PERMILLE}, {"consensus-fill", required_argument, nullptr, CONSENSUS_FILL},
@@ -281,6 +291,9 @@ Options parse(int argc, char **argv) {
       case READS_OUT_BGZF: o.reads_out_bgzf = true; break;
       case COVERAGE_OUT: o.coverage_out = optarg; break;
       case VARIANTS_OUT: o.variants_out = optarg; break;
+      case INDELS_OUT: o.indels_out = optarg; break;
+      case INDELS_MIN_ALT: o.indels_min_alt = to_u32(optarg, "indels-min-alt"); o.indels_min_alt_given = true; break;
+      case INDELS_MIN_DEPTH: o.indels_min_depth = to_u32(optarg, "indels-min-depth"); o.indels_min_depth_given = true; break;
       case CONSENSUS_OUT: o.consensus_out = optarg; break;
       case CONSENSUS_MIN_DEPTH:
         o.consensus.min_depth = to_u32(optarg, "consensus-min-depth");
@@ -374,6 +387,8 @@ Options parse(int argc, char **argv) {
   if (o.extract_exclude && o.extract_taxids.empty()) die("option '--extract-exclude' needs '--extract-taxid'");
   if (o.variants_min_alt_given && o.variants_out.empty()) die("option '--variants-min-alt' needs '--variants-out'");
   if (o.variants_min_depth_given && o.variants_out.empty()) die("option '--variants-min-depth' needs '--variants-out'");
+  if (o.indels_min_alt_given && o.indels_out.empty()) die("option '--indels-min-alt' needs '--indels-out'");
+  if (o.indels_min_depth_given && o.indels_out.empty()) die("option '--indels-min-depth' needs '--indels-out'");
   if (o.consensus_dependent && o.consensus_out.empty()) die(std::string("option '--") + o.consensus_dependent + "' needs '--consensus-out'");
   if (o.depth_min_given && o.depth_out.empty()) die("option '--depth-min' needs '--depth-out'");
   if (o.qc_max_cycles_given && o.qc_out.empty()) die("option '--qc-max-cycles' needs '--qc-out'");
@@ -584,7 +599,7 @@ int run(const Options &o, const std::string &command_line) {
   kp.gap_extend = o.gap_extend;
   kp.score_threshold = o.score_threshold;
   // reportCigar = a SAM file was asked for (src/SLAM.h:169); the variants walk the CIGARs too (the SAM text follows sp.tail.report_cigar)
-  kp.report_cigar = (want_sam || !o.variants_out.empty() || !o.consensus_out.empty() || !o.depth_out.empty() || !o.align_qc_out.empty()) ? 1 : 0;
+  kp.report_cigar = (want_sam || !o.variants_out.empty() || !o.indels_out.empty() || !o.consensus_out.empty() || !o.depth_out.empty() || !o.align_qc_out.empty()) ? 1 : 0;
   kp.device = o.device;
   kslam_ctx *ctx = nullptr;
   if (kslam_create(&kp, &ctx) != KSLAM_OK) die(std::string("GPU context: ") + (ctx ? kslam_last_error(ctx) : "kslam_create failed"));
@@ -657,6 +672,7 @@ int run(const Options &o, const std::string &command_line) {
       {o.kraken_report, "Kraken-style report", "the Kraken-style report", [ctx, &o](int fd) { return kslam_stream_set_kreport(ctx, fd); }},
       {o.consensus_out, "consensus", "the consensus file", [ctx, &o](int fd) { return kslam_stream_set_consensus(ctx, fd, &o.consensus); }},
       {o.variants_out, "variants", "the variants file", [ctx, &o](int fd) { return kslam_stream_set_variants(ctx, fd, o.variants_min_alt, o.variants_min_depth); }},
+      {o.indels_out, "indels", "the indels file", [ctx, &o](int fd) { return kslam_stream_set_indels(ctx, fd, o.indels_min_alt, o.indels_min_depth); }},
       {o.depth_out, "depth", "the depth file", [ctx, &o](int fd) { return kslam_stream_set_depth(ctx, fd, o.depth_min); }},
       {o.genes_out, "genes", "the gene table", [ctx, &o](int fd) { return kslam_stream_set_genes(ctx, fd); }},
       {o.qc_out, "read QC", "the read QC report", [ctx, &o](int fd) { return kslam_stream_set_read_qc(ctx, fd, o.qc_max_cycles); }},
