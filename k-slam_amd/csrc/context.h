@@ -9,6 +9,7 @@
 //   api_multi.hip  several devices: shard export / merge, kslam_multi_*
 //   api_readsplit.hip  the reads split by outcome, cut out of the uploaded text
 //   api_taxreads.hip   the reads of chosen taxa, likewise
+//   api_gunzip.hip     plain gzip input: the stages of gunzip.hip in order, in rounds
 //   api_coverage.hip, api_variants.hip, api_indels.hip, api_depth.hip, api_kreport.hip, api_genes.hip, api_readqc.hip, api_alignqc.hip,
 //   api_consensus.hip, api_bamsort.hip
 //                  the opt-in reports the lanes feed, one file each; what they share is in api_reports.h (included below)
@@ -19,10 +20,12 @@
 #include "samtext.h"
 #include "bgzf.h"
 #include "inflate.h"
+#include "gunzip.h"
 #include "consensus.h"
 #include "../../include/kslam_samtext.h"
 #include "../../include/kslam_bgzf.h"
 #include "../../include/kslam_inflate.h"
+#include "../../include/kslam_gunzip.h"
 #include "../../include/kslam_bam.h"
 #include "../../include/kslam_samseq.h"
 #include "../../include/kslam_samunmapped.h"
@@ -210,6 +213,9 @@ struct kslam_ctx {
   DevBuf bgzf_out, bgzf_in;
   InflateWork inflw;              // kslam_bgzf_inflate (inflate.hip, include/kslam_inflate.h): one round's bytes, text and members
   double inflate_kernel_ms = 0;   // device time of the last kslam_bgzf_inflate's kernels, by events around each round's launch
+  // ---- plain gzip (gunzip.hip, include/kslam_gunzip.h): the scratch, the two sizes (0: the default), the last call's figures ----
+  GunzipWork gzw;
+  struct { uint64_t chunk = 0, round = 0; kslam_gunzip_stats stats{}; } gz;
   bool in_multi = false;          // one of a kslam_multi's contexts
   // ---- the reads split by outcome (readsplit.hip, include/kslam_readsplit.h) ----
   ReadSplitWork rsw;

@@ -20,6 +20,9 @@
 //   --indels-out arg    write the insertions and deletions the reads carry, left-normalised, to this file as VCF
 //                       (include/kslam_indels.h); implies what --variants-out implies
 //   --indels-min-alt arg (=2), --indels-min-depth arg (=1)   its filter (need --indels-out)
+//   --gunzip            read R1FILE / R2FILE that are plain gzip (RFC 1952: gzip, pigz, `cat a.gz b.gz`), inflated in parallel on
+//                       the GPU (include/kslam_gunzip.h); each file on its own, BGZF keeps its own path.  Without it plain gzip
+//                       is refused
 #include <algorithm>
 #include <cerrno>
 #include <chrono>
@@ -41,6 +44,7 @@
 #include "../include/kslam_bgzf.h"
 #include "../include/kslam_db.h"
 #include "../include/kslam_inflate.h"
+#include "../include/kslam_gunzip.h"
 #include "../include/kslam_samseq.h"
 #include "../include/kslam_samunmapped.h"
 #include "../include/kslam_readsplit.h"
@@ -95,6 +99,7 @@ struct Options {
   bool indels_min_alt_given = false, indels_min_depth_given = false;
   bool variants_min_alt_given = false, variants_min_depth_given = false;
   bool sam_sorted = false;                 // --sam-sorted (include/kslam_bamsort.h)
+  bool gunzip = false;                     // --gunzip (include/kslam_gunzip.h)
   std::string sam_index;                   // --sam-index
   std::string consensus_out;               // --consensus-out (include/kslam_consensus.h)
   kslam_consensus_params consensus{1, 500, KSLAM_CONSENSUS_FILL_N, 1};
@@ -208,7 +213,7 @@ void usage(FILE *o) {
 Options parse(int argc, char **argv) {
   Options o;
   enum { DB = 256, MINSCORE, FRACTION, MATCH, MISMATCH, GAPO, GAPE, NREADS, ATONCE, OUT, SAM, NALIGN, XA, VERSION, JUST, NOPSEUDO, HELP, INPUT,
-         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SORTED, SAM_INDEX, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT,
+         PARSE_FASTA, UNSUPPORTED, DEVICE, IGNORED, SAM_BGZF, SAM_BAM, SAM_SORTED, SAM_INDEX, GUNZIP, SAM_SEQ, SAM_UNMAPPED, SAM_DEFLATE, CLASSIFIED_OUT, UNCLASSIFIED_OUT, READS_OUT_BGZF, COVERAGE_OUT,
          VARIANTS_OUT, VARIANTS_MIN_ALT, VARIANTS_MIN_DEPTH, INDELS_OUT, INDELS_MIN_ALT, INDELS_MIN_DEPTH, CONSENSUS_OUT, CONSENSUS_MIN_DEPTH, CONSENSUS_PERMILLE, CONSENSUS_FILL, CONSENSUS_MIN_COVERED, DEPTH_OUT, DEPTH_MIN, GENES_OUT, QC_OUT, QC_MAX_CYCLES, ALIGN_QC_OUT, ALIGN_QC_MAX_CYCLES, KRAKEN_REPORT, EXTRACT_TAXID, EXTRACT_OUT, EXTRACT_CHILDREN, EXTRACT_PARENTS, EXTRACT_EXCLUDE };
   static const option longopts[] = {
       {"db", required_argument, nullptr, DB}, {"min-alignment-score", required_argument, nullptr, MINSCORE},
@@ -227,6 +232,7 @@ Options parse(int argc, char **argv) {
       {"sam-bam", no_argument, nullptr, SAM_BAM},       // not in the reference: the SAM file as BAM (include/kslam_bam.h)
       // not in the reference: the SAM file as a coordinate-sorted BAM with its BAI index (include/kslam_bamsort.h)
       {"sam-sorted", no_argument, nullptr, SAM_SORTED}, {"sam-index", required_argument, nullptr, SAM_INDEX},
+      {"gunzip", no_argument, nullptr, GUNZIP},   // not in the reference: plain gzip input (include/kslam_gunzip.h)
       {"sam-deflate", required_argument, nullptr, SAM_DEFLATE},   // not in the reference: kslam_set_bgzf_deflate (include/kslam_bgzf.h)
       {"sam-seq", no_argument, nullptr, SAM_SEQ},       // not in the reference: SEQ and QUAL in the SAM file (include/kslam_samseq.h)
       {"sam-unmapped", no_argument, nullptr, SAM_UNMAPPED},   // not in the reference: rows for the reads without alignment (include/kslam_samunmapped.h)
@@ -284,6 +290,7 @@ Options parse(int argc, char **argv) {
       case SAM_BAM: o.sam_bam = true; break;
       case SAM_SORTED: o.sam_sorted = true; break;
       case SAM_INDEX: o.sam_index = optarg; break;
+      case GUNZIP: o.gunzip = true; break;
       case SAM_SEQ: o.sam_seq = true; break;
       case SAM_UNMAPPED: o.sam_unmapped = true; break;
       case CLASSIFIED_OUT: o.classified_out = optarg; break;
@@ -454,14 +461,21 @@ struct FileText {   // a whole file in memory -- page-locked (DMA straight from 
     owner = nullptr;
   }
   // A file that starts with the gzip magic is BGZF: its members are inflated on the GPU (include/kslam_inflate.h), the
-  // compressed bytes are released, and the run goes on with the text.  Plain gzip ends the run with the scan's message.
+  // compressed bytes are released, and the run goes on with the text.  Plain gzip ends the run with the scan's message --
+  // unless --gunzip was given: then it is inflated on the GPU too, from guessed and proven block starts (include/kslam_gunzip.h).
   kslam_ctx *owner = nullptr;   // set: p is the context's page-locked text (kslam_free_pinned)
-  void inflate_if_gzip(kslam_ctx *ctx, const std::string &path) {
+  void inflate_if_gzip(kslam_ctx *ctx, const std::string &path, bool gunzip) {
     if (!good || !kslam_bgzf_is_gzip(p, len)) return;
     uint64_t n_members = 0, text_len = 0;
-    if (kslam_bgzf_scan(p, len, &n_members, &text_len) != KSLAM_OK) die(path + ": " + kslam_tail_last_error());
     char *text = nullptr;
-    if (kslam_bgzf_inflate(ctx, p, len, &text, &text_len) != KSLAM_OK) die(path + ": " + kslam_last_error(ctx));
+    const kslam_status scanned = kslam_bgzf_scan(p, len, &n_members, &text_len);
+    if (scanned == KSLAM_ERR_UNSUPPORTED && gunzip) {
+      if (kslam_gunzip_inflate(ctx, p, len, &text, &text_len) != KSLAM_OK) die(path + ": " + kslam_last_error(ctx));
+    } else {
+      if (scanned != KSLAM_OK)
+        die(path + ": " + kslam_tail_last_error() + (scanned == KSLAM_ERR_UNSUPPORTED ? "; or read it as it is with --gunzip" : ""));
+      if (kslam_bgzf_inflate(ctx, p, len, &text, &text_len) != KSLAM_OK) die(path + ": " + kslam_last_error(ctx));
+    }
     release();
     p = text;
     len = text_len;
@@ -620,8 +634,8 @@ int run(const Options &o, const std::string &command_line) {
     t2.load(r2);
     if (!t2.good) logl("FASTQ file " + r2 + " bad");
   }
-  t1.inflate_if_gzip(ctx, r1);
-  t2.inflate_if_gzip(ctx, r2);
+  t1.inflate_if_gzip(ctx, r1, o.gunzip);
+  t2.inflate_if_gzip(ctx, r2, o.gunzip);
   // ---- outputs ----
   int sam_fd = -1, per_read_fd = -1;
   char *header = nullptr;
